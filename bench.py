@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py - trimodal TriCoLo training samples/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +12,14 @@ the all-gathered global batch, backward, gradient all-reduce, Adam.  `--config 2
 BASELINE.json (Bi(V) B=64, Bi(I) B=64, Tri 64^3 + 12x224^2 + CLIP-text B=64 per GPU).  Synthetic batches are resident
 in HBM before the timed region.  One step = forward + losses + backward + optimizer update; nothing is skipped or cached.
 
-Precision modes, ALL timed by the same invocation at N = 1 (one JSON line):
+A plain run sets up, warms up, times exactly --steps steps of the `--precision` mode (one window) and prints the JSON line; its
+`metric` / `value` / `unit` / `higher_is_better` / `dtype` / `ms_per_step` are the headline, every other measurement is null.
+`--dump-outputs DIR` writes what the last timed step produced: DIR/<loss name>.npy (the step's loss dict), DIR/params_sample.npy (a
+fixed seeded sample of the updated parameters) and DIR/buffers.npy (the BatchNorm statistics), all float32, about 32 MB.
+
+`--full` adds everything below: three timed windows (value = the median one), the other precision modes, the per-kernel roofline
+legs, the data-parallel phase breakdown, the CPU baseline and the config-5 voxel forward.  Precision modes, ALL timed by the same
+`--full` invocation at N = 1 (one JSON line):
   * `value` / `ms_per_step` / `roofline`: the f16 mode - f16 activation storage and MFMA operands, fp32 accumulation,
     bf16x3 heads / GRU.  It is the fastest mode whose embeddings and losses stay within the north star's 1e-3 of the fp32
     reference (asserted by tests/test_gpu_modules.py::test_f16_mode_meets_the_1e3_parity_bound on configs 1, 3, 4, 5).
@@ -338,8 +346,32 @@ def voxel_fwd_roofline(net, batch, B, nrep=3):
             "levels": levels}
 
 
-def run_mode(a, precision, world, rank, device, want_voxel_roofline):
-    """Build the net in one precision mode, capture the step, time K steps, then the per-kernel roofline leg."""
+DUMP_PARAM_SAMPLE = 1 << 23            # parameters written by --dump-outputs: 8 Mi float32 (32 MB), a sample at config 4
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, losses, net):
+    """What the last timed step handed back to its caller, as float32 .npy files: the loss dict, the updated parameters (all of them in
+    named_parameters order, or a fixed seeded sample of DUMP_PARAM_SAMPLE when there are more) and the floating-point buffers."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, k.replace("/", "__") + ".npy"), v.detach().float().cpu().numpy())
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_SAMPLE].sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, "params_sample.npy"), flat.cpu().numpy())
+        bufs = [b.detach().reshape(-1).float() for b in net.buffers() if b.is_floating_point()]
+        if bufs:
+            np.save(os.path.join(out_dir, "buffers.npy"), torch.cat(bufs).cpu().numpy())
+
+
+def run_mode(a, precision, world, rank, device, want_voxel_roofline, full=True, dump_dir=None):
+    """Build the net in one precision mode, capture the step, time K steps (dump the last step's outputs to `dump_dir`), then, with
+    `full`, the data-parallel breakdown and the per-kernel roofline leg."""
     from tricolo_amd import ops, parallel
     net, cfg = build_net(a, precision, device)
     opt = net.configure_optimizers()
@@ -364,7 +396,7 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
         split = parallel.BackwardSplit.for_net(net)
 
     def step(batch):
-        return parallel.dp_training_step(net, batch, opt, split=split)["train_loss/total_loss"]
+        return parallel.dp_training_step(net, batch, opt, split=split)      # the loss dict
 
     def warm_eager():
         s = torch.cuda.Stream()
@@ -406,7 +438,7 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
         if graphs is not None:
             item = graphs[i % len(graphs)]
             if dp_graph:
-                return item.replay()
+                return {"train_loss/total_loss": item.replay()}
             g, l = item
             g.replay()
             return l
@@ -444,15 +476,17 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
             el = float(tmax.item())
         windows.append(el)
     elapsed = sorted(windows)[len(windows) // 2]
-    final_loss = float(loss.item())
+    final_loss = float(loss["train_loss/total_loss"].item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, net)
     nonfinite = ({"skipped_steps": opt.skipped_steps(), "skipped_elements": opt.nonfinite_skipped()} if hasattr(opt, "skipped_steps") else None)
 
     # ---- data-parallel breakdown (N > 1, or TRICOLO_FORCE_DIST=1 in a world of one): the exposed time of the two exchange steps and
     # of the three graph segments, HIP events on this rank's stream, median of 10 replays behind the timed windows; every rank reports
     # (rank 0 gathers the lines) together with the number of ranks the RCCL communicator really spans.
     dp_info = None
-    have_graphs = dp_graph and graphs is not None
-    if dp_graph and world > 1:                       # the leg below holds collectives: every rank must take the same branch
+    have_graphs = full and dp_graph and graphs is not None
+    if full and dp_graph and world > 1:              # the leg below holds collectives: every rank must take the same branch
         ok = torch.tensor([1.0 if have_graphs else 0.0], dtype=torch.float32, device="cpu" if dist.get_backend() == "gloo" else device)
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         have_graphs = have_graphs and float(ok.item()) > 0.5
@@ -477,9 +511,9 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
               f"{med['all_gather']:.3f} ms, all-reduce {med['all_reduce']:.3f} ms", file=sys.stderr, flush=True)
 
     # ---- roofline leg: per-kernel HIP-event timing of eager steps, dominant kernel by time.  Rank 0 records; at N > 1
-    # EVERY rank runs the steps (they contain the collectives - a rank-0-only step would wait for its peers forever).
+    # EVERY rank runs the steps (they contain the collectives - a rank-0-only step would wait for its peers forever).  --full only.
     roof, vox_roof = None, None
-    if rank == 0:
+    if rank == 0 and full:
         ops.TIMER = ops.KernelTimer()
     nprof = 6                          # (eager steps of the leg: 72 launches of the graded family instead of 36 - the run-to-run spread of `frac` was +-3 %)
     # serialise the streams for this leg: a kernel's HIP-event duration must not include the other towers' kernels
@@ -488,16 +522,16 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
     for side_name in ("_side", "_side_ds", "_side_prep"):
         if net.image_encoder is not None and getattr(net.image_encoder, side_name, None) is not None:
             getattr(net.image_encoder, side_name).enabled = False
-    if rank == 0:
+    if rank == 0 and full:
         torch.cuda._sleep(int(20e6))
         ops.TIMER.calibrate()
-    for i in range(nprof):
+    for i in range(nprof if full else 0):
         # park the GPU on a spin kernel first so the host enqueues the whole step ahead of it: the HIP events then
         # bracket back-to-back kernel execution instead of host launch gaps (eager launches cost ~10 us each)
         torch.cuda._sleep(int(60e6))
         step(batches[i % len(batches)])
     torch.cuda.synchronize()
-    if rank == 0:
+    if rank == 0 and full:
         agg = {k: v for k, v in ops.TIMER.summary().items() if k.startswith("conv_")}
         ev_ovh = ops.TIMER.overhead_ms
         ops.TIMER = None
@@ -571,12 +605,12 @@ def run_mode(a, precision, world, rank, device, want_voxel_roofline):
 
 
 def run_mode_in_child(a, mode):
-    """`bench.py --precision <mode> --modes '' --no-cpu-baseline` with this run's workload flags in a child process (a child, not an
-    exec: this process has initialised the GPU); returns the same per-mode object run_mode() does."""
+    """`bench.py --full --precision <mode> --modes '' --no-cpu-baseline` with this run's workload flags in a child process (a child,
+    not an exec: this process has initialised the GPU); returns the same per-mode object run_mode() does."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--precision", mode, "--modes", "", "--no-cpu-baseline", "--steps", str(a.steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--precision", mode, "--modes", "", "--no-cpu-baseline", "--steps", str(a.steps),
            "--warmup", str(a.warmup), "--config", str(a.config), "--per-gpu-batch", str(a.per_gpu_batch),
-           "--resident-batches", str(a.resident_batches), "--preroll", str(a.preroll)]
+           "--resident-batches", str(a.resident_batches), "--preroll", str(a.preroll), "--windows", str(a.windows)]
     for flag, val in (("--voxel-size", a.voxel_size), ("--num-views", a.num_views), ("--image-size", a.image_size)):
         if val is not None:
             cmd += [flag, str(val)]
@@ -638,8 +672,17 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-budget-s", type=float, default=30.0)
     ap.add_argument("--resident-batches", type=int, default=8)
     ap.add_argument("--preroll", type=int, default=40)
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each; value = the median window")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; value = the median window (default: 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other precision modes, the roofline legs, the data-parallel breakdown, the CPU baseline and "
+                         "the config-5 voxel forward (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, a seeded sample of the updated parameters and the BatchNorm buffers "
+                         "as float32 DIR/<name>.npy")
     a = ap.parse_args(argv)
+    if a.windows is None:
+        a.windows = 3 if a.full else 1
     text, image, voxel, V, nv, S, pb = CONFIGS[a.config]
     a.text, a.image, a.voxel = text, image, voxel
     a.voxel_size = a.voxel_size or V
@@ -714,12 +757,14 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=device)
 
-    if a.modes is None:
+    if not a.full:
+        extra = []                                                      # a plain run times the headline mode only
+    elif a.modes is None:
         extra = [m for m in ("bf16x3", "bf16", "f16") if m != a.precision] if world == 1 else []
     else:
         extra = [m for m in a.modes.split(",") if m and m != a.precision]
 
-    head, vox_roof, cfg = run_mode(a, a.precision, world, rank, device, want_voxel_roofline=True)
+    head, vox_roof, cfg = run_mode(a, a.precision, world, rank, device, want_voxel_roofline=True, full=a.full, dump_dir=a.dump_outputs)
     modes = {}
     for m in extra:
         if world == 1 and not dist.is_initialized():
@@ -735,11 +780,11 @@ def main():
             modes[m], _, _ = run_mode(a, m, world, rank, device, want_voxel_roofline=False)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:             # the CPU leg is an N = 1 artefact (task contract)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU leg is an N = 1 artefact (task contract)
         cpu = cpu_baseline(a, cfg)
 
     vox5 = None
-    if rank == 0 and world == 1 and a.config == 4 and not a.no_voxel_config5 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and a.config == 4 and not a.no_voxel_config5 and not a.no_cpu_baseline:
         try:                                                            # (default line only: A/B runs pass --no-cpu-baseline)
             vox5 = voxel_fwd_config5_in_child()
         except Exception as e:                                         # noqa: BLE001  reported, never fatal for the headline
@@ -756,7 +801,7 @@ def main():
             "config": {"workload": workload_name(a), "global_batch": gb, "per_gpu_batch": a.per_gpu_batch, "parallelism": f"dp{world}",
                        "resident_batches": a.resident_batches,
                        "switches": {k: v for k, v in sorted(os.environ.items()) if k.startswith("TRICOLO_")},   # every kernel / tile-rule switch that was set
-                       "precision_mode": a.precision, "hip_graph": head["hip_graph"], "final_loss": head["final_loss"],
+                       "precision_mode": a.precision, "hip_graph": head["hip_graph"], "final_loss": head["final_loss"], "full": a.full,
                        "roofline_3dconv_fwd_primary": "frac_active_rows_raw_events (FLOPs of the active rows over the raw single-launch event times; "
                                                       "`frac` = executed FLOPs on the same times)",
                        "parity": "f16 mode: step-0 losses and embeddings within 1e-3 of the fp32 reference on BASELINE configs 1,3,4,5 "

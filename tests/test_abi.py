@@ -86,3 +86,37 @@ def test_bench_gpus_n_spawns_its_ranks_and_fails_cleanly_without_devices():
         assert r.stderr.count("needs an MI355X") == 2, r.stderr[-2000:]          # one message per spawned rank
     elif torch.cuda.device_count() == 1:
         assert "need 2 devices" in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_plain_run_times_exactly_steps_and_full_keeps_three_windows():
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.full, a.windows, a.steps, a.dump_outputs) == (False, 1, 7, None)     # one window of --steps timed steps
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert (a.full, a.windows, a.dump_outputs) == (True, 3, "d")
+    assert bench.parse_args(["--windows", "2"]).windows == 2
+
+
+def test_bench_dump_outputs_float32_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss dict, the updated parameters (a fixed seeded sample above DUMP_PARAM_SAMPLE) and the
+    floating-point buffers, as float32 .npy files; the same call writes the same arrays."""
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(4, 3), torch.nn.BatchNorm1d(3))
+    losses = {"train_loss/total_loss": torch.tensor(1.5), "train_loss/text_voxel_loss": torch.tensor(0.25)}
+    bench.dump_outputs(str(tmp_path / "all"), losses, net)
+    files = sorted(os.listdir(tmp_path / "all"))
+    assert files == ["buffers.npy", "params_sample.npy", "train_loss__text_voxel_loss.npy", "train_loss__total_loss.npy"]
+    arrs = {f: np.load(tmp_path / "all" / f) for f in files}
+    assert all(v.dtype == np.float32 for v in arrs.values())
+    assert float(arrs["train_loss__total_loss.npy"]) == 1.5
+    flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    np.testing.assert_array_equal(arrs["params_sample.npy"], flat)                  # 21 parameters: below the sample size, all of them
+    assert arrs["buffers.npy"].shape == (6,)                                         # running mean + var; num_batches_tracked is integer
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 10)
+    bench.dump_outputs(str(tmp_path / "s1"), losses, net)
+    bench.dump_outputs(str(tmp_path / "s2"), losses, net)
+    s1, s2 = np.load(tmp_path / "s1" / "params_sample.npy"), np.load(tmp_path / "s2" / "params_sample.npy")
+    assert s1.shape == (10,) and np.array_equal(s1, s2) and np.isin(s1, flat).all()

@@ -7,7 +7,7 @@ out=gpurun_out/ab/$tag.txt; : > $out
 for rep in $(seq 1 ${AB_REPS:-3}); do
   for v in A B; do
     if [ $v = A ]; then e="$A"; else e="$B"; fi
-    line=$(env $e python3 bench.py --modes "" --no-cpu-baseline "$@" 2>gpurun_out/ab/$tag.err | tail -1)
+    line=$(env $e python3 bench.py --full --modes "" --no-cpu-baseline "$@" 2>${out%.txt}.err | tail -1)
     echo "$v [$e] $(echo "$line" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["ms_per_step_windows"]["min"], d["ms_per_step_windows"]["max"], d["value"])')" >> $out
   done
 done

@@ -6,7 +6,7 @@ cp tricolo_amd/libtricolo_hip.so /tmp/new.so
 for i in 1 2 3; do
   for which in new base; do
     if [ $which = base ]; then cp tricolo_amd/libtricolo_hip_base.so tricolo_amd/libtricolo_hip.so; else cp /tmp/new.so tricolo_amd/libtricolo_hip.so; fi
-    python bench.py $AB_ARGS --modes "" --no-cpu-baseline 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$which', b['ms_per_step'], b['ms_per_step_windows']['min'])"
+    python bench.py $AB_ARGS --full --modes "" --no-cpu-baseline 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$which', b['ms_per_step'], b['ms_per_step_windows']['min'])"
   done
 done
 cp /tmp/new.so tricolo_amd/libtricolo_hip.so

@@ -2,7 +2,7 @@
 """MFMA utilisation per kernel from a rocprofv3 PMC pass (north star: "evidenced by rocprof ... MFMA utilisation against gfx950 peak").
 
     cd /tmp && rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d <dir> -- python3 bench.py --steps 3 --warmup 2 \
-        --modes "" --no-cpu-baseline
+        --full --modes "" --no-cpu-baseline
     python tools/pmc_mfma.py <dir> > profiles/r4/pmc_mfma_f16.json
 
 SQ_VALU_MFMA_BUSY_CYCLES counts, summed over all SIMDs, the cycles the matrix pipe was busy (16 per v_mfma_f32_16x16x32_*);

@@ -89,7 +89,7 @@ def main():
     # Adam kernel, one per step)
     steps = max([v["dispatches"] for k, v in kernels.items() if k.startswith("adam_seg_kernel") or k.startswith("adam_kernel")] or [0])
     step_bytes = int(sum((v["fetch_bytes_per_launch"] + v["write_bytes_per_launch"]) * v["dispatches"] for v in kernels.values()) / steps) if steps else None
-    json.dump({"step_bytes": step_bytes, "steps_in_run": steps, "method": f"two rocprofv3 runs of `python3 bench.py --steps 3 --warmup 2 --precision {mode} --modes '' --no-cpu-baseline`, one with "
+    json.dump({"step_bytes": step_bytes, "steps_in_run": steps, "method": f"two rocprofv3 runs of `python3 bench.py --steps 3 --warmup 2 --precision {mode} --full --modes '' --no-cpu-baseline`, one with "
                          "--pmc FETCH_SIZE, one with --pmc WRITE_SIZE (the TCC block cannot hold both); per-kernel mean over all dispatches of "
                          "the run; counter unit KiB; FETCH_SIZE doubled (gfx950 tallies 128-B read requests at 64 B, MI355X_MICROARCH.md "
                          "'HBM'); Infinity-Cache hits are included in both counters, so this is fabric traffic >= HBM traffic; built by "

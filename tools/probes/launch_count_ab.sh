@@ -4,8 +4,8 @@
 N=${1:-8}
 a=(); b=()
 for i in $(seq $N); do
-  x=$(python bench.py --modes "" --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['ms_per_step'])")
-  y=$(TRICOLO_NO_MASK_PYRAMID=1 python bench.py --modes "" --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['ms_per_step'])")
+  x=$(python bench.py --full --modes "" --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['ms_per_step'])")
+  y=$(TRICOLO_NO_MASK_PYRAMID=1 python bench.py --full --modes "" --no-cpu-baseline 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read())['ms_per_step'])")
   echo "pair $i: default $x  +7 launches $y"
   a+=($x); b+=($y)
 done
