@@ -403,6 +403,26 @@ int tri_ntxent_multi_bwd(const float* const* z, int M, int B, int D, float tempe
                          const float* const* dpair, const float* dtotal, float* const* dz, const void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- Triplet loss, semi-hard with a hard fallback (tricolo/loss/triplet.py) ------------------------------------------------ */
+/* loss = mean over S = {(i, j), j != i : d[i][i] < d[i][j] < d[i][i] + margin} of d[i][i] - d[i][j] + margin, over
+ * H = {(i, j), j != i : d[i][j] < d[i][i]} when S is empty, NaN (0 / 0, every gradient NaN) when both are;
+ * d[i][j] = sqrt(max(|zls[j]|^2 - 2 <zls[i], zis[j]> + |zis[i]|^2, 0)) in float64 from the fp32 rows, gradient 0 where d = 0.
+ * Branch and counts are decided on the device.  counts (optional, device int[2]) = (|S|, |H|).  3 launches forward, 1 backward.
+ * 2 <= B <= 4096, 1 <= D <= 2048 (TRI_ERR_UNSUPPORTED otherwise).  dloss: DEVICE scalar, upstream d(total)/d(loss), folded in. */
+size_t tri_triplet_workspace(int B, int D);
+int tri_triplet_fwd(const float* zis, const float* zls, int B, int D, double margin, float* loss, int* counts, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int tri_triplet_bwd(const float* zis, const float* zls, int B, int D, double margin, const float* dloss, float* dzis, float* dzls,
+                    const void* workspace, size_t workspace_bytes, void* stream);
+/* All pairs of a step at once, same contract as tri_ntxent_multi_*: pair (a, b) in itertools.combinations order is
+ * loss(zis = z[a], zls = z[b]); losses [P + 1] = pair losses, then (l0 + l1) + l2 in fp32; counts (optional) [P][2] = (|S|, |H|) per pair.
+ * 2 <= B <= 512, D % 4 == 0, 4 <= D <= 2048 (TRI_ERR_UNSUPPORTED otherwise: use the per-pair calls). */
+size_t tri_triplet_multi_workspace(int M, int B, int D);
+int tri_triplet_multi_fwd(const float* const* z, int M, int B, int D, double margin, float* losses, int* counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int tri_triplet_multi_bwd(const float* const* z, int M, int B, int D, double margin, const float* const* dpair, const float* dtotal,
+                          float* const* dz, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Adam (torch.optim.Adam as instantiated by config/config.yaml:50-53, tricolo_net.py:43-44) ------------------------ */
 /* `step` is a DEVICE int[4]: [0] optimizer steps applied (the t of the bias corrections; tri_adam_tick adds one), [1] the running count
  * of gradient elements the update kernels skipped because they were inf / NaN (per-element fallback: such an element leaves p, m and v

@@ -44,7 +44,7 @@ class TriConvBnSums(C.Structure):
 TRI_WGRAD_JOBS_MAX = 12
 TRI_ERR_ARG, TRI_ERR_UNSUPPORTED = -1, -2                   # common.h
 
-P, I, L, F, Z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
+P, I, L, F, Z, DBL = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
 DP = C.POINTER(TriConvDesc)
 
 # name -> (restype, argtypes); must list every symbol of include/tricolo_hip.h (checked by tests/test_abi.py)
@@ -139,6 +139,12 @@ SIGNATURES = {
     "tri_ntxent_multi_workspace": (Z, [I, I, I]),
     "tri_ntxent_multi_fwd": (I, [P, I, I, I, F, F, I, P, P, Z, P]),
     "tri_ntxent_multi_bwd": (I, [P, I, I, I, F, F, I, P, P, P, P, Z, P]),
+    "tri_triplet_workspace": (Z, [I, I]),
+    "tri_triplet_fwd": (I, [P, P, I, I, DBL, P, P, P, Z, P]),
+    "tri_triplet_bwd": (I, [P, P, I, I, DBL, P, P, P, P, Z, P]),
+    "tri_triplet_multi_workspace": (Z, [I, I, I]),
+    "tri_triplet_multi_fwd": (I, [P, I, I, I, DBL, P, P, P, Z, P]),
+    "tri_triplet_multi_bwd": (I, [P, I, I, I, DBL, P, P, P, P, Z, P]),
     "tri_copy_segments": (I, [P, P, P, I, P]),
     "tri_gru_bias_grads": (I, [P, I, P, P, P, P, P]),
     "tri_adam_tick": (I, [P, P]),

@@ -17,8 +17,9 @@ Known differences, handled explicitly:
     every `tricolo_amd.*` target rewritten to its `tricolo.*` counterpart (FusedAdam -> torch.optim.Adam) as a DictConfig when
     omegaconf is importable (it is wherever the reference runs), else as a plain nested dict that `OmegaConf.create()` turns into
     one - in that case only the `state_dict` / `optimizer_states` halves are directly consumable by the reference;
-  * CLIPImageEncoder and TripletLoss (config.yaml:83-96) are outside the hot path and are not built: a config that names
-    them raises in tricolo_amd.config.instantiate (no such class under tricolo_amd), it does not load silently.
+  * CLIPImageEncoder (config.yaml:86-89) is outside the hot path and is not built: a config that names it raises in
+    tricolo_amd.config.instantiate (no such class under tricolo_amd), it does not load silently.  TripletLoss (config.yaml:102-104) is
+    built (tricolo_amd.loss.triplet) and maps to tricolo.loss.triplet.TripletLoss like every other target.
 Pure host code: no kernel is involved.
 """
 from __future__ import annotations

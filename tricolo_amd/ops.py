@@ -1416,6 +1416,61 @@ def ntxent_fwd_bwd(za, zb, temperature, alpha, norm=True, want_grad=True):
     return loss, dza, dzb
 
 
+# ------------------------------------------------------------------------------------------------ Triplet loss
+def triplet_fwd(zis, zls, margin):
+    """Loss only; returns (loss, counts int32 [2] = (|S|, |H|), workspace) - hand the workspace to triplet_bwd."""
+    B, D = zis.shape
+    loss = torch.empty((), dtype=torch.float32, device=zis.device)
+    counts = torch.empty((2,), dtype=torch.int32, device=zis.device)
+    nbytes = lib().tri_triplet_workspace(B, D)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=zis.device)
+    check(lib().tri_triplet_fwd(ptr(_f32(zis)), ptr(_f32(zls)), B, D, float(margin), ptr(loss), ptr(counts), ptr(ws), nbytes, stream()),
+          "tri_triplet_fwd")
+    return loss, counts, ws
+
+
+def triplet_bwd(zis, zls, ws, margin, dloss):
+    """(dzis, dzls) times the upstream scalar dloss (device tensor) in one launch."""
+    B, D = zis.shape
+    dzis, dzls = torch.empty_like(zis), torch.empty_like(zls)
+    check(lib().tri_triplet_bwd(ptr(_f32(zis)), ptr(_f32(zls)), B, D, float(margin), ptr(_f32(dloss)), ptr(dzis), ptr(dzls), ptr(ws),
+                                ws.numel(), stream()), "tri_triplet_bwd")
+    return dzis, dzls
+
+
+def triplet_multi_supported(B: int, D: int, M: int) -> bool:
+    return M in (2, 3) and 2 <= B <= 512 and 4 <= D <= 2048 and D % 4 == 0
+
+
+def triplet_multi_fwd(zs, margin):
+    """Every pair of the M = 2 / 3 embeddings `zs` at once: (losses [P + 1] = pair losses in combination order, then their
+    sum; counts int32 [P, 2] = (|S|, |H|) per pair; workspace for triplet_multi_bwd)."""
+    M = len(zs)
+    B, D = zs[0].shape
+    P = M * (M - 1) // 2
+    losses = torch.empty((P + 1,), dtype=torch.float32, device=zs[0].device)
+    counts = torch.empty((P, 2), dtype=torch.int32, device=zs[0].device)
+    nbytes = lib().tri_triplet_multi_workspace(M, B, D)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=zs[0].device)
+    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
+    check(lib().tri_triplet_multi_fwd(zp, M, B, D, float(margin), ptr(losses), ptr(counts), ptr(ws), nbytes, stream()), "tri_triplet_multi_fwd")
+    return losses, counts, ws
+
+
+def triplet_multi_bwd(zs, ws, margin, dpairs=None, dtotal=None):
+    """Gradients of all M embeddings in one launch; dpairs (list of 0-d device tensors or None) / dtotal are the upstream
+    gradients of the pair losses / of their sum."""
+    M = len(zs)
+    B, D = zs[0].shape
+    P = M * (M - 1) // 2
+    dzs = [torch.empty_like(z) for z in zs]
+    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
+    dp = (_C.C.c_void_p * P)(*[ptr(d) for d in dpairs]) if dpairs is not None else None
+    dzp = (_C.C.c_void_p * M)(*[ptr(d) for d in dzs])
+    check(lib().tri_triplet_multi_bwd(zp, M, B, D, float(margin), dp, ptr(dtotal), dzp, ptr(ws), ws.numel(), stream()), "tri_triplet_multi_bwd")
+    return dzs
+
+
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_tick(step):
     check(lib().tri_adam_tick(ptr(step), stream()), "tri_adam_tick")
