@@ -423,6 +423,24 @@ int tri_triplet_multi_fwd(const float* const* z, int M, int B, int D, double mar
 int tri_triplet_multi_bwd(const float* const* z, int M, int B, int D, double margin, const float* const* dpair, const float* dtotal,
                           float* const* dz, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Shape F1 / chamfer distance on point clouds (calculate_f1.py: knn_points(K=1) both ways, F1 at a distance) -------------- */
+/* Batched one-sided nearest neighbour.  P [N][S1][3], Q [N][S2][3] fp32 contiguous (p_shared / q_shared != 0: that side is ONE
+ * cloud [S][3] used for every n).  len_p / len_q (optional, device int64 [N]): rows at and beyond a length are padding and are never
+ * read.  d2 [N][S1] = the smallest (ax-bx)^2 + (ay-by)^2 + (az-bz)^2 (fp32, formed from the differences) over the valid points of
+ * Q[n]; idx (optional, int64 [N][S1]) = the lowest index that attains it.  Padding rows are written as 0 / -1, an empty Q[n]
+ * gives +inf / -1.  Any S1, S2 in 0 .. 2^28, any N >= 0 (large batches are split over launches).  Bit-reproducible. */
+int tri_nn_dist2(const float* P, const float* Q, const long* len_p, const long* len_q, int N, int S1, int S2, int p_shared, int q_shared,
+                 float* d2, long* idx, void* stream);
+/* Per cloud n: counts [N][T] (int) = valid points with sqrtf(d2) < thresholds[k] (thresholds: HOST array of T <= 8 floats), sums [N] =
+ * fp32 sum of d2 over the valid points in a fixed order.  One launch. */
+#define TRI_F1_MAX_THRESHOLDS 8
+int tri_f1_counts(const float* d2, const long* lengths, int N, int S, const float* thresholds, int T, int* counts, float* sums, void* stream);
+/* precision [T][N] = 100 * (count_p / len_p), recall [T][N] = 100 * (count_q / len_q), f1 = (2 * precision * recall) / (precision +
+ * recall + eps), chamfer [N] (optional) = sum_p / len_p + sum_q / len_q: fp32, the reference's order of operations, correctly rounded
+ * divisions.  Lengths default to S1 / S2; a length of 0 gives NaN (the mean of nothing), as the reference would. */
+int tri_f1_finalize(const int* count_p, const int* count_q, const float* sum_p, const float* sum_q, const long* len_p, const long* len_q,
+                    int N, int S1, int S2, int T, float eps, float* precision, float* recall, float* f1, float* chamfer, void* stream);
+
 /* ---- Adam (torch.optim.Adam as instantiated by config/config.yaml:50-53, tricolo_net.py:43-44) ------------------------ */
 /* `step` is a DEVICE int[4]: [0] optimizer steps applied (the t of the bias corrections; tri_adam_tick adds one), [1] the running count
  * of gradient elements the update kernels skipped because they were inf / NaN (per-element fallback: such an element leaves p, m and v

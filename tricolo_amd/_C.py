@@ -145,6 +145,9 @@ SIGNATURES = {
     "tri_triplet_multi_workspace": (Z, [I, I, I]),
     "tri_triplet_multi_fwd": (I, [P, I, I, I, DBL, P, P, P, Z, P]),
     "tri_triplet_multi_bwd": (I, [P, I, I, I, DBL, P, P, P, P, Z, P]),
+    "tri_nn_dist2": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
+    "tri_f1_counts": (I, [P, P, I, I, C.POINTER(F), I, P, P, P]),
+    "tri_f1_finalize": (I, [P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
     "tri_copy_segments": (I, [P, P, P, I, P]),
     "tri_gru_bias_grads": (I, [P, I, P, P, P, P, P]),
     "tri_adam_tick": (I, [P, P]),

@@ -1471,6 +1471,64 @@ def triplet_multi_bwd(zs, ws, margin, dpairs=None, dtotal=None):
     return dzs
 
 
+# ------------------------------------------------------------------------------------------------ shape F1 / chamfer
+def _cloud_lengths(lengths, N, device):
+    if lengths is None:
+        return None
+    if lengths.dtype != torch.int64 or lengths.shape != (N,) or lengths.device != device or not lengths.is_contiguous():
+        raise ValueError(f"lengths must be a contiguous int64 tensor of shape ({N},) on {device}")
+    return lengths
+
+
+def _cloud(x, name):
+    if x.dim() != 3 or x.shape[-1] != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 tensor of shape [N, S, 3], got {tuple(x.shape)} {x.dtype}"
+                         + ("" if x.is_contiguous() else " (not contiguous)"))
+    return x
+
+
+def nn_dist2(p, q, lengths_p=None, lengths_q=None, return_idx=False):
+    """p [N, S1, 3], q [N, S2, 3] fp32 on the GPU (either side may have batch 1: shared by all N) -> d2 [N, S1] fp32, the squared
+    distance of every valid point of p[n] to its nearest valid point of q[n], and with return_idx the int64 index of that point.
+    lengths_* (int64 [N]): rows at and beyond a length are padding (outputs 0 / -1)."""
+    _cloud(p, "p"), _cloud(q, "q")
+    N = max(p.shape[0], q.shape[0])
+    if p.shape[0] not in (1, N) or q.shape[0] not in (1, N) or p.shape[0] == 0 or q.shape[0] == 0:
+        raise ValueError(f"batch sizes {p.shape[0]} and {q.shape[0]} do not match (one side may be 1)")
+    S1, S2 = p.shape[1], q.shape[1]
+    lengths_p, lengths_q = _cloud_lengths(lengths_p, N, p.device), _cloud_lengths(lengths_q, N, p.device)
+    d2 = torch.empty((N, S1), dtype=torch.float32, device=p.device)
+    idx = torch.empty((N, S1), dtype=torch.int64, device=p.device) if return_idx else None
+    check(lib().tri_nn_dist2(ptr(p), ptr(q), ptr(lengths_p), ptr(lengths_q), N, S1, S2, int(p.shape[0] == 1 and N > 1),
+                             int(q.shape[0] == 1 and N > 1), ptr(d2), ptr(idx), stream()), "tri_nn_dist2")
+    return (d2, idx) if return_idx else d2
+
+
+def f1_counts(d2, thresholds, lengths=None):
+    """d2 [N, S] fp32 -> (counts int32 [N, T] of valid points with sqrt(d2) < t, sums fp32 [N] of d2 over the valid points)."""
+    N, S = d2.shape
+    T = len(thresholds)
+    if not 1 <= T <= 8:
+        raise ValueError("1 to 8 thresholds")
+    counts = torch.empty((N, T), dtype=torch.int32, device=d2.device)
+    sums = torch.empty((N,), dtype=torch.float32, device=d2.device)
+    thr = (_C.C.c_float * T)(*[float(t) for t in thresholds])
+    check(lib().tri_f1_counts(ptr(_f32(d2)), ptr(_cloud_lengths(lengths, N, d2.device)), N, S, thr, T, ptr(counts), ptr(sums), stream()),
+          "tri_f1_counts")
+    return counts, sums
+
+
+def f1_finalize(count_p, count_q, sum_p, sum_q, S1, S2, eps, lengths_p=None, lengths_q=None):
+    """(precision, recall, f1) fp32 [T, N] and chamfer fp32 [N] from the counts and sums of both directions."""
+    N, T = count_p.shape
+    out = torch.empty((3, T, N), dtype=torch.float32, device=count_p.device)
+    chamfer = torch.empty((N,), dtype=torch.float32, device=count_p.device)
+    check(lib().tri_f1_finalize(ptr(count_p), ptr(count_q), ptr(sum_p), ptr(sum_q), ptr(_cloud_lengths(lengths_p, N, count_p.device)),
+                                ptr(_cloud_lengths(lengths_q, N, count_p.device)), N, S1, S2, T, float(eps), ptr(out[0]), ptr(out[1]),
+                                ptr(out[2]), ptr(chamfer), stream()), "tri_f1_finalize")
+    return out[0], out[1], out[2], chamfer
+
+
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_tick(step):
     check(lib().tri_adam_tick(ptr(step), stream()), "tri_adam_tick")
