@@ -441,6 +441,32 @@ int tri_f1_counts(const float* d2, const long* lengths, int N, int S, const floa
 int tri_f1_finalize(const int* count_p, const int* count_q, const float* sum_p, const float* sum_q, const long* len_p, const long* len_q,
                     int N, int S1, int S2, int T, float eps, float* precision, float* recall, float* f1, float* chamfer, void* stream);
 
+/* ---- Mesh surface sampling (calculate_f1.py: Meshes.get_bounding_boxes, scale_verts, sample_points_from_meshes) ---------------- */
+/* A packed batch of N triangle meshes: verts [sumV][3] fp32, faces [sumF][3] int32 vertex indices LOCAL to their mesh, vert_off /
+ * face_off device int64 [N + 1] (first 0, ascending), scale (optional, device fp32 [N]): one factor per mesh, applied to the vertices
+ * as fl32(v * scale[n]) before anything else, as the reference scales its meshes before it samples them.  A vertex index outside the
+ * mesh is clamped to the mesh's own vertices (callers validate on the host; the kernels never read beyond the mesh).
+ *
+ * tri_mesh_bbox replaces gt_meshes.get_bounding_boxes() (calculate_f1.py:90): bbox [N][3][2] fp32 = per-axis (min, max) over ALL
+ * vertices of the mesh, referenced by a face or not; a mesh without vertices gives zeros.  Not scaled. */
+int tri_mesh_bbox(const float* verts, const long* vert_off, int N, float* bbox, void* stream);
+/* The face-area CDF that sample_points_from_meshes (calculate_f1.py:125) draws its faces from: area = 0.5 * |(b - a) x (c - a)| in fp32
+ * on the scaled vertices, cdf [sumF] float64 = the inclusive prefix sum of the areas per mesh, total [N] float64 = its last entry (0
+ * for a mesh without faces).  Summed in float64 in 2,048-face chunks counted from the mesh's first face (chunk sums, a serial chain
+ * over the sums, apply): the bits depend on the mesh alone, the CDF never decreases and a face of area 0 repeats the entry before it
+ * exactly.  max_faces: at least the largest face count of the batch (it sizes the grid), below 2^31.  No atomics; bit-reproducible. */
+int tri_mesh_face_cdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale, int N,
+                      long max_faces, double* cdf, double* total, void* stream);
+/* Replaces sample_points_from_meshes(meshes, S) (calculate_f1.py:125; normals are not produced).  For mesh n and sample s:
+ * Philox4x32-10, key = (low, high 32 bits of seed), counter = (s, n, 0, 0) -> x0..x3; u_f = (x0 >> 8) * 2^-24, u1, u2 likewise from x1,
+ * x2; the face is the smallest f with cdf[f] > u_f * total[n] (float64; a face of area 0 is never chosen); with r = sqrtf(u1) the point is
+ * (1 - r) a + r (1 - u2) b + r u2 c in fp32 on the scaled vertices.  points [N][S][3] fp32, face_idx (optional) int64 [N][S], local
+ * to the mesh.  A mesh without faces or with total area 0 gives zero rows and -1.  Row (n, s) depends on (seed, n, s) and the mesh
+ * only - not on S, the launch shape or the other meshes.  Large batches are split over launches. */
+int tri_mesh_sample_points(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale,
+                           const double* cdf, const double* total, int N, int S, unsigned long long seed, float* points, long* face_idx,
+                           void* stream);
+
 /* ---- Adam (torch.optim.Adam as instantiated by config/config.yaml:50-53, tricolo_net.py:43-44) ------------------------ */
 /* `step` is a DEVICE int[4]: [0] optimizer steps applied (the t of the bias corrections; tri_adam_tick adds one), [1] the running count
  * of gradient elements the update kernels skipped because they were inf / NaN (per-element fallback: such an element leaves p, m and v

@@ -148,6 +148,9 @@ SIGNATURES = {
     "tri_nn_dist2": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
     "tri_f1_counts": (I, [P, P, I, I, C.POINTER(F), I, P, P, P]),
     "tri_f1_finalize": (I, [P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
+    "tri_mesh_bbox": (I, [P, P, I, P, P]),
+    "tri_mesh_face_cdf": (I, [P, P, P, P, P, I, L, P, P, P]),
+    "tri_mesh_sample_points": (I, [P, P, P, P, P, P, P, I, I, C.c_ulonglong, P, P, P]),
     "tri_copy_segments": (I, [P, P, P, I, P]),
     "tri_gru_bias_grads": (I, [P, I, P, P, P, P, P]),
     "tri_adam_tick": (I, [P, P]),

@@ -7,10 +7,15 @@ five launches from points to F1, nothing comes back to the host in between).  On
 chunked torch fallback with the same arithmetic (fp32, distances from the differences); it exists so that the interface and
 the F1 formula can be used and tested without a GPU and is not tuned.
 
-The feature starts where the reference's point_cache/*.npy starts: loading OBJ meshes and sampling their surfaces
-(pytorch3d's sample_points_from_meshes) is not part of this package.
+Clouds come from the reference's point_cache/*.npy format.  A shape without a cached cloud is loaded from its
+model_normalized.obj, scaled and sampled by tricolo_amd.evaluation.mesh (csrc/mesh_sample.hip on the GPU) and written to the cache
+when --mesh-root / --category-map are given; without them only an existing cache is read, as before.
 
-    python -m tricolo_amd.evaluation.shape_f1 nearest.jsonl --point-cache DIR
+One deliberate difference from the reference: it scales a retrieved shape by the gt-10 factor of whichever ground truth it met
+first (10 worker processes race for the cache); here a cached cloud always carries its OWN gt-10 factor - deterministic, and what the
+reference writes for every shape that occurs as a ground truth.  mesh.compare_meshes keeps the reference's pair semantics.
+
+    python -m tricolo_amd.evaluation.shape_f1 nearest.jsonl --point-cache DIR [--mesh-root ShapeNetCore.v2 --category-map val_map.json]
 """
 import argparse
 import json
@@ -157,10 +162,46 @@ def _load_cloud(path):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
 
 
-def shape_f1_from_nearest(nearest_path, point_cache_dir, threshold=0.1, batch=64, rescale=False, device=None):
+def _load_category_map(category_map):
+    if category_map is None or isinstance(category_map, dict):
+        return category_map or {}
+    with open(category_map) as f:                                                   # the reference's val_map.json
+        return {item["model_id"]: item["category"] for item in json.load(f)}
+
+
+def fill_point_cache(model_ids, point_cache_dir, mesh_root, category_map, num_samples=10000, seed=0, batch=64, device=None):
+    """Sample <mesh_root>/<category_map[id]>/<id>/models/model_normalized.obj for every id that has a mesh but no <dir>/<id>.npy
+    and write the cloud as float32 [1, S, 3] (the reference's format), scaled to a longest bounding-box edge of 10 ("gt-10" on the
+    mesh's own box).  Ids are taken in sorted order, `batch` meshes per launch; returns the ids written."""
+    from . import mesh as _mesh
+    if device is None:
+        device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    amap = _load_category_map(category_map)
+    todo = []
+    for mid in sorted(set(model_ids)):
+        if mid in amap and not os.path.exists(os.path.join(point_cache_dir, mid + ".npy")):
+            obj = os.path.join(mesh_root, amap[mid], mid, "models", "model_normalized.obj")
+            if os.path.exists(obj):
+                todo.append((mid, obj))
+    if todo:
+        os.makedirs(point_cache_dir, exist_ok=True)
+    for b0 in range(0, len(todo), batch):
+        chunk = todo[b0:b0 + batch]
+        meshes = [_mesh.load_obj(obj) for _, obj in chunk]
+        points = _mesh.sample_points_from_meshes([m[0] for m in meshes], [m[1] for m in meshes], num_samples, seed, "gt-10",
+                                                 device=device).cpu().numpy()
+        for i, (mid, _) in enumerate(chunk):
+            np.save(os.path.join(point_cache_dir, mid + ".npy"), points[i:i + 1])
+    return [mid for mid, _ in todo]
+
+
+def shape_f1_from_nearest(nearest_path, point_cache_dir, threshold=0.1, batch=64, rescale=False, device=None, mesh_root=None,
+                          category_map=None, num_samples=10000, seed=0):
     """What calculate_f1.py's main does: for every record of nearest.jsonl (as compute_metrics(nearest_path=...) writes it) the F1 of
-    <dir>/<retrieved_models[0]>.npy against <dir>/<groundtruth.split("-")[0]>.npy.  Records whose clouds are not in the directory are
-    skipped and counted.  Returns {"mean_f1", "f1" (one value per record kept), "records" (their line numbers), "skipped"}."""
+    <dir>/<retrieved_models[0]>.npy against <dir>/<groundtruth.split("-")[0]>.npy.  With mesh_root (and category_map: a dict
+    model id -> category, or the path of the reference's val_map.json) a shape without a cloud is first sampled from its
+    model_normalized.obj into the directory (fill_point_cache).  Records with a shape that has neither a cloud nor a mesh are skipped
+    and counted.  Returns {"mean_f1", "f1" (one value per record kept), "records" (their line numbers), "skipped"}."""
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     pairs = []
@@ -169,6 +210,8 @@ def shape_f1_from_nearest(nearest_path, point_cache_dir, threshold=0.1, batch=64
             if line.strip():
                 rec = json.loads(line)
                 pairs.append((line_no, rec["retrieved_models"][0], rec["groundtruth"].split("-")[0]))
+    if mesh_root is not None:
+        fill_point_cache([mid for pr in pairs for mid in pr[1:]], point_cache_dir, mesh_root, category_map, num_samples, seed, batch, device)
     have = lambda mid: os.path.exists(os.path.join(point_cache_dir, mid + ".npy"))            # noqa: E731
     kept = [pr for pr in pairs if have(pr[1]) and have(pr[2])]
     clouds, values = {}, []
@@ -207,10 +250,16 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=0.1)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--rescale", action="store_true", help="apply the gt-10 scale to the clouds (cached clouds already carry it)")
+    ap.add_argument("--mesh-root", default=None, help="ShapeNetCore.v2 directory: shapes without a cloud are sampled from "
+                    "<root>/<category>/<id>/models/model_normalized.obj into the point cache")
+    ap.add_argument("--category-map", default=None, help="val_map.json of the reference: a list of {model_id, category}")
+    ap.add_argument("--num-samples", type=int, default=10000, help="points per sampled mesh")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the surface sampler")
     a = ap.parse_args(argv)
-    r = shape_f1_from_nearest(a.nearest, a.point_cache, a.threshold, a.batch, a.rescale)
+    r = shape_f1_from_nearest(a.nearest, a.point_cache, a.threshold, a.batch, a.rescale, mesh_root=a.mesh_root,
+                              category_map=a.category_map, num_samples=a.num_samples, seed=a.seed)
     if r["skipped"]:
-        print(f"skipped {r['skipped']} of {r['skipped'] + len(r['f1'])} records: point cloud not in {a.point_cache}")
+        print(f"skipped {r['skipped']} of {r['skipped'] + len(r['f1'])} records: neither a point cloud in {a.point_cache} nor a mesh")
     print(r["mean_f1"])
 
 

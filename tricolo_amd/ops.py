@@ -1529,6 +1529,72 @@ def f1_finalize(count_p, count_q, sum_p, sum_q, S1, S2, eps, lengths_p=None, len
     return out[0], out[1], out[2], chamfer
 
 
+# ------------------------------------------------------------------------------------------------ mesh surface sampling
+def _mesh_arg(x, name, dtype, shape_tail=None, numel=None):
+    if x.dtype != dtype or not x.is_contiguous() or (shape_tail is not None and (x.dim() != 2 or x.shape[1] != shape_tail)) or \
+            (numel is not None and x.shape != (numel,)):
+        want = f"[*, {shape_tail}]" if shape_tail is not None else f"[{numel}]"
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {want}, got {tuple(x.shape)} {x.dtype}"
+                         + ("" if x.is_contiguous() else " (not contiguous)"))
+    return x
+
+
+def _mesh_batch(verts, faces, vert_off, face_off, scale):
+    """The packed batch of csrc/mesh_sample.hip: verts fp32 [sumV, 3], faces int32 [sumF, 3] (local indices), offsets int64 [N + 1]."""
+    for x in (verts, faces, vert_off, face_off, scale):
+        ptr(x)                                                                   # host tensors: "no CPU fallback"
+    _mesh_arg(verts, "verts", torch.float32, 3)
+    if faces is not None:
+        _mesh_arg(faces, "faces", torch.int32, 3)
+    N = vert_off.numel() - 1
+    if N < 0:
+        raise ValueError("vert_off must hold N + 1 offsets")
+    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
+    if face_off is not None:
+        _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
+    if scale is not None:
+        _mesh_arg(scale, "scale", torch.float32, numel=N)
+    return N
+
+
+def mesh_bbox(verts, vert_off):
+    """verts fp32 [sumV, 3], vert_off int64 [N + 1] on the GPU -> bbox fp32 [N, 3, 2]: per-axis (min, max) over all vertices of a mesh."""
+    N = _mesh_batch(verts, None, vert_off, None, None)
+    bbox = torch.empty((N, 3, 2), dtype=torch.float32, device=verts.device)
+    check(lib().tri_mesh_bbox(ptr(verts), ptr(vert_off), N, ptr(bbox), stream()), "tri_mesh_bbox")
+    return bbox
+
+
+def mesh_face_cdf(verts, faces, vert_off, face_off, scale=None, max_faces=None):
+    """-> (cdf float64 [sumF], total float64 [N]): the per-mesh inclusive prefix sum of the fp32 face areas of the scaled meshes.
+    max_faces: the largest face count of the batch when the caller knows it (saves reading face_off back)."""
+    N = _mesh_batch(verts, faces, vert_off, face_off, scale)
+    if max_faces is None:
+        max_faces = int((face_off[1:] - face_off[:-1]).max()) if N else 0
+    cdf = torch.empty((faces.shape[0],), dtype=torch.float64, device=verts.device)
+    total = torch.empty((N,), dtype=torch.float64, device=verts.device)
+    check(lib().tri_mesh_face_cdf(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(scale), N, int(max_faces), ptr(cdf), ptr(total),
+                                  stream()), "tri_mesh_face_cdf")
+    return cdf, total
+
+
+def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples, seed=0, scale=None, return_face_idx=False):
+    """num_samples area-weighted surface points per mesh -> points fp32 [N, S, 3] (and face_idx int64 [N, S], local to the mesh): row
+    (n, s) is a function of (seed, n, s) and mesh n alone.  cdf / total: mesh_face_cdf's, taken with the same scale."""
+    N = _mesh_batch(verts, faces, vert_off, face_off, scale)
+    ptr(cdf), ptr(total)
+    _mesh_arg(cdf, "cdf", torch.float64, numel=faces.shape[0])
+    _mesh_arg(total, "total", torch.float64, numel=N)
+    S = int(num_samples)
+    if S < 0:
+        raise ValueError("num_samples must not be negative")
+    points = torch.empty((N, S, 3), dtype=torch.float32, device=verts.device)
+    idx = torch.empty((N, S), dtype=torch.int64, device=verts.device) if return_face_idx else None
+    check(lib().tri_mesh_sample_points(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(scale), ptr(cdf), ptr(total), N, S,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(points), ptr(idx), stream()), "tri_mesh_sample_points")
+    return (points, idx) if return_face_idx else points
+
+
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_tick(step):
     check(lib().tri_adam_tick(ptr(step), stream()), "tri_adam_tick")
