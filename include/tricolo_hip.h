@@ -467,6 +467,17 @@ int tri_mesh_sample_points(const float* verts, const int* faces, const long* ver
                            const double* cdf, const double* total, int N, int S, unsigned long long seed, float* points, long* face_idx,
                            void* stream);
 
+/* ---- Bicubic antialiased resize of u8 renderings (general_dataset.py:63-65: Resize(image_size, BICUBIC, antialias=True)) ------- */
+/* in [planes][Hin][Win] u8 -> out [planes][Hout][Wout] u8, both contiguous: cast to fp32, the separable bicubic (a = -0.5) antialias
+ * filter of ATen's _upsample_bicubic2d_aa (width pass first; per axis scale = n_in / n_out, support = 2 max(scale, 1), windows clipped
+ * at the borders and renormalised), clamp to [0, 255], round half to even.  Any sizes, down and up; Hin == Hout && Win == Wout copies.
+ * fp32 accumulation in tap order, no atomics: bit-reproducible.  workspace: tri_resize_bicubic_aa_workspace(...) bytes of device
+ * memory, 16-byte aligned (the per-axis window / weight tables, written by the call).  TRI_ERR_UNSUPPORTED when one output row's
+ * window and the tables exceed 64 KiB of LDS (nothing is truncated). */
+size_t tri_resize_bicubic_aa_workspace(int Hin, int Win, int Hout, int Wout);
+int tri_resize_bicubic_aa_u8(const uint8_t* in, int planes, int Hin, int Win, uint8_t* out, int Hout, int Wout, void* workspace,
+                             void* stream);
+
 /* ---- Adam (torch.optim.Adam as instantiated by config/config.yaml:50-53, tricolo_net.py:43-44) ------------------------ */
 /* `step` is a DEVICE int[4]: [0] optimizer steps applied (the t of the bias corrections; tri_adam_tick adds one), [1] the running count
  * of gradient elements the update kernels skipped because they were inf / NaN (per-element fallback: such an element leaves p, m and v

@@ -1176,6 +1176,47 @@ def nchw3_u8_to_nhwc4(x_u8, dtype=torch.float32, mean=None, std=None):
     return out
 
 
+def resize_output_size(H: int, W: int, size):
+    """torchvision Resize's size rule: (h, w) as given, an int = the short edge becomes `size`, the long edge int(size * long / short)."""
+    if isinstance(size, (tuple, list)):
+        if len(size) == 1:
+            return resize_output_size(H, W, int(size[0]))
+        if len(size) != 2:
+            raise ValueError(f"size must be an int or (H, W), got {size!r}")
+        return int(size[0]), int(size[1])
+    short, long = (W, H) if W <= H else (H, W)
+    new_short, new_long = int(size), int(int(size) * long / short)
+    return (new_long, new_short) if W <= H else (new_short, new_long)
+
+
+def resize_bicubic_aa_u8(x_u8, size):
+    """u8 [..., H, W] -> u8 [..., Hout, Wout]: torchvision's Resize(size, BICUBIC, antialias=True) on a uint8 tensor
+    (general_dataset.py:63-65) = float32, F.interpolate(mode="bicubic", align_corners=False, antialias=True), clamp(0, 255), round
+    half to even, uint8.  GPU tensors run csrc/resize.hip; host tensors take that torch expression (the loader stays usable and
+    testable without a GPU), as the mesh-sampling and chamfer ops split."""
+    if x_u8.dtype != torch.uint8:
+        raise ValueError(f"resize_bicubic_aa_u8 takes a uint8 tensor, got {x_u8.dtype}")
+    if x_u8.dim() < 2:
+        raise ValueError(f"resize_bicubic_aa_u8 takes [..., H, W], got {tuple(x_u8.shape)}")
+    H, W = int(x_u8.shape[-2]), int(x_u8.shape[-1])
+    Ho, Wo = resize_output_size(H, W, size)
+    if min(H, W, Ho, Wo) <= 0:
+        raise ValueError(f"resize_bicubic_aa_u8: empty image {H}x{W} -> {Ho}x{Wo}")
+    lead = tuple(x_u8.shape[:-2])
+    if not x_u8.is_cuda:
+        x4 = x_u8 if x_u8.dim() == 4 else x_u8.reshape(1, -1, H, W)
+        y = torch.nn.functional.interpolate(x4.to(torch.float32), size=(Ho, Wo), mode="bicubic", align_corners=False, antialias=True)
+        return y.clamp(0, 255).round().to(torch.uint8).reshape(lead + (Ho, Wo))
+    x = x_u8.contiguous()
+    out = torch.empty(lead + (Ho, Wo), dtype=torch.uint8, device=x.device)
+    planes = x.numel() // (H * W)
+    if planes >= 1 << 31:
+        raise ValueError("resize_bicubic_aa_u8: 2^31 or more planes")
+    ws = torch.empty((max(16, lib().tri_resize_bicubic_aa_workspace(H, W, Ho, Wo)),), dtype=torch.uint8, device=x.device)
+    check(lib().tri_resize_bicubic_aa_u8(ptr(x), planes, H, W, ptr(out), Ho, Wo, ptr(ws), stream()), "tri_resize_bicubic_aa_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ row ops
 def l2norm_fwd(x, eps=1e-12):
     rows, D = x.shape

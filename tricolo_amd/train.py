@@ -9,6 +9,12 @@ Lightning installed, use the reference's own train.py with the `_target_` overri
 
     python -m tricolo_amd.train data=synthetic model.text_encoder=BiGRUEncoder model.voxel_encoder=SparseCNNEncoder \
         experiment_name=demo trainer.max_epochs=4
+
+The packed Text2Shape sets of the reference's data/preprocess_all_data.py are read by tricolo_amd.data.dataset.PackedDataset
+(renderings resized on the GPU, u8 store resident on the device):
+
+    python -m tricolo_amd.train data=text2shape_chair_table data.dataset_root_path=/path/to/data model.text_encoder=BiGRUEncoder \
+        model.image_encoder=MVCNNEncoder model.voxel_encoder=SparseCNNEncoder experiment_name=chair_table
 """
 from __future__ import annotations
 
@@ -100,15 +106,29 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
     return {"epoch": int(cfg.trainer.max_epochs) - 1, "global_step": step, "best": best, "history": history}
 
 
+PACKED_DATASETS = ("Text2ShapeChairTable", "Text2ShapeC13")
+
+
 def main(argv=None):
     from .data import synthetic as syn
     from .model.tricolo_net import TriCoLoNet
     cfg = tcfg.compose(overrides=list(argv if argv is not None else sys.argv[1:]))
-    if cfg.data.get("dataset") != "Synthetic":
-        raise SystemExit("tricolo_amd.train only ships the synthetic data source (no dataset can be downloaded here); with real "
-                         "data use the reference's train.py + DataModule and the `_target_` overrides of INTEGRATION.md")
+    if cfg.data.get("dataset") not in ("Synthetic",) + PACKED_DATASETS:
+        raise SystemExit(f"tricolo_amd.train reads data=synthetic and the packed Text2Shape sets {PACKED_DATASETS} "
+                         f"(data/dataset.py: <exp_data_root_path>/<category>/<model_id>.npz + <split>_map.json), not {cfg.data.get('dataset')!r}")
     torch.manual_seed(cfg.train_seed)
     net = TriCoLoNet(cfg)
+    out = os.path.join(cfg.experiment_output_path, "training") if cfg.get("experiment_name") else None
+    ckpt = os.path.join(out, cfg.ckpt_name) if (out and cfg.get("ckpt_name")) else None
+    if cfg.data.dataset in PACKED_DATASETS:
+        from .data.dataset import PackedDataset
+        # data_module.py:14-31: train split shuffled with drop_last, cfg.inference.split in file order.  The store lives where the step
+        # runs; without a GPU it is still built (on the host) so that a data problem shows before anything else - fit() itself needs the GPU.
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+        bs = int(cfg.data.batch_size)
+        train_set, val_set = PackedDataset(cfg, "train", device=dev), PackedDataset(cfg, cfg.inference.split, device=dev)
+        return fit(net, cfg, train_set.batches(bs, shuffle_seed=cfg.train_seed, drop_last=True), val_set.batches(bs), ckpt_path=ckpt,
+                   out_dir=out)
     V = cfg.data.voxel_size if cfg.model.voxel_encoder else None
     nv = cfg.data.num_views if cfg.model.image_encoder else None
     B = min(int(cfg.data.get("batch_size", 32)), 64)
@@ -122,8 +142,6 @@ def main(argv=None):
             for i in range(0, len(order) - B + 1, B):
                 yield syn.batch_to_device(syn.collate_items([items[j] for j in order[i:i + B]], voxel=V is not None, views=nv is not None), "cuda")
         return gen
-    out = os.path.join(cfg.experiment_output_path, "training") if cfg.get("experiment_name") else None
-    ckpt = os.path.join(out, cfg.ckpt_name) if (out and cfg.get("ckpt_name")) else None
     return fit(net, cfg, batches(train, cfg.train_seed), batches(held), ckpt_path=ckpt, out_dir=out)
 
 
