@@ -467,6 +467,23 @@ int tri_mesh_sample_points(const float* verts, const int* faces, const long* ver
                            const double* cdf, const double* total, int N, int S, unsigned long long seed, float* points, long* face_idx,
                            void* stream);
 
+/* ---- Multi-view rendering (data/preprocess_all_data.py:44-82: the pyrender scene, restated as a rasteriser) -------------------- */
+/* The packed batch of the mesh sampler plus: face_mat int32 [sumF], the material of every face, local to its mesh; mat_kd fp32
+ * [sumM][3] diffuse colours with mat_off int64 [N + 1]; cam fp32 [N][views][12] = eye[3], then the 3 x 3 world-to-camera rotation row
+ * by row (the camera looks down -z, +y up).  image u8 [N][views][3][H][W]; visibility (optional) int32 [N][views][H][W]: the face
+ * seen at the pixel centre, local to its mesh, -1 for background.  A perspective projection with vertical field of view yfov on an
+ * H x W viewport; a face with a vertex nearer than znear is dropped whole (NO near-plane clipping), vertices snap to 1/256 pixel,
+ * coverage by int64 edge functions at the pixel centres with the top-left rule, both sides visible, depth 1 / z interpolated in
+ * fp32, the nearest face per pixel by a 64-bit atomic max (at bit-equal depth the lower face index): independent of the order in
+ * which faces arrive, bit-reproducible.  Flat Lambert shading, Kd (0.1 + 3 / pi max(n . (0, 1, 0), 0)), white background.  The
+ * arithmetic is spelled out at the head of csrc/raster.hip.  workspace: tri_raster_workspace(...) bytes of device memory, 16-byte
+ * aligned (0 for sizes tri_raster_render refuses).  Limits of one call: fewer than 2^31 faces, fewer than 2^31 pixels over all meshes
+ * and views, at most 65535 views: TRI_ERR_UNSUPPORTED before anything is launched.  Indices outside a mesh are clamped to it. */
+size_t tri_raster_workspace(long sumF, int N, int views, int H, int W);
+int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                      const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
+                      double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
+
 /* ---- Bicubic antialiased resize of u8 renderings (general_dataset.py:63-65: Resize(image_size, BICUBIC, antialias=True)) ------- */
 /* in [planes][Hin][Win] u8 -> out [planes][Hout][Wout] u8, both contiguous: cast to fp32, the separable bicubic (a = -0.5) antialias
  * filter of ATen's _upsample_bicubic2d_aa (width pass first; per axis scale = n_in / n_out, support = 2 max(scale, 1), windows clipped

@@ -1,0 +1,289 @@
+// Multi-view rendering of a packed batch of triangle meshes (the renderer behind data/preprocess_all_data.py:44-82 of the reference,
+// restated as a rasteriser: visibility by a 64-bit atomic max, flat Lambert shading).  The packed batch is the one of mesh_sample.hip
+// (verts [sumV][3], faces int32 [sumF][3] local to the mesh, vert_off / face_off int64 [N + 1]) plus a material index per face, a
+// table of diffuse colours per mesh and, per (mesh, view), the camera: eye[3] and the 3 x 3 world-to-camera rotation R (row major).
+// The kernel is DEFINED by its arithmetic; tricolo_amd/data/render.py restates it in torch and gives the same bits.
+//
+//   setup (per view and face, fp32, every operation rounded on its own - contraction is off in this file; a / b is the correctly
+//   rounded quotient, formed as fl32(fl64(a) / fl64(b)): 53 >= 2 * 24 + 2 bits make the second rounding harmless):
+//     q = v - eye;  p.k = (R[k][0] q.x + R[k][1] q.y) + R[k][2] q.z;  nz = -p.z (the camera looks down -z, +y is up)
+//     a face with a vertex at nz < znear (or NaN) is dropped whole - there is NO near-plane clipping
+//     xs = ((fx p.x) / nz + 1) (W / 2),  ys = (1 - (fy p.y) / nz) (H / 2)   with fy = fl32(1 / tan(yfov / 2)), fx = fl32(fy H / W), both
+//                                                                           formed in float64 on the host; row 0 is the top
+//     X = (int)rintf(256 xs), Y likewise (1/256 pixel, ties to even); |X| or |Y| > 2^20 drops the face
+//   coverage: 2A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) in int64; 2A == 0 drops the face, 2A < 0 swaps vertices 1 and 2 (both sides
+//     are visible).  Edge a -> b at the pixel centre P = (256 px + 128, 256 py + 128): E = (b.x - a.x)(P.y - a.y) - (b.y - a.y)(P.x - a.x),
+//     E0 on 1 -> 2, E1 on 2 -> 0, E2 on 0 -> 1.  P is covered when every E > 0, or E == 0 on an edge that is top (dy == 0, dx > 0) or
+//     left (dy < 0): two faces sharing an edge cover every pixel centre on it exactly once.
+//   depth: d_i = 1 / nz_i;  l_i = fl32(E_i) / fl32(2A);  d = (l0 d0 + l1 d1) + l2 d2   (1 / z is linear on the screen; larger = nearer)
+//   visibility: key = bits(d) << 32 | (0xFFFFFFFF - face), face local to the mesh; atomic max per pixel over a cleared u64 buffer.
+//     d > 0, so the bits order like the values: the nearest face wins, at bit-equal depth the lower index - whatever the arrival order.
+//   shading (per pixel, world space): c = (b - a) x (c - a) componentwise as mesh_sample.hip's areas, len = sqrt((cx^2 + cy^2) + cz^2)
+//     correctly rounded, e = eye - a, the normal is turned toward the eye by the sign of (cx ex + cy ey) + cz ez; with the light
+//     l = (0, 1, 0): ndl = max(+-cy / len, 0) (0 when len == 0), s = 0.1 + fl32(3 / pi) ndl, colour = clamp(Kd s, 0, 1),
+//     u8 = floor(255 colour + 0.5); background 255.
+//
+// Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
+// larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
+// queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
+#include <math.h>
+
+#include "common.h"
+#include "../../include/tricolo_hip.h"
+
+#pragma clang fp contract(off)
+
+#define RS_THREADS 256
+#define RS_SMALL 8                              // boxes up to 8 x 8 pixel centres stay with their lane
+#define RS_QUEUE_BLOCKS 4096                    // fixed grid of the queue kernel
+#define RS_CLEAR_BLOCKS 2048
+#define RS_SNAP_MAX 1048576.f                   // 2^20 in 1/256 pixel
+#define RS_MAX_PIXELS (1L << 31)
+#define RS_KDIFF 0.95492965f                    // fl32(3 / pi): intensity 3, Lambert's 1 / pi
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ float rs_div(float a, float b) { return (float)((double)a / (double)b); }
+__device__ __forceinline__ float rs_sqrt(float x) { return (float)sqrt((double)x); }
+
+struct RsFace {
+    long A2, e[3];                              // doubled area (> 0); the edge functions at the centre of pixel (x0, y0)
+    int sx[3], sy[3], bias[3];                  // their steps per pixel in x and y; 0 on a top / left edge, -1 otherwise
+    float d[3];
+    int x0, x1, y0, y1;                         // the box of pixel centres, clipped to the image
+};
+
+// the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
+__device__ __forceinline__ int rs_mesh_of(const long* __restrict__ face_off, int N, long gf) {
+    int lo = 0, hi = N;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (face_off[mid] <= gf) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool rs_setup(const float* __restrict__ verts, const int* __restrict__ faces, const long* __restrict__ vert_off,
+                                         const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx, float fy,
+                                         float znear, RsFace& o) {
+    const long v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    if (V <= 0) return false;
+    const float* c = cam + (size_t)nv * 12;
+    const int* fi = faces + (size_t)gf * 3;
+    const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+    int X[3], Y[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const long j = min((long)(unsigned)fi[k], V - 1);              // a bad index reads the mesh's own last vertex, never beyond it
+        const float* p = verts + (size_t)(v0 + j) * 3;
+        const float qx = p[0] - c[0], qy = p[1] - c[1], qz = p[2] - c[2];
+        const float px = (c[3] * qx + c[4] * qy) + c[5] * qz;
+        const float py = (c[6] * qx + c[7] * qy) + c[8] * qz;
+        const float nz = -((c[9] * qx + c[10] * qy) + c[11] * qz);
+        const bool front = nz >= znear;                                 // false for NaN
+        const float z = front ? nz : 1.f;
+        const float xf = rintf(((rs_div(fx * px, z) + 1.0f) * hw) * 256.f);
+        const float yf = rintf(((1.0f - rs_div(fy * py, z)) * hh) * 256.f);
+        const bool in = fabsf(xf) <= RS_SNAP_MAX && fabsf(yf) <= RS_SNAP_MAX;
+        ok = ok && front && in;
+        X[k] = in ? (int)xf : 0;
+        Y[k] = in ? (int)yf : 0;
+        o.d[k] = rs_div(1.0f, z);
+    }
+    if (!ok) return false;
+    long A2 = (long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long)(X[2] - X[0]) * (Y[1] - Y[0]);
+    if (A2 == 0) return false;
+    if (A2 < 0) {
+        int t = X[1]; X[1] = X[2]; X[2] = t;
+        t = Y[1]; Y[1] = Y[2]; Y[2] = t;
+        const float s = o.d[1]; o.d[1] = o.d[2]; o.d[2] = s;
+        A2 = -A2;
+    }
+    o.A2 = A2;
+    o.x0 = max(0, (min(X[0], min(X[1], X[2])) + 127) >> 8);             // ceil((X - 128) / 256)
+    o.x1 = min(W - 1, (max(X[0], max(X[1], X[2])) - 128) >> 8);         // floor((X - 128) / 256)
+    o.y0 = max(0, (min(Y[0], min(Y[1], Y[2])) + 127) >> 8);
+    o.y1 = min(H - 1, (max(Y[0], max(Y[1], Y[2])) - 128) >> 8);
+    if (o.x0 > o.x1 || o.y0 > o.y1) return false;
+    const long Px = 256L * o.x0 + 128, Py = 256L * o.y0 + 128;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {                                       // edge k runs from vertex k + 1 to vertex k + 2
+        const int a = (k + 1) % 3, b = (k + 2) % 3;
+        const int dx = X[b] - X[a], dy = Y[b] - Y[a];
+        o.e[k] = (long)dx * (Py - Y[a]) - (long)dy * (Px - X[a]);
+        o.sx[k] = -256 * dy;                                            // |dx|, |dy| <= 2^21: the steps fit 32 bits
+        o.sy[k] = 256 * dx;
+        o.bias[k] = (dy < 0 || (dy == 0 && dx > 0)) ? 0 : -1;
+    }
+    return true;
+}
+
+__device__ __forceinline__ void rs_pixel(const RsFace& f, long e0, long e1, long e2, u64* __restrict__ kp, unsigned low) {
+    if (((e0 + f.bias[0]) | (e1 + f.bias[1]) | (e2 + f.bias[2])) < 0) return;
+    const float fa = (float)(double)f.A2;
+    const float l0 = rs_div((float)(double)e0, fa), l1 = rs_div((float)(double)e1, fa), l2 = rs_div((float)(double)e2, fa);
+    const float d = (l0 * f.d[0] + l1 * f.d[1]) + l2 * f.d[2];
+    const u64 key = ((u64)__float_as_uint(d) << 32) | low;
+    if (*kp < key) atomicMax(kp, key);                                  // keys only grow: a stale read costs an atomic, never a pixel
+}
+
+__global__ __launch_bounds__(RS_THREADS) void raster_clear_kernel(u64* __restrict__ keys, long npix, u64* __restrict__ qcount) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *qcount = 0;
+    for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < npix; i += (long)gridDim.x * RS_THREADS) keys[i] = 0;
+}
+
+// blockIdx.y = view, one lane per face of the whole batch
+__global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                  const long* __restrict__ vert_off, const long* __restrict__ face_off,
+                                                                  const float* __restrict__ cam, int N, long sumF, int views, int H, int W,
+                                                                  float fx, float fy, float znear, u64* __restrict__ keys,
+                                                                  u64* __restrict__ qcount, uint2* __restrict__ queue, u64 qcap) {
+    const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    const int view = blockIdx.y, lane = threadIdx.x & 63;
+    RsFace f;
+    bool live = false, big = false;
+    int n = 0;
+    long nv = 0;
+    if (gf < sumF) {
+        n = rs_mesh_of(face_off, N, gf);
+        nv = (long)n * views + view;
+        live = rs_setup(verts, faces, vert_off, cam, gf, n, nv, H, W, fx, fy, znear, f);
+        big = live && (f.x1 - f.x0 >= RS_SMALL || f.y1 - f.y0 >= RS_SMALL);
+    }
+    // queue append: every lane of the wave is here; one atomic add per wave, the slots in lane order
+    const u64 mask = __ballot(big);
+    if (mask) {
+        const int leader = __ffsll((long long)mask) - 1;
+        u64 base = 0;
+        if (lane == leader) base = atomicAdd(qcount, (u64)__popcll(mask));
+        base = __shfl(base, leader);
+        if (big) {
+            const u64 slot = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
+            if (slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
+        }
+    }
+    if (!live || big) return;
+    const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - face_off[n]);
+    u64* row = keys + ((size_t)nv * H + f.y0) * W;
+    long r0 = f.e[0], r1 = f.e[1], r2 = f.e[2];
+    for (int y = f.y0; y <= f.y1; ++y, row += W, r0 += f.sy[0], r1 += f.sy[1], r2 += f.sy[2]) {
+        long e0 = r0, e1 = r1, e2 = r2;
+        for (int x = f.x0; x <= f.x1; ++x, e0 += f.sx[0], e1 += f.sx[1], e2 += f.sx[2]) rs_pixel(f, e0, e1, e2, row + x, low);
+    }
+}
+
+// fixed grid; workgroup b takes queue entries b, b + gridDim.x, ... up to the count the first kernel left on the device
+__global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                  const long* __restrict__ vert_off, const long* __restrict__ face_off,
+                                                                  const float* __restrict__ cam, int N, int views, int H, int W, float fx,
+                                                                  float fy, float znear, u64* __restrict__ keys,
+                                                                  const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
+    const u64 count = min(*qcount, qcap);
+    for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
+        const uint2 item = queue[q];
+        const long gf = item.x;
+        const int n = rs_mesh_of(face_off, N, gf);
+        const long nv = (long)n * views + (int)item.y;
+        RsFace f;
+        if (!rs_setup(verts, faces, vert_off, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;    // the same answer in every lane
+        const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - face_off[n]);
+        const int bw = f.x1 - f.x0 + 1, cnt = bw * (f.y1 - f.y0 + 1);
+        u64* box = keys + ((size_t)nv * H + f.y0) * W + f.x0;
+        for (int i = threadIdx.x; i < cnt; i += RS_THREADS) {
+            const int iy = i / bw, ix = i - iy * bw;
+            rs_pixel(f, f.e[0] + (long)ix * f.sx[0] + (long)iy * f.sy[0], f.e[1] + (long)ix * f.sx[1] + (long)iy * f.sy[1],
+                     f.e[2] + (long)ix * f.sx[2] + (long)iy * f.sy[2], box + (size_t)iy * W + ix, low);
+        }
+    }
+}
+
+// one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                    const long* __restrict__ vert_off, const long* __restrict__ face_off,
+                                                                    const int* __restrict__ face_mat, const float* __restrict__ mat_kd,
+                                                                    const long* __restrict__ mat_off, const float* __restrict__ cam,
+                                                                    int views, int HW, long npix, const u64* __restrict__ keys,
+                                                                    uint8_t* __restrict__ image, int* __restrict__ visibility) {
+    const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (i >= npix) return;
+    const long nv = i / HW;
+    const int pix = (int)(i - nv * HW), n = (int)(nv / views);
+    const u64 key = keys[i];
+    uint8_t* out = image + (size_t)nv * 3 * HW + pix;
+    const long f0 = face_off[n], F = face_off[n + 1] - f0, v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    const long lf = (long)(0xFFFFFFFFu - (unsigned)key);
+    if (key == 0 || lf >= F || V <= 0) {
+        out[0] = 255; out[HW] = 255; out[2 * (size_t)HW] = 255;
+        if (visibility) visibility[i] = -1;
+        return;
+    }
+    if (visibility) visibility[i] = (int)lf;
+    const int* fi = faces + (size_t)(f0 + lf) * 3;
+    const float* a = verts + (size_t)(v0 + min((long)(unsigned)fi[0], V - 1)) * 3;
+    const float* b = verts + (size_t)(v0 + min((long)(unsigned)fi[1], V - 1)) * 3;
+    const float* c = verts + (size_t)(v0 + min((long)(unsigned)fi[2], V - 1)) * 3;
+    const float* eye = cam + (size_t)nv * 12;
+    const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+    const float wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2];
+    const float cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
+    const float len = rs_sqrt((cx * cx + cy * cy) + cz * cz);
+    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
+    const float side = (cx * ex + cy * ey) + cz * ez;
+    float ndl = 0.f;
+    if (len > 0.f) {
+        const float ny = rs_div(cy, len);
+        ndl = fmaxf(side < 0.f ? -ny : ny, 0.f);
+    }
+    const float shade = 0.1f + RS_KDIFF * ndl;
+    const long m0 = mat_off[n], M = mat_off[n + 1] - m0;
+    const long m = min((long)(unsigned)face_mat[f0 + lf], M - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float kd = M > 0 ? mat_kd[(size_t)(m0 + m) * 3 + k] : 0.4f;
+        const float col = fminf(fmaxf(kd * shade, 0.f), 1.f);
+        out[(size_t)k * HW] = (uint8_t)(int)floorf(255.f * col + 0.5f);
+    }
+}
+
+static bool rs_sizes_ok(long sumF, int N, int views, int H, int W) {
+    return N >= 0 && sumF >= 0 && views >= 0 && H >= 0 && W >= 0;
+}
+
+extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W) {
+    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W >= (double)RS_MAX_PIXELS) return 0;
+    const size_t npix = (size_t)N * views * H * W;
+    return npix * 8 + 16 + (size_t)sumF * views * 8;                    // keys | queue count (padded to 16 bytes) | queue
+}
+
+extern "C" int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                 const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
+                                 double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    if (!rs_sizes_ok(sumF, N, views, H, W)) { tri_set_error("tri_raster_render: negative size"); return TRI_ERR_ARG; }
+    if (!(yfov > 0.0 && yfov < M_PI) || !(znear > 0.0)) { tri_set_error("tri_raster_render: yfov must lie in (0, pi) and znear above 0"); return TRI_ERR_ARG; }
+    if (sumF >= (1L << 31)) { tri_set_error("tri_raster_render: 2^31 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
+    if (views > 65535) { tri_set_error("tri_raster_render: more than 65535 views"); return TRI_ERR_UNSUPPORTED; }
+    if ((double)N * views * H * W >= (double)RS_MAX_PIXELS) {
+        tri_set_error("tri_raster_render: 2^31 or more pixels (a visibility buffer of 16 GiB or more) in one launch");
+        return TRI_ERR_UNSUPPORTED;
+    }
+    const long npix = (long)N * views * H * W;
+    if (npix == 0) return TRI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    u64* keys = (u64*)workspace;
+    u64* qcount = keys + npix;
+    uint2* queue = (uint2*)(qcount + 2);
+    const u64 qcap = (u64)sumF * views;
+    const double fyd = 1.0 / tan(yfov / 2.0);
+    const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
+    raster_clear_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(keys, npix, qcount);
+    if (sumF > 0) {
+        raster_faces_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
+            verts, faces, vert_off, face_off, cam, N, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+        raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(verts, faces, vert_off, face_off, cam, N, views, H, W, fx, fy, zn, keys,
+                                                                    qcount, queue, qcap);
+    }
+    raster_resolve_kernel<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(
+        verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, views, H * W, npix, keys, image, visibility);
+    return tri_check_launch("tri_raster_render");
+}

@@ -1,0 +1,136 @@
+"""Preprocessing of the Text2Shape data on the GPU: what the reference's data/preprocess_all_data.py:109-155 does for the three
+splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
+
+    python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda]
+
+It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
+cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
+shapenet.json; for Text2ShapeC13 the existing map file is read instead - and `<exp_data_root_path>/<category>/<model_id>.npz`
+with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V], from the nrrd_256_filter_div_{V}_solid grids, data/nrrd.py) and images
+(uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
+`<dirname(dataset_path)>/ShapeNetCore.v2/<category>/<model_id>/models/model_normalized.obj` by ops.render_views (csrc/raster.hip), a
+batch of meshes per call.  data/render.py says what that renderer restates of the reference's pyrender scene, what it deliberately
+does differently (Lambert shading, flat normals, no culling, no textures) and that no pixel has been compared with pyrender's.
+
+Every .npz is written under a temporary name and renamed; a file that exists is skipped, so an interrupted run resumes.
+--jpeg-roundtrip passes every view through an in-memory JPEG at PIL's default quality, as the reference's img.save("<i>.jpg")
+followed by Image.open does.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+from .. import config as tcfg
+from . import render
+from .materials import load_obj_materials
+from .nrrd import read_nrrd
+
+VOXEL_SIZES = (32, 64, 128)
+SPLITS = ("train", "val", "test")
+
+
+def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
+    """preprocess_all_data.py:16-41: -> ((category, model_id), ...) in order of first occurrence; writes the list of
+    {model_id, category, caption, tokens} to output_json_path.  Words are joined up to the first pad id 0, newlines removed."""
+    with open(caption_file_path, "rb") as f:
+        caption_tuples = pickle.load(f)["caption_tuples"]
+    with open(id_word_file_path, "r") as f:
+        idx_to_word = json.load(f)["idx_to_word"]
+    ignored = set(ignored_models or ())
+    samples, seen = [], {}
+    for inds, category, nrrd_name in caption_tuples:
+        inds = np.asarray(inds)
+        text = []
+        for ind in inds.tolist():
+            if ind == 0:
+                break
+            text.append(idx_to_word[str(ind)])
+        model_id = nrrd_name.split(".")[0]
+        if f"{category}/{model_id}" in ignored:
+            continue
+        samples.append({"model_id": model_id, "category": category, "caption": " ".join(text).replace("\n", ""), "tokens": inds.tolist()})
+        seen.setdefault((category, model_id), True)
+    os.makedirs(os.path.dirname(os.path.abspath(output_json_path)), exist_ok=True)
+    with open(output_json_path, "w") as f:
+        json.dump(samples, f, indent=2)
+    return tuple(seen)
+
+
+def read_model_ids(map_json_path):
+    """preprocess_all_data.py:130-137: the (category, model_id) pairs of an existing map file, in order of first occurrence."""
+    with open(map_json_path, "r") as f:
+        return tuple(dict.fromkeys((it["category"], it["model_id"]) for it in json.load(f)))
+
+
+def jpeg_roundtrip(images):
+    """uint8 [n, 3, H, W] -> the same views after PIL's JPEG encoder (default quality) and decoder."""
+    from PIL import Image
+    out = np.empty_like(images)
+    for i, view in enumerate(images):
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(view.transpose(1, 2, 0))).save(buf, format="JPEG")
+        buf.seek(0)
+        out[i] = np.asarray(Image.open(buf).convert("RGB")).transpose(2, 0, 1)
+    return out
+
+
+def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print):
+    """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped)."""
+    todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
+    for i in range(0, len(todo), batch_meshes):
+        batch = todo[i:i + batch_meshes]
+        meshes = [load_obj_materials(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
+        images = render.render_meshes([m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes], [m[3] for m in meshes],
+                                      num_views=num_views, image_size=render.IMAGE_SIZE, device=device).cpu().numpy()
+        for (cat, mid), views in zip(batch, images):
+            grids = {f"voxel{v}": read_nrrd(os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd"), v) for v in VOXEL_SIZES}
+            os.makedirs(os.path.join(out_root, cat), exist_ok=True)
+            path = os.path.join(out_root, cat, f"{mid}.npz")
+            tmp = f"{path}.{os.getpid()}.tmp"
+            with open(tmp, "wb") as f:
+                np.savez_compressed(f, images=jpeg_roundtrip(views) if roundtrip else views, **grids)
+            os.replace(tmp, path)
+        log(f"  packed {min(i + batch_meshes, len(todo))} / {len(todo)}")
+    return len(todo), len(keys) - len(todo)
+
+
+def main(argv=None, log=print):
+    """-> {split: {"models", "written", "skipped"}}."""
+    ap = argparse.ArgumentParser(prog="python -m tricolo_amd.data.preprocess", description=__doc__.split("\n\n")[0])
+    ap.add_argument("overrides", nargs="*", help="config overrides, e.g. data=text2shape_chair_table data.dataset_root_path=...")
+    ap.add_argument("--batch-meshes", type=int, default=8, help="meshes rendered per call")
+    ap.add_argument("--jpeg-roundtrip", action="store_true", help="pass every view through an in-memory JPEG, as the reference's .jpg files do")
+    ap.add_argument("--device", default="cuda", help="cuda (csrc/raster.hip) or cpu (the untuned torch restatement)")
+    args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.batch_meshes < 1:
+        ap.error("--batch-meshes must be positive")
+    cfg = tcfg.compose(overrides=args.overrides)
+    data = cfg.data
+    obj_root = os.path.join(os.path.dirname(data.dataset_path), "ShapeNetCore.v2")
+    stats = {}
+    for split in SPLITS:
+        log(f"==> {split} split")
+        map_path = getattr(data, f"{split}_lang_data_path")
+        if data.dataset == "Text2ShapeChairTable":
+            keys = create_model_id_caption_mapping(os.path.join(data.dataset_path, f"processed_captions_{split}.p"),
+                                                   os.path.join(data.dataset_path, "shapenet.json"), map_path, data.ignored_models)
+        else:
+            keys = read_model_ids(map_path)
+        written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
+                                       args.batch_meshes, args.jpeg_roundtrip, log)
+        stats[split] = {"models": len(keys), "written": written, "skipped": skipped}
+        log(f"  {len(keys)} models: {written} written, {skipped} already there")
+    return stats
+
+
+if __name__ == "__main__":
+    main()

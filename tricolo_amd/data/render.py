@@ -1,0 +1,241 @@
+"""Multi-view renderings of ShapeNet meshes without a GL stack: the scene of the reference's data/preprocess_all_data.py:52-80,
+restated for the rasteriser of csrc/raster.hip (ops.render_views).
+
+What is restated: a perspective camera with yfov pi/3 on a square 224 x 224 viewport, pyrender's default znear 0.05, a white
+background, ambient light 0.1, one white directional light of intensity 3 turned by rotation_matrix(pi/2, [-1, 0, 0]) - it shines
+straight down, so the direction toward it is (0, 1, 0) - and, for view i of num_views, the camera pose R = R_y(angle) R_x(-pi/5),
+eye = c + R (0, 0, 0.85) with angle = 2 pi i / num_views and c the centre of the mesh's bounding box.  That reading of trimesh's
+Scene.centroid and scene.cameras.look_at (one point, a given distance) comes from their documented behaviour.  trimesh and pyrender
+are not installed where this was written: NOBODY HAS COMPARED A PIXEL OF THIS RENDERER WITH PYRENDER'S OUTPUT.
+
+Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliberate differences:
+  * Lambert diffuse plus ambient, Kd (0.1 + 3/pi max(n . l, 0)), instead of pyrender's metallic-roughness BRDF;
+  * flat face normals (no vertex normals, no smoothing), turned toward the eye;
+  * no back-face culling: both sides of a face are drawn (ShapeNet's winding is unreliable);
+  * map_Kd textures are ignored: a textured material renders with its Kd;
+  * no near-plane clipping: a face with a vertex nearer than znear is dropped whole.  model_normalized.obj lies within 0.5 of its
+    centre and the camera stands 0.85 away, so no face of such a mesh comes near the plane; no anti-aliasing either.
+
+On GPU tensors ops.render_views launches the HIP kernels; on CPU tensors the same call runs render_views_cpu below, a torch
+restatement of the kernel's arithmetic (spelled out at the head of csrc/raster.hip) that gives the same bits.  It exists for
+checking and for machines without a GPU and is not tuned.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+YFOV, ZNEAR, IMAGE_SIZE = math.pi / 3, 0.05, 224
+DISTANCE, ELEVATION = 0.85, math.pi / 5
+SNAP_MAX = float(2 ** 20)
+KDIFF = float(np.float32(3.0 / math.pi))
+CANDIDATES_PER_PASS = 1 << 21                       # (face, pixel) pairs the fallback expands at a time
+
+
+# ------------------------------------------------------------------------------------------------ cameras
+def camera_poses(center, num_views, distance=DISTANCE, elevation=ELEVATION):
+    """-> (eye float64 [num_views, 3], R float64 [num_views, 3, 3]): R is the world-to-camera rotation (its rows are the camera's
+    x, y, z axes in the world; the camera looks down its -z), the transpose of the pose rotation R_y(angle) R_x(-elevation) of
+    preprocess_all_data.py:71-78, angle = 2 pi i / num_views; eye = center + distance * (third row of R)."""
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    ce, se = math.cos(-elevation), math.sin(-elevation)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, ce, -se], [0.0, se, ce]])
+    eyes, rots = [], []
+    for i in range(int(num_views)):
+        a = 2.0 * math.pi * i / num_views
+        ry = np.array([[math.cos(a), 0.0, math.sin(a)], [0.0, 1.0, 0.0], [-math.sin(a), 0.0, math.cos(a)]])
+        pose = ry @ rx                                                              # camera-to-world
+        eyes.append(c + pose @ np.array([0.0, 0.0, distance]))
+        rots.append(pose.T)
+    return np.stack(eyes) if eyes else np.zeros((0, 3)), np.stack(rots) if rots else np.zeros((0, 3, 3))
+
+
+def bbox_center(verts):
+    """The centre of the bounding box of all vertices, float64 (zeros for a mesh without vertices)."""
+    v = verts.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(verts) else np.asarray(verts, dtype=np.float64)
+    return 0.5 * (v.min(0) + v.max(0)) if v.shape[0] else np.zeros(3)
+
+
+def pack_cameras(centers, num_views, device=None):
+    """float32 [N, num_views, 12] for ops.render_views: eye, then the world-to-camera rotation row by row."""
+    rows = []
+    for c in centers:
+        eye, rot = camera_poses(c, num_views)
+        rows.append(np.concatenate([eye, rot.reshape(-1, 9)], axis=1))
+    cam = np.stack(rows).astype(np.float32) if rows else np.zeros((0, int(num_views), 12), np.float32)
+    return torch.from_numpy(np.ascontiguousarray(cam)).to(device or "cpu")
+
+
+def projection_scales(H, W, yfov):
+    """(fx, fy) as the kernel's host code forms them: float64, then rounded to fp32."""
+    fy = 1.0 / math.tan(float(yfov) / 2.0)
+    return float(np.float32(fy * float(H) / float(W))), float(np.float32(fy))
+
+
+# ------------------------------------------------------------------------------------------------ the torch fallback
+def _f32(x):
+    return torch.tensor(x, dtype=torch.float32)
+
+
+def snap_vertices(verts, cam, H, W, yfov, znear):
+    """Per vertex of one mesh in one view: (ok bool [V], X int64 [V], Y int64 [V], d fp32 [V]) - in front of znear and inside the
+    snap range, the screen position in 1/256 pixel, 1 / depth."""
+    fx, fy = (_f32(s) for s in projection_scales(H, W, yfov))
+    eye, R = cam[:3], cam[3:]
+    q = verts - eye
+    px = (R[0] * q[:, 0] + R[1] * q[:, 1]) + R[2] * q[:, 2]
+    py = (R[3] * q[:, 0] + R[4] * q[:, 1]) + R[5] * q[:, 2]
+    nz = -((R[6] * q[:, 0] + R[7] * q[:, 1]) + R[8] * q[:, 2])
+    front = nz >= _f32(float(np.float32(znear)))
+    z = torch.where(front, nz, torch.ones_like(nz))
+    xf = torch.round((((fx * px) / z + 1.0) * (0.5 * W)) * 256.0)
+    yf = torch.round(((1.0 - (fy * py) / z) * (0.5 * H)) * 256.0)
+    inside = (xf.abs() <= SNAP_MAX) & (yf.abs() <= SNAP_MAX)
+    X = torch.where(inside, xf, torch.zeros_like(xf)).to(torch.int64)
+    Y = torch.where(inside, yf, torch.zeros_like(yf)).to(torch.int64)
+    return front & inside, X, Y, 1.0 / z
+
+
+def project_faces(verts, faces, cam, H, W, yfov, znear):
+    """Setup of csrc/raster.hip for one mesh and one view.  verts fp32 [V, 3], faces int64 [F, 3] (already clamped to the mesh),
+    cam fp32 [12] -> (keep bool [F], X int64 [F, 3], Y int64 [F, 3], d fp32 [F, 3], A2 int64 [F]) with vertices 1 and 2 swapped
+    where the doubled area was negative; keep is False for dropped faces (behind znear, off the snap range, zero area)."""
+    okv, Xv, Yv, dv = snap_vertices(verts, cam, H, W, yfov, znear)
+    X, Y, d = Xv[faces], Yv[faces], dv[faces]
+    A2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (X[:, 2] - X[:, 0]) * (Y[:, 1] - Y[:, 0])
+    keep = okv[faces].all(dim=1) & (A2 != 0)
+    flip = A2 < 0
+    order = torch.where(flip[:, None], torch.tensor([0, 2, 1]), torch.tensor([0, 1, 2]))
+    return keep, X.gather(1, order), Y.gather(1, order), d.gather(1, order), A2.abs()
+
+
+def _visibility_one(verts, faces, cam, H, W, yfov, znear):
+    """keys int64 [H * W] of one mesh and one view: bits(d) << 32 | (0xFFFFFFFF - face), 0 for background."""
+    keys = torch.zeros((H * W,), dtype=torch.int64)
+    keep, X, Y, d, A2 = project_faces(verts, faces, cam, H, W, yfov, znear)
+    x0 = ((X.amin(1) + 127) >> 8).clamp(min=0)
+    x1 = ((X.amax(1) - 128) >> 8).clamp(max=W - 1)
+    y0 = ((Y.amin(1) + 127) >> 8).clamp(min=0)
+    y1 = ((Y.amax(1) - 128) >> 8).clamp(max=H - 1)
+    keep = keep & (x0 <= x1) & (y0 <= y1)
+    fidx = torch.nonzero(keep).reshape(-1)
+    if fidx.numel() == 0:
+        return keys
+    bw, bh = (x1 - x0 + 1)[fidx], (y1 - y0 + 1)[fidx]
+    cnt = bw * bh
+    ends = torch.cumsum(cnt, 0)
+    start = 0
+    while start < fidx.numel():                                                     # passes of about CANDIDATES_PER_PASS pairs
+        base = int(ends[start - 1]) if start else 0
+        stop = int(torch.searchsorted(ends, torch.tensor(base + CANDIDATES_PER_PASS), right=True))
+        stop = max(stop, start + 1)
+        sel = fidx[start:stop]
+        c, w = cnt[start:stop], bw[start:stop]
+        rep = torch.repeat_interleave(torch.arange(sel.numel()), c)
+        local = torch.arange(int(c.sum())) - torch.repeat_interleave(torch.cumsum(c, 0) - c, c)
+        iy = torch.div(local, w[rep], rounding_mode="floor")
+        ix = local - iy * w[rep]
+        f = sel[rep]
+        px, py = x0[f] + ix, y0[f] + iy
+        Px, Py = 256 * px + 128, 256 * py + 128
+        inside = torch.ones_like(f, dtype=torch.bool)
+        E = []
+        for k in range(3):
+            a, b = (k + 1) % 3, (k + 2) % 3
+            dx, dy = X[f, b] - X[f, a], Y[f, b] - Y[f, a]
+            e = dx * (Py - Y[f, a]) - dy * (Px - X[f, a])
+            top_left = (dy < 0) | ((dy == 0) & (dx > 0))
+            inside &= (e > 0) | ((e == 0) & top_left)
+            E.append(e)
+        f, px, py = f[inside], px[inside], py[inside]
+        fa = A2[f].to(torch.float32)
+        lam = [e[inside].to(torch.float32) / fa for e in E]
+        depth = (lam[0] * d[f, 0] + lam[1] * d[f, 1]) + lam[2] * d[f, 2]
+        key = (depth.view(torch.int32).to(torch.int64) << 32) | (0xFFFFFFFF - f)
+        keys.scatter_reduce_(0, py * W + px, key, reduce="amax", include_self=True)
+        start = stop
+    return keys
+
+
+def _shade_one(verts, faces, face_mat, kd, cam, vis):
+    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background)."""
+    out = torch.full((3, vis.numel()), 255, dtype=torch.uint8)
+    pix = torch.nonzero(vis >= 0).reshape(-1)
+    if pix.numel() == 0:
+        return out
+    f = vis[pix]
+    a, b, c = verts[faces[f, 0]], verts[faces[f, 1]], verts[faces[f, 2]]
+    u, w = b - a, c - a
+    cx = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1]
+    cy = u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2]
+    cz = u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+    length = torch.sqrt((cx * cx + cy * cy) + cz * cz)
+    e = cam[:3] - a
+    side = (cx * e[:, 0] + cy * e[:, 1]) + cz * e[:, 2]
+    ok = length > 0
+    ny = cy / torch.where(ok, length, torch.ones_like(length))
+    ndl = torch.where(ok, torch.where(side < 0, -ny, ny).clamp(min=0.0), torch.zeros_like(ny))
+    shade = 0.1 + _f32(KDIFF) * ndl
+    M = kd.shape[0]
+    if M > 0:
+        m = face_mat[f].to(torch.int64)
+        col = kd[torch.where(m < 0, torch.full_like(m, M - 1), m.clamp(max=M - 1))]
+    else:
+        col = torch.full((f.numel(), 3), 0.4, dtype=torch.float32)
+    rgb = torch.floor(255.0 * (col * shade[:, None]).clamp(0.0, 1.0) + 0.5).to(torch.uint8)
+    out[:, pix] = rgb.t()
+    return out
+
+
+def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
+                     return_visibility=False):
+    """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch."""
+    voff, foff, moff = vert_off.tolist(), face_off.tolist(), mat_off.tolist()
+    N, views = len(voff) - 1, cam.shape[1]
+    image = torch.full((N, views, 3, H, W), 255, dtype=torch.uint8)
+    vis = torch.full((N, views, H, W), -1, dtype=torch.int32)
+    for n in range(N):
+        v = verts[voff[n]:voff[n + 1]]
+        f = faces[foff[n]:foff[n + 1]].to(torch.int64)
+        if v.shape[0] == 0 or f.shape[0] == 0 or H * W == 0:
+            continue
+        f = torch.where(f < 0, torch.full_like(f, v.shape[0] - 1), f.clamp(max=v.shape[0] - 1))     # the kernel's unsigned clamp
+        fm, kd = face_mat[foff[n]:foff[n + 1]], mat_kd[moff[n]:moff[n + 1]]
+        for k in range(views):
+            keys = _visibility_one(v, f, cam[n, k], H, W, yfov, znear)
+            face = torch.where(keys != 0, 0xFFFFFFFF - (keys & 0xFFFFFFFF), torch.full_like(keys, -1))
+            vis[n, k] = face.to(torch.int32).view(H, W)
+            image[n, k] = _shade_one(v, f, fm, kd, cam[n, k], face).view(3, H, W)
+    return (image, vis) if return_visibility else image
+
+
+# ------------------------------------------------------------------------------------------------ the convenient call
+def pack_materials(face_mat_list, kd_list, device=None):
+    """-> (face_mat int32 [sumF], mat_kd fp32 [sumM, 3], mat_off int64 [N + 1]); validated on the host."""
+    moff = [0]
+    for n, (fm, kd) in enumerate(zip(face_mat_list, kd_list)):
+        if kd.dim() != 2 or kd.shape[1] != 3 or kd.shape[0] < 1 or kd.dtype != torch.float32:
+            raise ValueError(f"mesh {n}: Kd must be a float32 tensor of shape [M >= 1, 3]")
+        if fm.numel() and (int(fm.min()) < 0 or int(fm.max()) >= kd.shape[0]):
+            raise ValueError(f"mesh {n}: material indices span {int(fm.min())} .. {int(fm.max())} but the mesh has {kd.shape[0]} materials")
+        moff.append(moff[-1] + kd.shape[0])
+    device = device or "cpu"
+    return (torch.cat([fm.to(device=device, dtype=torch.int32).reshape(-1) for fm in face_mat_list]).contiguous(),
+            torch.cat([kd.to(device) for kd in kd_list]).contiguous(), torch.tensor(moff, dtype=torch.int64, device=device))
+
+
+def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False):
+    """The reference's num_views renderings of every mesh -> uint8 [N, num_views, 3, S, S] on `device` (where verts_list[0] lives
+    when None): packs the batch (evaluation.mesh.pack_meshes), places the cameras around every mesh's bounding-box centre and calls
+    ops.render_views."""
+    from .. import ops
+    from ..evaluation.mesh import pack_meshes
+    verts, faces, voff, foff, _ = pack_meshes(verts_list, faces_list, device)
+    if len(face_mat_list) != len(faces_list) or any(fm.shape[0] != f.shape[0] for fm, f in zip(face_mat_list, faces_list)):
+        raise ValueError("every mesh needs one material index per face")
+    fm, kd, moff = pack_materials(face_mat_list, kd_list, verts.device)
+    cam = pack_cameras([bbox_center(v) for v in verts_list], num_views, verts.device)
+    H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
+    return ops.render_views(verts, faces, voff, foff, fm, kd, moff, cam, H, W, YFOV, ZNEAR, return_visibility)

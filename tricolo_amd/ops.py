@@ -1636,6 +1636,55 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
     return (points, idx) if return_face_idx else points
 
 
+# ------------------------------------------------------------------------------------------------ multi-view rendering
+RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
+
+
+def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=math.pi / 3, znear=0.05,
+                 return_visibility=False):
+    """Render every mesh of a packed batch (evaluation.mesh.pack_meshes) from every camera -> images uint8 [N, views, 3, H, W], with
+    return_visibility also int32 [N, views, H, W]: the face seen at each pixel centre, local to its mesh, -1 for background.
+    face_mat int32 [sumF]: a material per face, local to the mesh; mat_kd fp32 [sumM, 3] diffuse colours with mat_off int64 [N + 1];
+    cam fp32 [N, views, 12]: eye, then the world-to-camera rotation row by row (data.render.pack_cameras).  The arithmetic is the
+    definition (head of csrc/raster.hip): a face with a vertex nearer than znear is dropped whole - there is NO near-plane clipping
+    (model_normalized.obj lies within 0.5 of its centre, the reference's camera stands 0.85 away) - both sides are drawn, flat
+    Lambert shading, white background.  One call takes fewer than 2^31 faces and fewer than 2^31 pixels over all meshes and views
+    (8 bytes of visibility key each); more raises before anything runs.  CPU tensors run data.render.render_views_cpu, the same
+    arithmetic in torch (untuned, for checking)."""
+    H, W = int(H), int(W)
+    tensors = (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam)
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("render_views: all tensors must live on one device")
+    N = vert_off.numel() - 1
+    _mesh_arg(verts, "verts", torch.float32, 3)
+    _mesh_arg(faces, "faces", torch.int32, 3)
+    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
+    _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
+    _mesh_arg(mat_off, "mat_off", torch.int64, numel=N + 1)
+    _mesh_arg(face_mat, "face_mat", torch.int32, numel=faces.shape[0])
+    _mesh_arg(mat_kd, "mat_kd", torch.float32, 3)
+    if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
+        raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
+    views, sumF = cam.shape[1], faces.shape[0]
+    if H < 0 or W < 0 or not (0.0 < float(yfov) < math.pi) or not float(znear) > 0.0:
+        raise ValueError("render_views: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
+    if sumF >= 2 ** 31:
+        raise ValueError("render_views: 2^31 or more faces in one batch")
+    if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
+        raise ValueError(f"render_views: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
+                         f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
+    if not verts.is_cuda:
+        from .data.render import render_views_cpu
+        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility)
+    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
+    vis = torch.empty((N, views, H, W), dtype=torch.int32, device=verts.device) if return_visibility else None
+    ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+    check(lib().tri_raster_render(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off), ptr(cam),
+                                  N, sumF, views, H, W, float(yfov), float(znear), ptr(ws), ptr(image), ptr(vis), stream()),
+          "tri_raster_render")
+    return (image, vis) if return_visibility else image
+
+
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_tick(step):
     check(lib().tri_adam_tick(ptr(step), stream()), "tri_adam_tick")
