@@ -484,6 +484,23 @@ int tri_raster_render(const float* verts, const int* faces, const long* vert_off
                       const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
                       double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
 
+/* ---- Coloured solid voxel grids from meshes (no counterpart in the reference, which reads downloaded NRRD grids) --------------- */
+/* The packed batch of tri_raster_render plus frame fp32 [N][4] = (origin x, y, z, cell size) per mesh.  grid u8 [N][4][V][V][V],
+ * indexed [channel][x][y][z] (mesh x, y, z -> grid i, j, k); labels (optional) u8 [N][V][V][V]: 0 exterior, 1 surface, 2 interior.
+ * Vertices snap to 1/256 voxel; a voxel is a surface voxel when the closed box [256 i, 256 (i + 1)]^3 and a face overlap (thirteen
+ * separating-axis tests, exact in int64; touching counts; zero-area faces and faces with a vertex beyond 2^17 units are dropped).
+ * Its colour is the rounded mean of floor(255 clamp(Kd, 0, 1) + 0.5) over all overlapping faces, every face weighing the same,
+ * summed with integer atomics: independent of the order in which faces arrive, bit-reproducible.  fill 0 = surface only; fill 1 =
+ * carve: a non-surface voxel with a surface voxel on all six axis rays is interior and takes the colour of the nearest one (ties in
+ * the order -x, +x, -y, +y, -z, +z).  Alpha 255 on surface and interior voxels; everything 0 elsewhere.  A mesh with cell <= 0 or a
+ * non-finite frame gives an all-zero grid.  The arithmetic is spelled out at the head of csrc/voxelize.hip.  workspace:
+ * tri_voxelize_workspace(...) bytes of device memory, 16-byte aligned (0 for sizes tri_voxelize_meshes refuses).  V must be 32, 64
+ * or 128; fewer than 2^24 faces and fewer than 2^31 voxels in one call: TRI_ERR_UNSUPPORTED before anything is launched. */
+size_t tri_voxelize_workspace(long sumF, int N, int V);
+int tri_voxelize_meshes(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                        const float* mat_kd, const long* mat_off, const float* frame, int N, long sumF, int V, int fill, void* workspace,
+                        uint8_t* grid, uint8_t* labels, void* stream);
+
 /* ---- Bicubic antialiased resize of u8 renderings (general_dataset.py:63-65: Resize(image_size, BICUBIC, antialias=True)) ------- */
 /* in [planes][Hin][Win] u8 -> out [planes][Hout][Wout] u8, both contiguous: cast to fp32, the separable bicubic (a = -0.5) antialias
  * filter of ATen's _upsample_bicubic2d_aa (width pass first; per axis scale = n_in / n_out, support = 2 max(scale, 1), windows clipped

@@ -1,0 +1,290 @@
+"""CPU: the torch restatement of csrc/voxelize.hip (ops.voxelize_meshes on CPU tensors) against the exact rational reference of
+tests/voxelize_reference.py on every voxel - alpha, labels and RGB - known answers, the properties the definition promises, and
+python -m tricolo_amd.data.preprocess --voxels mesh on a tree without any NRRD file.
+
+The brute force clips every face against every voxel, so the scenes sit in the low 12^3 corner of a V = 32 grid; the tests assert
+that the snapped mesh lies inside that corner as far as it lies inside the grid, and that the rest of the grid is empty."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import test_preprocess as tp
+from tests import voxelize_reference as vr
+from tricolo_amd import config as tcfg
+from tricolo_amd import ops
+from tricolo_amd.data import preprocess as pp
+from tricolo_amd.data import voxelize as VX
+from tricolo_amd.data.render import pack_materials
+from tricolo_amd.evaluation.mesh import pack_meshes
+
+
+def run(scenes, V, fill="carve", device="cpu"):
+    """ops.voxelize_meshes on a batch of scenes -> (grid uint8 [N, 4, V, V, V], labels uint8 [N, V, V, V]) on the host."""
+    v, f, voff, foff, _ = pack_meshes([s[0] for s in scenes], [s[1] for s in scenes], device)
+    fm, kd, moff = pack_materials([s[2] for s in scenes], [s[3] for s in scenes], device)
+    frame = torch.stack([s[4] for s in scenes]).to(device)
+    grid, labels = ops.voxelize_meshes(v, f, voff, foff, fm, kd, moff, frame, V, fill, return_labels=True)
+    assert grid.shape == (len(scenes), 4, V, V, V) and labels.shape == (len(scenes), V, V, V)
+    assert grid.dtype == torch.uint8 and labels.dtype == torch.uint8 and grid.device.type == torch.device(device).type
+    return grid.cpu(), labels.cpu()
+
+
+def check_invariants(grid, labels):
+    alpha = grid[:, 3]
+    assert ((alpha == 255) == (labels > 0)).all() and ((alpha == 0) | (alpha == 255)).all()
+    assert (grid[:, :3][(alpha == 0)[:, None].expand(-1, 3, -1, -1, -1)] == 0).all()
+    assert int(labels.max()) <= 2
+
+
+def against_reference(scene, what, fills=("carve",), V=32, K=vr.CORNER):
+    """The restatement against the brute force for every fill mode -> (grid, labels) of the first."""
+    ok, G = vr.snap(scene[0].numpy(), scene[4].numpy())
+    for idx in scene[1].tolist():                                                     # every kept face stays below the corner's far faces
+        if all(ok[v] for v in idx):
+            assert all(max(G[v][a] for v in idx) < 256 * K[a] or K[a] == V for a in range(3)), what
+    first = None
+    for fill, (want_grid, want_labels) in zip(fills, vr.reference(scene, V, K, [f == "carve" for f in fills])):
+        grid, labels = run([scene], V, fill)
+        check_invariants(grid, labels)
+        wrong = int((labels[0].numpy() != want_labels).sum()), int((grid[0].numpy() != want_grid).any(0).sum())
+        print(f"{what}, {fill}: {int((want_labels == 1).sum())} surface and {int((want_labels == 2).sum())} interior voxels, {wrong[0]} label and "
+              f"{wrong[1]} colour differences")
+        assert wrong == (0, 0), what
+        first = first or (grid[0], labels[0])
+    return first
+
+
+# ---------------------------------------------------------------------------------------------------- the rational reference
+def test_one_triangle():
+    grid, labels = against_reference(vr.one_triangle(), "one triangle")
+    assert 20 < int((labels == 1).sum()) < 400 and int((labels == 2).sum()) == 0
+    assert (grid[:3][:, labels == 1].t() == torch.tensor(vr.colour_bytes([0], vr.KD3[:1].numpy())[0])).all()      # one material: its bytes
+
+
+def test_random_soup():
+    scene = vr.soup()
+    grid, labels = against_reference(scene, "soup", fills=("carve", "surface"))
+    assert int((labels == 1).sum()) > 200
+    assert len(grid[:3][:, labels == 1].t().unique(dim=0)) > 3                          # mixed colours where materials meet
+
+
+def test_face_in_a_boundary_plane():
+    grid, labels = against_reference(vr.boundary_plane(), "boundary plane")
+    assert (labels[2] == 1).sum() > 0 and torch.equal(labels[2] == 1, labels[3] == 1)    # x = 3 exactly: layers 2 and 3 alike
+    assert (labels[:, :, 4] == 1).sum() > 0 and (labels[:, :, 5] == 1).sum() > 0         # z = 5 exactly
+    assert (labels[:, 1, 5] == 1).any() and (labels[:, 2, 5] == 1).any()                 # its edge along y = 2 touches row 1 as well
+
+
+def test_zero_area_faces():
+    scene = vr.zero_area()
+    grid, labels = against_reference(scene, "zero area")
+    proper = (scene[0], scene[1][[0, 2]], scene[2][[0, 2]], scene[3], scene[4])
+    alone, _ = run([proper], 32)
+    assert torch.equal(alone[0], grid)                                                    # the three degenerate faces leave no trace
+
+
+def test_faces_outside_the_frame():
+    grid, labels = against_reference(vr.outside(), "partly and wholly outside")
+    assert (labels[0] == 1).any() and (labels[:, 0] == 1).any()                           # the cut faces reach the grid's low faces
+    grid, labels = against_reference(vr.touching_from_outside(), "touching the grid from outside")
+    assert int((labels == 1).sum()) >= 1 and int((labels[1:] == 1).sum()) == 0           # layer 0 only
+
+
+def test_face_beyond_the_snap_bound():
+    scene = vr.beyond_snap()
+    grid, labels = against_reference(scene, "beyond the snap bound", K=(32, 12, 12))   # the kept long face crosses the grid along x
+    kept = (scene[0], scene[1][1:], scene[2][1:], scene[3], scene[4])
+    alone, _ = run([kept], 32)
+    assert torch.equal(alone[0], grid)
+    assert (labels[31] == 1).any()                                                        # the kept long face runs to the far side
+
+
+def test_degenerate_frames_give_empty_grids():
+    scene = vr.one_triangle()
+    for bad in ([0.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0, -0.05], [float("nan"), 0.0, 0.0, 0.05], [0.0, float("inf"), 0.0, 0.05], [0.0, 0.0, 0.0, float("inf")]):
+        grid, labels = run([scene[:4] + (torch.tensor(bad, dtype=torch.float32),)], 32)
+        assert not grid.any() and not labels.any(), bad
+
+
+# ---------------------------------------------------------------------------------------------------- known answers
+UNIT = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float32)
+
+
+def test_closed_cube_shell():
+    """Walls at 4.5 and 12.5 (side 8): the shell lies in the voxels 4 .. 12, 9^3 - 7^3 of them, around 7^3 interior ones."""
+    grid, labels = run([vr.box_shell((4.5, 4.5, 4.5), (12.5, 12.5, 12.5), UNIT)], 32)
+    check_invariants(grid, labels)
+    assert int((labels == 1).sum()) == 9 ** 3 - 7 ** 3 and int((labels == 2).sum()) == 7 ** 3
+    assert (labels[0, 5:12, 5:12, 5:12] == 2).all() and (labels[0, 4:13, 4:13, 4:13] > 0).all()
+    surface_only, l2 = run([vr.box_shell((4.5, 4.5, 4.5), (12.5, 12.5, 12.5), UNIT)], 32, "surface")
+    assert torch.equal(l2 == 1, labels == 1) and int((l2 == 2).sum()) == 0
+    assert torch.equal(surface_only[0][:, l2[0] == 1], grid[0][:, labels[0] == 1])
+
+
+def test_box_open_at_the_top_has_no_interior():
+    grid, labels = run([vr.box_shell((4.5, 4.5, 4.5), (12.5, 12.5, 12.5), UNIT, top=False)], 32)
+    assert int((labels == 2).sum()) == 0 and int((labels == 1).sum()) == 9 ** 3 - 7 ** 3 - 7 * 7
+
+
+def test_sphere_volume():
+    """The solid count lies between the volumes of the spheres of radius r -+ sqrt(3) cell."""
+    r = 10.3
+    grid, labels = run([vr.uv_sphere(r, (15.7, 16.2, 15.4), UNIT)], 32)
+    check_invariants(grid, labels)
+    solid = int((labels > 0).sum())
+    lo, hi = (4.0 / 3.0 * math.pi * (r + s * math.sqrt(3.0)) ** 3 for s in (-1, 1))
+    print(f"sphere of radius {r}: {solid} solid voxels, between {lo:.0f} and {hi:.0f}")
+    assert lo <= solid <= hi and int((labels == 2).sum()) > 1000
+
+
+def test_two_colour_cube():
+    """Red top (+y wall), blue elsewhere: an interior voxel is red where the +y ray is strictly shorter than -x, +x and -y, which
+    come before it in the tie order, and no longer than -z and +z, which come after."""
+    grid, labels = run([vr.box_shell((4.5, 4.5, 4.5), (12.5, 12.5, 12.5), UNIT, top_material=1)], 32)
+    red, blue = [255, 0, 0, 255], [0, 0, 255, 255]
+    seen = set()
+    for i in range(5, 12):
+        for j in range(5, 12):
+            for k in range(5, 12):
+                up = 12 - j
+                want = red if up < min(i - 4, 12 - i, j - 4) and up <= min(k - 4, 12 - k) else blue
+                assert grid[0, :, i, j, k].tolist() == want, (i, j, k)
+                seen.add(tuple(want))
+    assert len(seen) == 2
+    assert grid[0, :, 8, 12, 8].tolist() == red and grid[0, :, 4, 8, 8].tolist() == blue
+    assert grid[0, :, 4, 12, 8].tolist() == [128, 0, 128, 255]                           # two red and two blue faces meet: (2 * 510 + 4) / 8
+
+
+# ---------------------------------------------------------------------------------------------------- properties
+def test_face_order_does_not_matter():
+    scene = vr.soup()
+    grid, labels = run([scene], 32)
+    p = torch.from_numpy(np.random.default_rng(5).permutation(scene[1].shape[0]))
+    again, labels2 = run([(scene[0], scene[1][p], scene[2][p], scene[3], scene[4])], 32)
+    assert torch.equal(grid, again) and torch.equal(labels, labels2)
+
+
+def batch_of_three():
+    empty = (torch.zeros((0, 3), dtype=torch.float32), torch.zeros((0, 3), dtype=torch.int64), torch.zeros((0,), dtype=torch.int32),
+             vr.KD3[:1].clone(), vr.FRAME.clone())
+    return [vr.soup(), empty, vr.box_shell((2.5, 3.5, 1.5), (8.5, 7.5, 9.5), UNIT, top_material=1)]
+
+
+def test_batching():
+    scenes = batch_of_three()
+    grid, labels = run(scenes, 32)
+    assert not grid[1].any() and not labels[1].any()
+    for n in (0, 2):
+        g, l = run([scenes[n]], 32)
+        assert torch.equal(g[0], grid[n]) and torch.equal(l[0], labels[n]), f"mesh {n} alone"
+    assert int((labels[2] == 2).sum()) == 5 * 3 * 7
+
+
+def test_default_frames():
+    box = torch.tensor([[-0.25, 0.125, 0.0], [0.75, 0.375, 0.5], [0.0, 0.25, 0.25]], dtype=torch.float32)   # sides 1, 0.25, 0.5 about (0.25, 0.25, 0.25)
+    frames = VX.default_frames([box, torch.zeros((0, 3)), torch.ones((4, 3))], 32)
+    assert frames.dtype == torch.float32 and frames.shape == (3, 4)
+    assert frames[0].tolist() == [-0.25, -0.25, -0.25, 1.0 / 32]
+    assert frames[1].tolist() == [0.0, 0.0, 0.0, 0.0] and frames[2].tolist() == [1.0, 1.0, 1.0, 0.0]            # no vertices; no extent
+    third = torch.tensor([[0.0, 0.0, 0.0], [0.3, 0.1, 0.2]], dtype=torch.float32)
+    f = VX.default_frames([third], 64)[0].numpy().astype(np.float64)
+    cell = float(np.float32(np.float64(np.float32(0.3)) / 64))
+    assert f[3] == cell and f[0] == float(np.float32(0.5 * float(np.float32(0.3)) - 32 * cell))
+    grids = VX.voxelize_meshes([box], [torch.tensor([[0, 1, 2]])], [torch.zeros(1, dtype=torch.int32)], [vr.KD3[:1]], 32)
+    assert grids.shape == (1, 4, 32, 32, 32) and grids[0, 3, 0].any() and grids[0, 3, 31].any()                # the longest side spans the grid
+
+
+def test_voxelize_meshes_refuses_bad_input_before_running():
+    s = vr.one_triangle()
+    v, f, voff, foff, _ = pack_meshes([s[0]], [s[1]])
+    fm, kd, moff = pack_materials([s[2]], [s[3]])
+    frame = s[4][None]
+    with pytest.raises(ValueError, match="V must be"):
+        ops.voxelize_meshes(v, f, voff, foff, fm, kd, moff, frame, 48)
+    with pytest.raises(ValueError, match="fill"):
+        ops.voxelize_meshes(v, f, voff, foff, fm, kd, moff, frame, 32, fill="flood")
+    with pytest.raises(ValueError, match="frame"):
+        ops.voxelize_meshes(v, f, voff, foff, fm, kd, moff, frame[0], 32)
+    with pytest.raises(ValueError, match="face_mat"):
+        ops.voxelize_meshes(v, f, voff, foff, fm[:0], kd, moff, frame, 32)
+
+
+# ---------------------------------------------------------------------------------------------------- preprocessing
+def write_box_model(obj_root, cat, mid, k):
+    """A closed box with a lid of its own material: axis-aligned faces keep the candidate boxes thin, and there is an inside."""
+    d = os.path.join(obj_root, cat, mid, "models")
+    os.makedirs(d, exist_ok=True)
+    x, y, z = 0.2 + 0.03 * k, 0.1 + 0.02 * k, 0.15
+    corners = [(sx * x, sy * y, sz * z) for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]
+    with open(os.path.join(d, "model_normalized.obj"), "w") as f:
+        f.write("mtllib model_normalized.mtl\n" + "".join(f"v {a} {b} {c}\n" for a, b, c in corners))
+        f.write("usemtl body\nf 1 2 4 3\nf 5 7 8 6\nf 1 5 6 2\nf 1 3 7 5\nf 2 6 8 4\nusemtl lid\nf 3 4 8 7\n")
+    with open(os.path.join(d, "model_normalized.mtl"), "w") as f:
+        f.write(f"newmtl body\nKd 0.1 0.5 {0.3 * k}\nnewmtl lid\nKd 0.9 0.2 0.1\n")
+
+
+def dataset_without_nrrd(root, nrrd_for=()):
+    """The tree preprocess.main reads, laid out as tests/test_preprocess.py lays out its own, WITHOUT NRRD grids - except for the
+    model ids in `nrrd_for`, which get random ones -> the overrides that point a config at it."""
+    dataset_path = os.path.join(root, "text2shape-data", "chair_table")
+    for split in pp.SPLITS:
+        tp.write_captions(dataset_path, split)
+    for k, (cat, mid) in enumerate(tp.MODELS[:3]):
+        write_box_model(os.path.join(root, "text2shape-data", "ShapeNetCore.v2"), cat, mid, k)
+        if mid in nrrd_for:
+            g = np.random.default_rng(k)
+            for V in pp.VOXEL_SIZES:
+                grid = np.zeros((4, V, V, V), np.uint8)
+                grid[:, 3:9, 2:7, 4:8] = g.integers(1, 255, (4, 6, 5, 4))
+                os.makedirs(os.path.join(dataset_path, f"nrrd_256_filter_div_{V}_solid", mid), exist_ok=True)
+                tp.write_nrrd(pp.nrrd_path(dataset_path, mid, V), grid, "gzip")
+    return ["data=text2shape_chair_table", f"data.dataset_root_path={root}", "data.num_views=2", "data.image_size=32", "data.voxel_size=32",
+            "data.batch_size=4", "data.ignored_models=[04379243/ignoredD]", "model.text_encoder=BiGRUEncoder", "model.image_encoder=MVCNNEncoder",
+            "model.voxel_encoder=SparseCNNEncoder"]
+
+
+def check_preprocess_from_meshes(root, device):
+    from tricolo_amd.data.dataset import PackedDataset
+    from tricolo_amd.data.materials import load_obj_materials
+    from tricolo_amd.data.nrrd import read_nrrd
+    overrides = dataset_without_nrrd(root)
+    dev = ["--device", device, "--batch-meshes", "2"]
+    with pytest.raises(FileNotFoundError):
+        pp.main(overrides + dev + ["--voxels", "nrrd"], log=lambda *a: None)              # the downloads are still what nrrd needs
+    stats = pp.main(overrides + dev + ["--voxels", "mesh"], log=lambda *a: None)
+    assert stats["train"] == {"models": 3, "written": 3, "skipped": 0}
+    cfg = tcfg.compose(overrides=overrides)
+    exp = cfg.data.exp_data_root_path
+    meshes = [load_obj_materials(os.path.join(root, "text2shape-data", "ShapeNetCore.v2", c, m, "models", "model_normalized.obj")) for c, m in tp.MODELS[:3]]
+    for k, (c, m) in enumerate(tp.MODELS[:3]):
+        with np.load(os.path.join(exp, c, f"{m}.npz")) as z:
+            assert sorted(z.files) == ["images", "voxel128", "voxel32", "voxel64"]
+            for V in pp.VOXEL_SIZES:
+                g = z[f"voxel{V}"]
+                assert g.shape == (4, V, V, V) and g.dtype == np.uint8 and set(np.unique(g[3])) == {0, 255}
+                assert g[3, 0].any() and g[3, V - 1].any() and g[3, V // 2, V // 2, V // 2] == 255      # x spans the grid; the centre is solid
+            want = VX.voxelize_meshes([meshes[k][0]], [meshes[k][1]], [meshes[k][2]], [meshes[k][3]], 32, device=device)
+            assert np.array_equal(z["voxel32"], want[0].cpu().numpy())                     # alone or in its batch: the same grid
+    ds = PackedDataset(cfg, "train", device=device)
+    batch = next(iter(ds.batches(4)(0)))
+    assert batch["voxels"]["rgba"].shape == (4, 4, 32, 32, 32) and batch["voxels"]["rgba"].dtype == torch.uint8
+    assert batch["voxels"]["rgba"][:, 3].flatten(1).any(dim=1).all() and batch["images"].shape == (4, 2, 3, 32, 32)
+    # auto: the files where a model has all three, the mesh otherwise
+    auto_root = os.path.join(root, "auto")
+    overrides = dataset_without_nrrd(auto_root, nrrd_for=("tableB", "chairC"))
+    stats = pp.main(overrides + dev + ["--voxels", "auto"], log=lambda *a: None)
+    assert stats["train"] == {"models": 3, "written": 3, "skipped": 0}
+    cfg = tcfg.compose(overrides=overrides)
+    with np.load(os.path.join(cfg.data.exp_data_root_path, "04379243", "tableB.npz")) as z:
+        for V in pp.VOXEL_SIZES:
+            assert np.array_equal(z[f"voxel{V}"], read_nrrd(os.path.join(cfg.data.dataset_path, f"nrrd_256_filter_div_{V}_solid", "tableB", "tableB.nrrd")))
+    with np.load(os.path.join(cfg.data.exp_data_root_path, "03001627", "chairA.npz")) as z, np.load(os.path.join(exp, "03001627", "chairA.npz")) as m:
+        for V in pp.VOXEL_SIZES:
+            assert np.array_equal(z[f"voxel{V}"], m[f"voxel{V}"])
+
+
+def test_preprocess_from_meshes_on_the_host(tmp_path):
+    check_preprocess_from_meshes(str(tmp_path), "cpu")

@@ -2,16 +2,23 @@
 splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
-        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda]
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
 shapenet.json; for Text2ShapeC13 the existing map file is read instead - and `<exp_data_root_path>/<category>/<model_id>.npz`
-with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V], from the nrrd_256_filter_div_{V}_solid grids, data/nrrd.py) and images
-(uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
+with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V]) and images (uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
 `<dirname(dataset_path)>/ShapeNetCore.v2/<category>/<model_id>/models/model_normalized.obj` by ops.render_views (csrc/raster.hip), a
 batch of meshes per call.  data/render.py says what that renderer restates of the reference's pyrender scene, what it deliberately
 does differently (Lambert shading, flat normals, no culling, no textures) and that no pixel has been compared with pyrender's.
+
+--voxels says where the grids come from.  nrrd (the default): Text2Shape's nrrd_256_filter_div_{V}_solid/<id>/<id>.nrrd downloads
+(data/nrrd.py), which exist for chairs and tables only.  mesh: ops.voxelize_meshes (csrc/voxelize.hip) voxelises the meshes already
+loaded for the renderer, one call per size for the whole batch, so that Text2ShapeC13 or one's own meshes get their grids too.
+auto: the NRRD files where all three exist for a model, the mesh otherwise.  The voxeliser is a definition of our own - surface
+voxels by an exact box / triangle overlap, the mean Kd of all overlapping faces, interiors carved along the six axis rays;
+data/voxelize.py spells it out - and NO GRID OF IT HAS BEEN COMPARED WITH TEXT2SHAPE'S: not the occupancy, not the orientation of
+the grid axes relative to the v2 meshes, not the colour of interior voxels.  The .npz layout is the same either way.
 
 Every .npz is written under a temporary name and renamed; a file that exists is skipped, so an interrupted run resumes.
 --jpeg-roundtrip passes every view through an in-memory JPEG at PIL's default quality, as the reference's img.save("<i>.jpg")
@@ -30,12 +37,13 @@ import numpy as np
 import torch
 
 from .. import config as tcfg
-from . import render
+from . import render, voxelize
 from .materials import load_obj_materials
 from .nrrd import read_nrrd
 
 VOXEL_SIZES = (32, 64, 128)
 SPLITS = ("train", "val", "test")
+VOXEL_SOURCES = ("nrrd", "mesh", "auto")
 
 
 def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
@@ -83,16 +91,33 @@ def jpeg_roundtrip(images):
     return out
 
 
-def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print):
-    """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped)."""
+def nrrd_path(data_root, mid, v):
+    return os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd")
+
+
+def voxelize_batch(meshes, device):
+    """{"voxel32" | "voxel64" | "voxel128": uint8 [len(meshes), 4, V, V, V]}: one ops.voxelize_meshes call per size."""
+    return {f"voxel{v}": voxelize.voxelize_meshes([m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes], [m[3] for m in meshes],
+                                                  v, fill="carve", device=device).cpu().numpy() for v in VOXEL_SIZES}
+
+
+def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd"):
+    """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
+    come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist)."""
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
     for i in range(0, len(todo), batch_meshes):
         batch = todo[i:i + batch_meshes]
         meshes = [load_obj_materials(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
         images = render.render_meshes([m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes], [m[3] for m in meshes],
                                       num_views=num_views, image_size=render.IMAGE_SIZE, device=device).cpu().numpy()
-        for (cat, mid), views in zip(batch, images):
-            grids = {f"voxel{v}": read_nrrd(os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd"), v) for v in VOXEL_SIZES}
+        from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
+                     (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
+        made = voxelize_batch([meshes[k] for k in from_mesh], device) if from_mesh else {}
+        for k, ((cat, mid), views) in enumerate(zip(batch, images)):
+            if k in from_mesh:
+                grids = {name: g[from_mesh.index(k)] for name, g in made.items()}
+            else:
+                grids = {f"voxel{v}": read_nrrd(nrrd_path(data_root, mid, v), v) for v in VOXEL_SIZES}
             os.makedirs(os.path.join(out_root, cat), exist_ok=True)
             path = os.path.join(out_root, cat, f"{mid}.npz")
             tmp = f"{path}.{os.getpid()}.tmp"
@@ -109,7 +134,9 @@ def main(argv=None, log=print):
     ap.add_argument("overrides", nargs="*", help="config overrides, e.g. data=text2shape_chair_table data.dataset_root_path=...")
     ap.add_argument("--batch-meshes", type=int, default=8, help="meshes rendered per call")
     ap.add_argument("--jpeg-roundtrip", action="store_true", help="pass every view through an in-memory JPEG, as the reference's .jpg files do")
-    ap.add_argument("--device", default="cuda", help="cuda (csrc/raster.hip) or cpu (the untuned torch restatement)")
+    ap.add_argument("--device", default="cuda", help="cuda (csrc/raster.hip, csrc/voxelize.hip) or cpu (the untuned torch restatements)")
+    ap.add_argument("--voxels", choices=VOXEL_SOURCES, default="nrrd", help="the grids: the nrrd_256_filter_div_{V}_solid downloads, voxelised "
+                    "from the meshes, or auto (the downloads where all three sizes exist for a model)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.batch_meshes < 1:
         ap.error("--batch-meshes must be positive")
@@ -126,7 +153,7 @@ def main(argv=None, log=print):
         else:
             keys = read_model_ids(map_path)
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
-                                       args.batch_meshes, args.jpeg_roundtrip, log)
+                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels)
         stats[split] = {"models": len(keys), "written": written, "skipped": skipped}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")
     return stats

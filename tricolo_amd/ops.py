@@ -1685,6 +1685,55 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     return (image, vis) if return_visibility else image
 
 
+# ------------------------------------------------------------------------------------------------ mesh voxelisation
+VOXELIZE_SIZES = (32, 64, 128)
+VOXELIZE_MAX_FACES, VOXELIZE_MAX_VOXELS = 2 ** 24, 2 ** 31                       # csrc/voxelize.hip VX_MAX_FACES, VX_MAX_VOXELS
+VOXELIZE_FILL = {"surface": 0, "carve": 1}
+
+
+def voxelize_meshes(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame, V, fill="carve", return_labels=False):
+    """Coloured voxel grids of every mesh of a packed batch (the batch of render_views) -> uint8 [N, 4, V, V, V] indexed
+    [channel, x, y, z], with return_labels also uint8 [N, V, V, V]: 0 exterior, 1 surface, 2 interior.  frame fp32 [N, 4]: per mesh
+    the grid's origin and cell size (data.voxelize.default_frames); a mesh with cell <= 0 or a non-finite frame gives zeros.  The
+    arithmetic is the definition (head of csrc/voxelize.hip): a voxel is on the surface when its closed box overlaps a face snapped
+    to 1/256 voxel, its colour is the rounded mean of the 8-bit Kd of all overlapping faces (each weighs the same); fill="carve"
+    makes every non-surface voxel with a surface voxel on all six axis rays interior, coloured like the nearest of them;
+    fill="surface" keeps the shell.  Alpha is 255 on surface and interior voxels, everything is 0 elsewhere.  V is 32, 64 or 128;
+    one call takes fewer than 2^24 faces and fewer than 2^31 voxels; more raises before anything runs.  CPU tensors run
+    data.voxelize.voxelize_meshes_cpu, the same arithmetic in torch (untuned, for checking)."""
+    V = int(V)
+    if fill not in VOXELIZE_FILL:
+        raise ValueError(f"voxelize_meshes: fill must be one of {sorted(VOXELIZE_FILL)}, got {fill!r}")
+    tensors = (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame)
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("voxelize_meshes: all tensors must live on one device")
+    N = vert_off.numel() - 1
+    _mesh_arg(verts, "verts", torch.float32, 3)
+    _mesh_arg(faces, "faces", torch.int32, 3)
+    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
+    _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
+    _mesh_arg(mat_off, "mat_off", torch.int64, numel=N + 1)
+    _mesh_arg(face_mat, "face_mat", torch.int32, numel=faces.shape[0])
+    _mesh_arg(mat_kd, "mat_kd", torch.float32, 3)
+    if frame.dtype != torch.float32 or frame.shape != (N, 4) or not frame.is_contiguous():
+        raise ValueError(f"frame must be a contiguous float32 tensor of shape [{N}, 4], got {tuple(frame.shape)} {frame.dtype}")
+    sumF = faces.shape[0]
+    if V not in VOXELIZE_SIZES:
+        raise ValueError(f"voxelize_meshes: V must be one of {VOXELIZE_SIZES}, got {V}")
+    if sumF >= VOXELIZE_MAX_FACES or N * V ** 3 >= VOXELIZE_MAX_VOXELS:
+        raise ValueError(f"voxelize_meshes: {sumF} faces, {N} meshes x {V}^3 voxels; one call takes fewer than 2^24 faces and fewer "
+                         "than 2^31 voxels - split the batch")
+    if not verts.is_cuda:
+        from .data.voxelize import voxelize_meshes_cpu
+        return voxelize_meshes_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame, V, VOXELIZE_FILL[fill], return_labels)
+    grid = torch.empty((N, 4, V, V, V), dtype=torch.uint8, device=verts.device)
+    labels = torch.empty((N, V, V, V), dtype=torch.uint8, device=verts.device) if return_labels else None
+    ws = torch.empty((max(16, lib().tri_voxelize_workspace(sumF, N, V)),), dtype=torch.uint8, device=verts.device)
+    check(lib().tri_voxelize_meshes(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off), ptr(frame),
+                                    N, sumF, V, VOXELIZE_FILL[fill], ptr(ws), ptr(grid), ptr(labels), stream()), "tri_voxelize_meshes")
+    return (grid, labels) if return_labels else grid
+
+
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_tick(step):
     check(lib().tri_adam_tick(ptr(step), stream()), "tri_adam_tick")
