@@ -212,6 +212,18 @@ def test_voxelize_meshes_refuses_bad_input_before_running():
         ops.voxelize_meshes(v, f, voff, foff, fm[:0], kd, moff, frame, 32)
 
 
+def test_mesh_batch_pack_refuses_bad_lists():
+    from tricolo_amd.meshes import MeshBatch
+    s = vr.one_triangle()
+    assert MeshBatch.pack([s[0]], [s[1]], [s[2]], [s[3]]).face_mat.shape == (1,)
+    with pytest.raises(ValueError, match="one material index per face"):
+        MeshBatch.pack([s[0]], [s[1]], [s[2][:0]], [s[3]])
+    with pytest.raises(ValueError, match="empty batch"):
+        MeshBatch.pack([], [], [], [])
+    with pytest.raises(ValueError, match="2 vertex arrays but 1 face arrays"):
+        MeshBatch.pack([s[0], s[0]], [s[1]], [s[2]], [s[3]])
+
+
 # ---------------------------------------------------------------------------------------------------- preprocessing
 def write_box_model(obj_root, cat, mid, k):
     """A closed box with a lid of its own material: axis-aligned faces keep the candidate boxes thin, and there is an inside."""
@@ -284,6 +296,21 @@ def check_preprocess_from_meshes(root, device):
     with np.load(os.path.join(cfg.data.exp_data_root_path, "03001627", "chairA.npz")) as z, np.load(os.path.join(exp, "03001627", "chairA.npz")) as m:
         for V in pp.VOXEL_SIZES:
             assert np.array_equal(z[f"voxel{V}"], m[f"voxel{V}"])
+
+
+def test_pack_models_packs_a_batch_once(tmp_path, monkeypatch):
+    """One batch of models is validated, packed and uploaded once: the renderer and the three voxel sizes share it."""
+    from tricolo_amd import meshes
+    obj_root, calls = str(tmp_path / "obj"), []
+    for k, (cat, mid) in enumerate(tp.MODELS[:2]):
+        write_box_model(obj_root, cat, mid, k)
+    pack_meshes = meshes.pack_meshes
+    monkeypatch.setattr(meshes, "pack_meshes", lambda *a, **kw: calls.append(len(a[0])) or pack_meshes(*a, **kw))
+    done = pp.pack_models(tp.MODELS[:2], obj_root, str(tmp_path / "none"), str(tmp_path / "out"), 2, "cpu", batch_meshes=2, log=lambda *a: None,
+                          voxels="mesh")
+    assert done == (2, 0) and calls == [2]
+    with np.load(str(tmp_path / "out" / tp.MODELS[0][0] / f"{tp.MODELS[0][1]}.npz")) as z:
+        assert sorted(z.files) == ["images", "voxel128", "voxel32", "voxel64"]
 
 
 def test_preprocess_from_meshes_on_the_host(tmp_path):

@@ -17,17 +17,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import raster_reference as rr                      # noqa: E402
 from tricolo_amd import ops                                  # noqa: E402
 from tricolo_amd.data import render as R                     # noqa: E402
-from tricolo_amd.evaluation.mesh import pack_meshes          # noqa: E402
+from tricolo_amd.meshes import MeshBatch                     # noqa: E402
 
 VIEWS, SIZE = 12, 224
 
 
 def batch(rings, n, dev):
     pv, pf, pm, pk = rr.procedural_mesh(rings)
-    v, f, voff, foff, _ = pack_meshes([pv] * n, [pf] * n, dev)
-    fm, kd, moff = R.pack_materials([pm] * n, [pk] * n, dev)
-    cam = R.pack_cameras([R.bbox_center(pv)] * n, VIEWS, dev)
-    return pf.shape[0], (v, f, voff, foff, fm, kd, moff, cam, SIZE, SIZE)
+    packed = MeshBatch.pack([pv] * n, [pf] * n, [pm] * n, [pk] * n, dev)
+    return pf.shape[0], (*packed.tensors, R.pack_cameras(R.box_centers(packed.boxes), VIEWS, dev), SIZE, SIZE)
 
 
 def main():

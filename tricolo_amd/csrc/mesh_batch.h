@@ -1,0 +1,77 @@
+// The packed batch of N triangle meshes that mesh_sample.hip, raster.hip and voxelize.hip work on, and the conventions all three keep;
+// tricolo_amd/meshes.py packs it on the host (MeshBatch.pack).  Mesh n owns the rows off[n] .. off[n + 1] - 1 of its arrays:
+//   verts fp32 [sumV][3] by vert_off, faces int32 [sumF][3] and face_mat int32 [sumF] by face_off, mat_kd fp32 [sumM][3] by mat_off;
+//   the three offset arrays are int64 [N + 1].
+// A face holds vertex indices LOCAL to its mesh, face_mat a material index local to the mesh; mat_kd holds diffuse colours.  The host
+// validates the indices; the kernels still read each as unsigned and clamp it to the mesh's last vertex (material), so a bad index
+// never reads beyond the mesh.  A mesh without vertices has nothing to clamp to - every kernel checks V > 0 first - and a mesh without
+// materials is grey 0.4.  The sampler has no use for materials and leaves the three material fields null.
+//
+// Contraction is switched off HERE, not only in the including files: `#pragma clang fp contract(off)` covers the code that follows it,
+// so a helper defined in a header ahead of the including file's own pragma would be compiled with contraction on - a * b + c became
+// v_fmac_f32 in such a helper while the same expression in a kernel body stayed a multiply and an add.  With an fma the cross product
+// of a face with b == c is a rounding error instead of exactly 0, and the torch restatements could not form the same bits.
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+typedef unsigned long long u64;
+
+struct MeshBatch {
+    const float* __restrict__ verts;
+    const int* __restrict__ faces;
+    const long* __restrict__ vert_off;
+    const long* __restrict__ face_off;
+    const int* __restrict__ face_mat;
+    const float* __restrict__ mat_kd;
+    const long* __restrict__ mat_off;
+    int N;
+};
+
+// the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
+__device__ __forceinline__ int mb_mesh_of(const MeshBatch& m, long gf) {
+    int lo = 0, hi = m.N;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (m.face_off[mid] <= gf) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// vertex i of the mesh that owns the V > 0 vertices from v0: a bad index reads the mesh's own last vertex, never beyond it
+__device__ __forceinline__ const float* mb_vertex(const MeshBatch& m, long v0, long V, int i) {
+    return m.verts + (size_t)(v0 + min((long)(unsigned)i, V - 1)) * 3;
+}
+
+// the diffuse colour of global face gf of mesh n: a bad material index reads the mesh's own last material; grey without materials
+__device__ __forceinline__ void mb_face_kd(const MeshBatch& m, int n, long gf, float* kd) {
+    const long m0 = m.mat_off[n], M = m.mat_off[n + 1] - m0;
+    const long j = min((long)(unsigned)m.face_mat[gf], M - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) kd[k] = M > 0 ? m.mat_kd[(size_t)(m0 + j) * 3 + k] : 0.4f;
+}
+
+// o = (b - a) x (c - a) in fp32, every operation rounded on its own
+__device__ __forceinline__ void mb_cross(const float* a, const float* b, const float* c, float* o) {
+    const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+    const float wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2];
+    o[0] = uy * wz - uz * wy; o[1] = uz * wx - ux * wz; o[2] = ux * wy - uy * wx;
+}
+
+// The correctly rounded quotient and root (what numpy and torch give on the host).  __fsqrt_rn compiles to the bare v_sqrt_f32 here,
+// 1 ulp off in a third of the cases, which biased the sampler's CDF by 2^-26 of the total against the cumsum of the fp32 areas.  Through
+// float64 the result is exact: a correctly rounded 53-bit result rounded again to 24 bits equals the directly rounded one (53 >= 2 * 24 + 2).
+__device__ __forceinline__ float mb_div(float a, float b) { return (float)((double)a / (double)b); }
+__device__ __forceinline__ float mb_sqrt(float x) { return (float)sqrt((double)x); }
+
+// Queue append.  EVERY lane of the wave must call this; one atomic add on *counter per wave, the slots in lane order.  Returns the
+// slot of a lane with pred set (the caller checks it against the queue's capacity); the value means nothing in the other lanes.
+__device__ __forceinline__ u64 mb_queue_slot(bool pred, u64* __restrict__ counter) {
+    const u64 mask = __ballot(pred);
+    if (!mask) return 0;
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
+    u64 base = 0;
+    if (lane == leader) base = atomicAdd(counter, (u64)__popcll(mask));
+    return __shfl(base, leader) + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
+}

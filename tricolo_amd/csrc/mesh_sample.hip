@@ -1,7 +1,6 @@
 // Surface samples of triangle meshes (the front half of the reference's calculate_f1.py: pytorch3d's Meshes.get_bounding_boxes,
 // scale_verts and sample_points_from_meshes): per-mesh bounding boxes, the float64 CDF of the fp32 face areas, and S area-weighted
-// points per mesh from a counter-based generator - all on a packed batch of N meshes (verts [sumV][3], faces int32 [sumF][3] local
-// to the mesh, vert_off / face_off int64 [N + 1]).
+// points per mesh from a counter-based generator - all on the packed batch of N meshes that mesh_batch.h lays out (without materials).
 //
 //   area[f]  = 0.5 * |(b - a) x (c - a)|, fp32, on the scaled vertices fl32(v * scale[n]); every operation rounded on its own
 //              (contraction is off in this file: with an fma the cross product of a face with b == c would be a rounding error
@@ -14,7 +13,7 @@
 //   sample   = Philox4x32-10(key = seed, counter = (s, n, 0, 0)) -> u_f, u1, u2 (24 bits each); face = the smallest f with
 //              cdf[f] > u_f * total (float64); point = (1 - r) a + r (1 - u2) b + r u2 c with r = sqrtf(u1), fp32.
 // No floating-point atomics anywhere; two runs give the same bits.
-#include "common.h"
+#include "mesh_batch.h"
 #include "../../include/tricolo_hip.h"
 
 #pragma clang fp contract(off)
@@ -62,29 +61,21 @@ extern "C" int tri_mesh_bbox(const float* verts, const long* vert_off, int N, fl
     return tri_check_launch("tri_mesh_bbox");
 }
 
-// sqrtf, correctly rounded (what numpy and torch give on the host): __fsqrt_rn compiles to the bare v_sqrt_f32 here, 1 ulp off in a
-// third of the cases, which biased the CDF by 2^-26 of the total against the cumsum of the fp32 areas.  Through float64 the result is
-// exact: a correctly rounded 53-bit root rounded again to 24 bits equals the directly rounded one (53 >= 2 * 24 + 2).
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
-
 // ---- face areas + CDF -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load_scaled(const float* __restrict__ verts, long v0, long V, int i, float s, float* o) {
-    const long j = min((long)(unsigned)i, V - 1);                      // a bad index reads the mesh's own last vertex, never beyond it
-    const float* p = verts + (size_t)(v0 + j) * 3;
+__device__ __forceinline__ void load_scaled(const MeshBatch& m, long v0, long V, int i, float s, float* o) {
+    const float* p = mb_vertex(m, v0, V, i);
     o[0] = p[0] * s; o[1] = p[1] * s; o[2] = p[2] * s;
 }
 
-__device__ __forceinline__ float face_area(const float* __restrict__ verts, const int* __restrict__ faces, long v0, long V, long f, float s) {
+__device__ __forceinline__ float face_area(const MeshBatch& m, long v0, long V, long f, float s) {
     if (V <= 0) return 0.f;
-    const int* fi = faces + (size_t)f * 3;
-    float a[3], b[3], c[3];
-    load_scaled(verts, v0, V, fi[0], s, a);
-    load_scaled(verts, v0, V, fi[1], s, b);
-    load_scaled(verts, v0, V, fi[2], s, c);
-    const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-    const float vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
-    const float cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
-    return 0.5f * sqrt_rn((cx * cx + cy * cy) + cz * cz);
+    const int* fi = m.faces + (size_t)f * 3;
+    float a[3], b[3], c[3], x[3];
+    load_scaled(m, v0, V, fi[0], s, a);
+    load_scaled(m, v0, V, fi[1], s, b);
+    load_scaled(m, v0, V, fi[2], s, c);
+    mb_cross(a, b, c, x);
+    return 0.5f * mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
 }
 
 // the value every lane before `lane` ended on: one serial chain over the 64 lanes (fixed order), every lane keeps its own step
@@ -99,14 +90,13 @@ __device__ __forceinline__ double wave_chain(double x, double start, int lane, d
 }
 
 // pass 1: chunk c of mesh n -> cdf[f] = fl(wb + fl(lb + loc)), the chunk-local CDF (final for chunk 0)
-__global__ __launch_bounds__(MS_THREADS) void mesh_cdf_local_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                    const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                    const float* __restrict__ scale, long n0, double* __restrict__ cdf) {
+__global__ __launch_bounds__(MS_THREADS) void mesh_cdf_local_kernel(MeshBatch m, const float* __restrict__ scale, long n0,
+                                                                    double* __restrict__ cdf) {
     __shared__ float sa[MS_CHUNK];
     __shared__ double sc[MS_CHUNK];
     __shared__ double wtot[4];
     const long n = n0 + blockIdx.y;
-    const long f0 = face_off[n], F = face_off[n + 1] - f0, v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
     const float s = scale ? scale[n] : 1.f;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const long nchunks = (F + MS_CHUNK - 1) / MS_CHUNK;
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_cdf_local_kernel(const float*
 #pragma unroll
         for (int k = 0; k < MS_K; ++k) {                                // coalesced over the faces; faces past the end add 0
             const int j = k * MS_THREADS + t;
-            sa[j] = j < cnt ? face_area(verts, faces, v0, V, f0 + base + j, s) : 0.f;
+            sa[j] = j < cnt ? face_area(m, v0, V, f0 + base + j, s) : 0.f;
         }
         __syncthreads();
         double loc[MS_K], run = 0.0;
@@ -184,12 +174,12 @@ extern "C" int tri_mesh_face_cdf(const float* verts, const int* faces, const lon
     if (max_faces >= (1L << 31)) { tri_set_error("tri_mesh_face_cdf: 2^31 or more faces in a mesh"); return TRI_ERR_UNSUPPORTED; }
     if (N == 0) return TRI_OK;
     hipStream_t st = (hipStream_t)stream;
+    const MeshBatch m{verts, faces, vert_off, face_off, nullptr, nullptr, nullptr, N};
     // blockIdx.x walks the chunks of a mesh (grid-stride), blockIdx.y the meshes; max_faces (>= every mesh's face count) sizes the grid
     const long chunks = max(1L, min((max_faces + MS_CHUNK - 1) / MS_CHUNK, 4096L));
     const long per_launch = max(1L, min((long)MS_MAX_GRID_Y, (long)MS_MAX_BLOCKS / chunks));
     for (long n0 = 0; n0 < N; n0 += per_launch)
-        mesh_cdf_local_kernel<<<dim3((unsigned)chunks, (unsigned)min(per_launch, N - n0)), MS_THREADS, 0, st>>>(verts, faces, vert_off, face_off,
-                                                                                                             scale, n0, cdf);
+        mesh_cdf_local_kernel<<<dim3((unsigned)chunks, (unsigned)min(per_launch, N - n0)), MS_THREADS, 0, st>>>(m, scale, n0, cdf);
     mesh_cdf_chain_kernel<<<(unsigned)(((long)N + 3) / 4), MS_THREADS, 0, st>>>(face_off, N, cdf, total);
     if (max_faces > MS_CHUNK)
         for (long n0 = 0; n0 < N; n0 += per_launch)
@@ -215,9 +205,7 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 // per thread in lockstep so that four such chains are in flight.  Points leave through LDS as consecutive dwords (a lane's own 12 bytes
 // would be three stride-12 stores per wave).
 template <bool IDX>
-__global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                 const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                 const float* __restrict__ scale, const double* __restrict__ cdf,
+__global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(MeshBatch m, const float* __restrict__ scale, const double* __restrict__ cdf,
                                                                  const double* __restrict__ total, int S, int tiles, long n0, uint32_t k0,
                                                                  uint32_t k1, float* __restrict__ points, long* __restrict__ face_idx) {
     __shared__ double coarse[MS_COARSE];
@@ -226,7 +214,7 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(const float* __
     const long n = n0 + blockIdx.x / (unsigned)tiles;
     const int s0 = (int)(blockIdx.x % (unsigned)tiles) * MS_TILE;
     const int cnt = min(MS_TILE, S - s0);
-    const long f0 = face_off[n], F = face_off[n + 1] - f0, v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
     const double A = F > 0 ? total[n] : 0.0;
     float* out = points + ((size_t)n * S + s0) * 3;
     if (!(F > 0 && V > 0 && A > 0.0 && A < INFINITY)) {                // nothing to sample from: zero rows, -1 (pytorch3d zero-fills)
@@ -270,12 +258,12 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(const float* __
         const int j = r * MS_THREADS + t;
         if (j >= cnt) continue;
         const long f = min(lo[r], F - 1);
-        const int* fi = faces + (size_t)(f0 + f) * 3;
+        const int* fi = m.faces + (size_t)(f0 + f) * 3;
         float a[3], b[3], c[3];
-        load_scaled(verts, v0, V, fi[0], sc, a);
-        load_scaled(verts, v0, V, fi[1], sc, b);
-        load_scaled(verts, v0, V, fi[2], sc, c);
-        const float rt = sqrt_rn(u1[r]);
+        load_scaled(m, v0, V, fi[0], sc, a);
+        load_scaled(m, v0, V, fi[1], sc, b);
+        load_scaled(m, v0, V, fi[2], sc, c);
+        const float rt = mb_sqrt(u1[r]);
         const float w0 = 1.0f - rt, w1 = rt * (1.0f - u2[r]), w2 = rt * u2[r];
 #pragma unroll
         for (int k = 0; k < 3; ++k) sp[j * 3 + k] = (w0 * a[k] + w1 * b[k]) + w2 * c[k];
@@ -293,14 +281,13 @@ extern "C" int tri_mesh_sample_points(const float* verts, const int* faces, cons
     const int tiles = (S + MS_TILE - 1) / MS_TILE;
     const long per_launch = max(1L, (long)MS_MAX_BLOCKS / tiles);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const MeshBatch m{verts, faces, vert_off, face_off, nullptr, nullptr, nullptr, N};
     for (long n0 = 0; n0 < N; n0 += per_launch) {
         const unsigned blocks = (unsigned)(min(per_launch, N - n0) * tiles);
         if (face_idx)
-            mesh_sample_kernel<true><<<blocks, MS_THREADS, 0, (hipStream_t)stream>>>(verts, faces, vert_off, face_off, scale, cdf, total, S,
-                                                                                    tiles, n0, k0, k1, points, face_idx);
+            mesh_sample_kernel<true><<<blocks, MS_THREADS, 0, (hipStream_t)stream>>>(m, scale, cdf, total, S, tiles, n0, k0, k1, points, face_idx);
         else
-            mesh_sample_kernel<false><<<blocks, MS_THREADS, 0, (hipStream_t)stream>>>(verts, faces, vert_off, face_off, scale, cdf, total, S,
-                                                                                     tiles, n0, k0, k1, points, face_idx);
+            mesh_sample_kernel<false><<<blocks, MS_THREADS, 0, (hipStream_t)stream>>>(m, scale, cdf, total, S, tiles, n0, k0, k1, points, face_idx);
     }
     return tri_check_launch("tri_mesh_sample_points");
 }

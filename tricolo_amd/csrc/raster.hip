@@ -1,7 +1,6 @@
 // Multi-view rendering of a packed batch of triangle meshes (the renderer behind data/preprocess_all_data.py:44-82 of the reference,
-// restated as a rasteriser: visibility by a 64-bit atomic max, flat Lambert shading).  The packed batch is the one of mesh_sample.hip
-// (verts [sumV][3], faces int32 [sumF][3] local to the mesh, vert_off / face_off int64 [N + 1]) plus a material index per face, a
-// table of diffuse colours per mesh and, per (mesh, view), the camera: eye[3] and the 3 x 3 world-to-camera rotation R (row major).
+// restated as a rasteriser: visibility by a 64-bit atomic max, flat Lambert shading).  The packed batch is the one mesh_batch.h lays out, with
+// its materials; per (mesh, view) there is the camera: eye[3] and the 3 x 3 world-to-camera rotation R (row major).
 // The kernel is DEFINED by its arithmetic; tricolo_amd/data/render.py restates it in torch and gives the same bits.
 //
 //   setup (per view and face, fp32, every operation rounded on its own - contraction is off in this file; a / b is the correctly
@@ -28,7 +27,7 @@
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_batch.h"
 #include "../../include/tricolo_hip.h"
 
 #pragma clang fp contract(off)
@@ -41,11 +40,6 @@
 #define RS_MAX_PIXELS (1L << 31)
 #define RS_KDIFF 0.95492965f                    // fl32(3 / pi): intensity 3, Lambert's 1 / pi
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ float rs_div(float a, float b) { return (float)((double)a / (double)b); }
-__device__ __forceinline__ float rs_sqrt(float x) { return (float)sqrt((double)x); }
-
 struct RsFace {
     long A2, e[3];                              // doubled area (> 0); the edge functions at the centre of pixel (x0, y0)
     int sx[3], sy[3], bias[3];                  // their steps per pixel in x and y; 0 on a top / left edge, -1 otherwise
@@ -53,43 +47,31 @@ struct RsFace {
     int x0, x1, y0, y1;                         // the box of pixel centres, clipped to the image
 };
 
-// the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
-__device__ __forceinline__ int rs_mesh_of(const long* __restrict__ face_off, int N, long gf) {
-    int lo = 0, hi = N;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (face_off[mid] <= gf) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool rs_setup(const float* __restrict__ verts, const int* __restrict__ faces, const long* __restrict__ vert_off,
-                                         const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx, float fy,
-                                         float znear, RsFace& o) {
-    const long v0 = vert_off[n], V = vert_off[n + 1] - v0;
+__device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
+                                         float fy, float znear, RsFace& o) {
+    const long v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
     if (V <= 0) return false;
     const float* c = cam + (size_t)nv * 12;
-    const int* fi = faces + (size_t)gf * 3;
+    const int* fi = m.faces + (size_t)gf * 3;
     const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
     int X[3], Y[3];
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const long j = min((long)(unsigned)fi[k], V - 1);              // a bad index reads the mesh's own last vertex, never beyond it
-        const float* p = verts + (size_t)(v0 + j) * 3;
+        const float* p = mb_vertex(m, v0, V, fi[k]);
         const float qx = p[0] - c[0], qy = p[1] - c[1], qz = p[2] - c[2];
         const float px = (c[3] * qx + c[4] * qy) + c[5] * qz;
         const float py = (c[6] * qx + c[7] * qy) + c[8] * qz;
         const float nz = -((c[9] * qx + c[10] * qy) + c[11] * qz);
         const bool front = nz >= znear;                                 // false for NaN
         const float z = front ? nz : 1.f;
-        const float xf = rintf(((rs_div(fx * px, z) + 1.0f) * hw) * 256.f);
-        const float yf = rintf(((1.0f - rs_div(fy * py, z)) * hh) * 256.f);
+        const float xf = rintf(((mb_div(fx * px, z) + 1.0f) * hw) * 256.f);
+        const float yf = rintf(((1.0f - mb_div(fy * py, z)) * hh) * 256.f);
         const bool in = fabsf(xf) <= RS_SNAP_MAX && fabsf(yf) <= RS_SNAP_MAX;
         ok = ok && front && in;
         X[k] = in ? (int)xf : 0;
         Y[k] = in ? (int)yf : 0;
-        o.d[k] = rs_div(1.0f, z);
+        o.d[k] = mb_div(1.0f, z);
     }
     if (!ok) return false;
     long A2 = (long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long)(X[2] - X[0]) * (Y[1] - Y[0]);
@@ -122,7 +104,7 @@ __device__ __forceinline__ bool rs_setup(const float* __restrict__ verts, const 
 __device__ __forceinline__ void rs_pixel(const RsFace& f, long e0, long e1, long e2, u64* __restrict__ kp, unsigned low) {
     if (((e0 + f.bias[0]) | (e1 + f.bias[1]) | (e2 + f.bias[2])) < 0) return;
     const float fa = (float)(double)f.A2;
-    const float l0 = rs_div((float)(double)e0, fa), l1 = rs_div((float)(double)e1, fa), l2 = rs_div((float)(double)e2, fa);
+    const float l0 = mb_div((float)(double)e0, fa), l1 = mb_div((float)(double)e1, fa), l2 = mb_div((float)(double)e2, fa);
     const float d = (l0 * f.d[0] + l1 * f.d[1]) + l2 * f.d[2];
     const u64 key = ((u64)__float_as_uint(d) << 32) | low;
     if (*kp < key) atomicMax(kp, key);                                  // keys only grow: a stale read costs an atomic, never a pixel
@@ -134,37 +116,25 @@ __global__ __launch_bounds__(RS_THREADS) void raster_clear_kernel(u64* __restric
 }
 
 // blockIdx.y = view, one lane per face of the whole batch
-__global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                  const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                  const float* __restrict__ cam, int N, long sumF, int views, int H, int W,
+__global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(MeshBatch m, const float* __restrict__ cam, long sumF, int views, int H, int W,
                                                                   float fx, float fy, float znear, u64* __restrict__ keys,
                                                                   u64* __restrict__ qcount, uint2* __restrict__ queue, u64 qcap) {
     const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-    const int view = blockIdx.y, lane = threadIdx.x & 63;
+    const int view = blockIdx.y;
     RsFace f;
     bool live = false, big = false;
     int n = 0;
     long nv = 0;
     if (gf < sumF) {
-        n = rs_mesh_of(face_off, N, gf);
+        n = mb_mesh_of(m, gf);
         nv = (long)n * views + view;
-        live = rs_setup(verts, faces, vert_off, cam, gf, n, nv, H, W, fx, fy, znear, f);
+        live = rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f);
         big = live && (f.x1 - f.x0 >= RS_SMALL || f.y1 - f.y0 >= RS_SMALL);
     }
-    // queue append: every lane of the wave is here; one atomic add per wave, the slots in lane order
-    const u64 mask = __ballot(big);
-    if (mask) {
-        const int leader = __ffsll((long long)mask) - 1;
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd(qcount, (u64)__popcll(mask));
-        base = __shfl(base, leader);
-        if (big) {
-            const u64 slot = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
-            if (slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
-        }
-    }
+    const u64 slot = mb_queue_slot(big, qcount);                        // every lane of the wave is here
+    if (big && slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
     if (!live || big) return;
-    const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - face_off[n]);
+    const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
     u64* row = keys + ((size_t)nv * H + f.y0) * W;
     long r0 = f.e[0], r1 = f.e[1], r2 = f.e[2];
     for (int y = f.y0; y <= f.y1; ++y, row += W, r0 += f.sy[0], r1 += f.sy[1], r2 += f.sy[2]) {
@@ -174,20 +144,18 @@ __global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(const float* _
 }
 
 // fixed grid; workgroup b takes queue entries b, b + gridDim.x, ... up to the count the first kernel left on the device
-__global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                  const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                  const float* __restrict__ cam, int N, int views, int H, int W, float fx,
+__global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, float fx,
                                                                   float fy, float znear, u64* __restrict__ keys,
                                                                   const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
     const u64 count = min(*qcount, qcap);
     for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
         const uint2 item = queue[q];
         const long gf = item.x;
-        const int n = rs_mesh_of(face_off, N, gf);
+        const int n = mb_mesh_of(m, gf);
         const long nv = (long)n * views + (int)item.y;
         RsFace f;
-        if (!rs_setup(verts, faces, vert_off, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;    // the same answer in every lane
-        const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - face_off[n]);
+        if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;                      // the same answer in every lane
+        const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
         const int bw = f.x1 - f.x0 + 1, cnt = bw * (f.y1 - f.y0 + 1);
         u64* box = keys + ((size_t)nv * H + f.y0) * W + f.x0;
         for (int i = threadIdx.x; i < cnt; i += RS_THREADS) {
@@ -199,19 +167,16 @@ __global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(const float* _
 }
 
 // one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                    const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                    const int* __restrict__ face_mat, const float* __restrict__ mat_kd,
-                                                                    const long* __restrict__ mat_off, const float* __restrict__ cam,
-                                                                    int views, int HW, long npix, const u64* __restrict__ keys,
-                                                                    uint8_t* __restrict__ image, int* __restrict__ visibility) {
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int HW, long npix,
+                                                                    const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                                    int* __restrict__ visibility) {
     const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
     if (i >= npix) return;
     const long nv = i / HW;
     const int pix = (int)(i - nv * HW), n = (int)(nv / views);
     const u64 key = keys[i];
     uint8_t* out = image + (size_t)nv * 3 * HW + pix;
-    const long f0 = face_off[n], F = face_off[n + 1] - f0, v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
     const long lf = (long)(0xFFFFFFFFu - (unsigned)key);
     if (key == 0 || lf >= F || V <= 0) {
         out[0] = 255; out[HW] = 255; out[2 * (size_t)HW] = 255;
@@ -219,29 +184,24 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(const float*
         return;
     }
     if (visibility) visibility[i] = (int)lf;
-    const int* fi = faces + (size_t)(f0 + lf) * 3;
-    const float* a = verts + (size_t)(v0 + min((long)(unsigned)fi[0], V - 1)) * 3;
-    const float* b = verts + (size_t)(v0 + min((long)(unsigned)fi[1], V - 1)) * 3;
-    const float* c = verts + (size_t)(v0 + min((long)(unsigned)fi[2], V - 1)) * 3;
+    const int* fi = m.faces + (size_t)(f0 + lf) * 3;
+    const float *a = mb_vertex(m, v0, V, fi[0]), *b = mb_vertex(m, v0, V, fi[1]), *c = mb_vertex(m, v0, V, fi[2]);
     const float* eye = cam + (size_t)nv * 12;
-    const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-    const float wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2];
-    const float cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
-    const float len = rs_sqrt((cx * cx + cy * cy) + cz * cz);
+    float x[3], kd[3];
+    mb_cross(a, b, c, x);
+    const float len = mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
     const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
-    const float side = (cx * ex + cy * ey) + cz * ez;
+    const float side = (x[0] * ex + x[1] * ey) + x[2] * ez;
     float ndl = 0.f;
     if (len > 0.f) {
-        const float ny = rs_div(cy, len);
+        const float ny = mb_div(x[1], len);
         ndl = fmaxf(side < 0.f ? -ny : ny, 0.f);
     }
     const float shade = 0.1f + RS_KDIFF * ndl;
-    const long m0 = mat_off[n], M = mat_off[n + 1] - m0;
-    const long m = min((long)(unsigned)face_mat[f0 + lf], M - 1);
+    mb_face_kd(m, n, f0 + lf, kd);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float kd = M > 0 ? mat_kd[(size_t)(m0 + m) * 3 + k] : 0.4f;
-        const float col = fminf(fmaxf(kd * shade, 0.f), 1.f);
+        const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
         out[(size_t)k * HW] = (uint8_t)(int)floorf(255.f * col + 0.5f);
     }
 }
@@ -276,14 +236,14 @@ extern "C" int tri_raster_render(const float* verts, const int* faces, const lon
     const u64 qcap = (u64)sumF * views;
     const double fyd = 1.0 / tan(yfov / 2.0);
     const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
     raster_clear_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(keys, npix, qcount);
     if (sumF > 0) {
         raster_faces_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
-            verts, faces, vert_off, face_off, cam, N, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
-        raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(verts, faces, vert_off, face_off, cam, N, views, H, W, fx, fy, zn, keys,
-                                                                    qcount, queue, qcap);
+            m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+        raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
     }
-    raster_resolve_kernel<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(
-        verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, views, H * W, npix, keys, image, visibility);
+    raster_resolve_kernel<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H * W, npix, keys, image,
+                                                                                                   visibility);
     return tri_check_launch("tri_raster_render");
 }

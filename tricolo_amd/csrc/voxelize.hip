@@ -1,9 +1,8 @@
 // Coloured solid voxel grids from a packed batch of triangle meshes: the voxel32 / voxel64 / voxel128 entries of a packed .npz made from
 // model_normalized.obj instead of the downloaded nrrd_256_filter_div_{V}_solid grids.  The reference has no voxeliser (it reads those
 // files), so this is a definition of our own; NOBODY HAS COMPARED A GRID WITH TEXT2SHAPE'S - not the occupancy, not the orientation
-// relative to the v2 meshes, not the colour of interior voxels.  The packed batch is the one of raster.hip (verts [sumV][3], faces
-// int32 [sumF][3] local to the mesh with the same unsigned clamp of bad indices, vert_off / face_off int64 [N + 1], face_mat, mat_kd,
-// mat_off) plus, per mesh, a frame fp32 [4] = (origin x, y, z, cell size); mesh x, y, z map to grid i, j, k.
+// relative to the v2 meshes, not the colour of interior voxels.  The packed batch is the one mesh_batch.h lays out, with its
+// materials; per mesh there is a frame fp32 [4] = (origin x, y, z, cell size); mesh x, y, z map to grid i, j, k.
 // The kernel is DEFINED by its arithmetic; tricolo_amd/data/voxelize.py restates it in torch and gives the same bits.
 //
 //   snap (per vertex and axis; contraction is off in this file): t = fl32(fl64(v - o) / fl64(cell)) with v - o an fp32 subtraction,
@@ -39,7 +38,7 @@
 // three axes (V / 32 words a row, 3 V^3 / 8 bytes a mesh, served from L2): clz / ffs on the row words give the two rays of an axis.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_batch.h"
 #include "../../include/tricolo_hip.h"
 
 #pragma clang fp contract(off)
@@ -56,8 +55,6 @@
 #define VX_MAX_VOXELS (1L << 31)
 #define VX_MAX_FACES (1L << 24)                 // 255 * 2^24 < 2^32: the 32-bit fields of the colour sums never carry
 
-typedef unsigned long long u64;
-
 struct VxFace {
     long n[3], nd, nr;                          // the normal, n . G_0, 128 |n|_1
     int ca[9], cb[9];                           // axis 3 j + i = e_i x f_j: its components along (i + 1) % 3 and (i + 2) % 3
@@ -65,36 +62,24 @@ struct VxFace {
     int b0[3], b1[3];                           // the candidate index range per axis, clipped to the grid
 };
 
-// the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
-__device__ __forceinline__ int vx_mesh_of(const long* __restrict__ face_off, int N, long gf) {
-    int lo = 0, hi = N;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (face_off[mid] <= gf) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ long vx_abs(long x) { return x < 0 ? -x : x; }
 
-__device__ __forceinline__ bool vx_setup(const float* __restrict__ verts, const int* __restrict__ faces, const long* __restrict__ vert_off,
-                                         const float* __restrict__ frame, long gf, int n, int V, VxFace& o) {
-    const long v0 = vert_off[n], NV = vert_off[n + 1] - v0;
+__device__ __forceinline__ bool vx_setup(const MeshBatch& m, const float* __restrict__ frame, long gf, int n, int V, VxFace& o) {
+    const long v0 = m.vert_off[n], NV = m.vert_off[n + 1] - v0;
     if (NV <= 0) return false;
     const float* fr = frame + (size_t)n * 4;
     const float cell = fr[3];
     if (!(cell > 0.f) || !(cell < INFINITY) || !(fabsf(fr[0]) < INFINITY) || !(fabsf(fr[1]) < INFINITY) || !(fabsf(fr[2]) < INFINITY)) return false;
-    const int* fi = faces + (size_t)gf * 3;
+    const int* fi = m.faces + (size_t)gf * 3;
     int G[3][3];
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const long j = min((long)(unsigned)fi[k], NV - 1);             // a bad index reads the mesh's own last vertex, never beyond it
-        const float* p = verts + (size_t)(v0 + j) * 3;
+        const float* p = mb_vertex(m, v0, NV, fi[k]);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const float d = p[a] - fr[a];
-            const float s = 256.f * (float)((double)d / (double)cell);
+            const float s = 256.f * mb_div(d, cell);
             const bool in = fabsf(s) <= VX_SNAP_MAX;                    // false for NaN
             ok = ok && in;
             G[k][a] = in ? (int)rintf(s) : 0;
@@ -152,15 +137,13 @@ __device__ __forceinline__ bool vx_hit(const VxFace& f, int i, int j, int k) {
 }
 
 // the two packed addends of face gf: 1 | red << 32 and green | blue << 32
-__device__ __forceinline__ void vx_colour(const int* __restrict__ face_mat, const float* __restrict__ mat_kd, const long* __restrict__ mat_off,
-                                          int n, long gf, u64& A, u64& B) {
-    const long m0 = mat_off[n], M = mat_off[n + 1] - m0;
-    const long m = min((long)(unsigned)face_mat[gf], M - 1);
+__device__ __forceinline__ void vx_colour(const MeshBatch& m, int n, long gf, u64& A, u64& B) {
+    float kd[3];
+    mb_face_kd(m, n, gf, kd);
     u64 q[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float kd = M > 0 ? mat_kd[(size_t)(m0 + m) * 3 + k] : 0.4f;
-        const float col = fminf(fmaxf(kd, 0.f), 1.f);
+        const float col = fminf(fmaxf(kd[k], 0.f), 1.f);
         q[k] = (u64)(int)floorf(255.f * col + 0.5f);
     }
     A = 1ULL | (q[0] << 32);
@@ -173,37 +156,23 @@ __global__ __launch_bounds__(VX_THREADS) void voxelize_clear_kernel(u64* __restr
 }
 
 // one lane per face of the whole batch
-__global__ __launch_bounds__(VX_THREADS) void voxelize_faces_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                    const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                    const int* __restrict__ face_mat, const float* __restrict__ mat_kd,
-                                                                    const long* __restrict__ mat_off, const float* __restrict__ frame, int N,
-                                                                    long sumF, int V, u64* __restrict__ acc, u64* __restrict__ qcount,
+__global__ __launch_bounds__(VX_THREADS) void voxelize_faces_kernel(MeshBatch m, const float* __restrict__ frame, long sumF, int V,
+                                                                    u64* __restrict__ acc, u64* __restrict__ qcount,
                                                                     unsigned* __restrict__ queue, u64 qcap) {
     const long gf = (long)blockIdx.x * VX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     VxFace f;
     bool live = false, big = false;
     int n = 0;
     if (gf < sumF) {
-        n = vx_mesh_of(face_off, N, gf);
-        live = vx_setup(verts, faces, vert_off, frame, gf, n, V, f);
+        n = mb_mesh_of(m, gf);
+        live = vx_setup(m, frame, gf, n, V, f);
         big = live && (long)(f.b1[0] - f.b0[0] + 1) * (f.b1[1] - f.b0[1] + 1) * (f.b1[2] - f.b0[2] + 1) > VX_SMALL_COUNT;
     }
-    // queue append: every lane of the wave is here; one atomic add per wave, the slots in lane order
-    const u64 mask = __ballot(big);
-    if (mask) {
-        const int leader = __ffsll((long long)mask) - 1;
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd(qcount, (u64)__popcll(mask));
-        base = __shfl(base, leader);
-        if (big) {
-            const u64 slot = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
-            if (slot < qcap) queue[slot] = (unsigned)gf;
-        }
-    }
+    const u64 slot = mb_queue_slot(big, qcount);                        // every lane of the wave is here
+    if (big && slot < qcap) queue[slot] = (unsigned)gf;
     if (!live || big) return;
     u64 A, B;
-    vx_colour(face_mat, mat_kd, mat_off, n, gf, A, B);
+    vx_colour(m, n, gf, A, B);
     for (int i = f.b0[0]; i <= f.b1[0]; ++i)
         for (int j = f.b0[1]; j <= f.b1[1]; ++j)
             for (int k = f.b0[2]; k <= f.b1[2]; ++k)
@@ -215,20 +184,17 @@ __global__ __launch_bounds__(VX_THREADS) void voxelize_faces_kernel(const float*
 }
 
 // fixed grid; workgroup b takes queue entries b, b + gridDim.x, ... up to the count the first kernel left on the device
-__global__ __launch_bounds__(VX_THREADS) void voxelize_queue_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                    const long* __restrict__ vert_off, const long* __restrict__ face_off,
-                                                                    const int* __restrict__ face_mat, const float* __restrict__ mat_kd,
-                                                                    const long* __restrict__ mat_off, const float* __restrict__ frame, int N,
-                                                                    int V, u64* __restrict__ acc, const u64* __restrict__ qcount,
-                                                                    const unsigned* __restrict__ queue, u64 qcap) {
+__global__ __launch_bounds__(VX_THREADS) void voxelize_queue_kernel(MeshBatch m, const float* __restrict__ frame, int V, u64* __restrict__ acc,
+                                                                    const u64* __restrict__ qcount, const unsigned* __restrict__ queue,
+                                                                    u64 qcap) {
     const u64 count = min(*qcount, qcap);
     for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
         const long gf = queue[q];
-        const int n = vx_mesh_of(face_off, N, gf);
+        const int n = mb_mesh_of(m, gf);
         VxFace f;
-        if (!vx_setup(verts, faces, vert_off, frame, gf, n, V, f)) continue;                 // the same answer in every lane
+        if (!vx_setup(m, frame, gf, n, V, f)) continue;                                    // the same answer in every lane
         u64 A, B;
-        vx_colour(face_mat, mat_kd, mat_off, n, gf, A, B);
+        vx_colour(m, n, gf, A, B);
         const int bj = f.b1[1] - f.b0[1] + 1, bk = f.b1[2] - f.b0[2] + 1, bjk = bj * bk;
         const int cnt = (f.b1[0] - f.b0[0] + 1) * bjk;                                     // at most 128^3
         for (int t = threadIdx.x; t < cnt; t += VX_THREADS) {
@@ -357,12 +323,12 @@ extern "C" int tri_voxelize_meshes(const float* verts, const int* faces, const l
     unsigned* queue = (unsigned*)(qcount + 2);
     const long nwords = 2 * nvox + 3 * (nvox / 64);
     const unsigned vblocks = (unsigned)((nvox + VX_THREADS - 1) / VX_THREADS);
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
     voxelize_clear_kernel<<<(unsigned)min((long)VX_CLEAR_BLOCKS, (nwords + VX_THREADS - 1) / VX_THREADS), VX_THREADS, 0, st>>>(acc, nwords, qcount);
     if (sumF > 0) {
-        voxelize_faces_kernel<<<(unsigned)((sumF + VX_THREADS - 1) / VX_THREADS), VX_THREADS, 0, st>>>(
-            verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame, N, sumF, V, acc, qcount, queue, (u64)sumF);
-        voxelize_queue_kernel<<<VX_QUEUE_BLOCKS, VX_THREADS, 0, st>>>(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame, N, V,
-                                                                      acc, qcount, queue, (u64)sumF);
+        voxelize_faces_kernel<<<(unsigned)((sumF + VX_THREADS - 1) / VX_THREADS), VX_THREADS, 0, st>>>(m, frame, sumF, V, acc, qcount, queue,
+                                                                                                       (u64)sumF);
+        voxelize_queue_kernel<<<VX_QUEUE_BLOCKS, VX_THREADS, 0, st>>>(m, frame, V, acc, qcount, queue, (u64)sumF);
         if (fill) voxelize_rows_kernel<<<vblocks, VX_THREADS, 0, st>>>(acc, nvox, V, bx, by, bz);
     }
     voxelize_resolve_kernel<<<vblocks, VX_THREADS, 0, st>>>(acc, nvox, V, fill, bx, by, bz, grid, labels);

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import torch
 
-from ..evaluation.mesh import load_obj
+from ..meshes import load_obj
 
 DEFAULT_KD = (0.4, 0.4, 0.4)
 
@@ -32,7 +32,7 @@ def load_mtl(path):
 
 def load_obj_materials(path):
     """-> (verts float32 [V, 3], faces int64 [F, 3], face_material int32 [F], Kd float32 [M, 3], names): verts and faces are
-    evaluation.mesh.load_obj's; a k-gon under a `usemtl` yields k - 2 faces of that material.  Material 0 is a default grey
+    meshes.load_obj's; a k-gon under a `usemtl` yields k - 2 faces of that material.  Material 0 is a default grey
     (0.4, 0.4, 0.4) named None: it covers faces before any usemtl, names no mtllib file defines, and missing MTL files.  The other
     materials follow in the order the mtllib files define them.  CRLF is tolerated."""
     verts, faces = load_obj(path)

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from .. import config as tcfg
+from ..meshes import MeshBatch
 from . import render, voxelize
 from .materials import load_obj_materials
 from .nrrd import read_nrrd
@@ -95,12 +96,6 @@ def nrrd_path(data_root, mid, v):
     return os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd")
 
 
-def voxelize_batch(meshes, device):
-    """{"voxel32" | "voxel64" | "voxel128": uint8 [len(meshes), 4, V, V, V]}: one ops.voxelize_meshes call per size."""
-    return {f"voxel{v}": voxelize.voxelize_meshes([m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes], [m[3] for m in meshes],
-                                                  v, fill="carve", device=device).cpu().numpy() for v in VOXEL_SIZES}
-
-
 def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd"):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
     come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist)."""
@@ -108,11 +103,13 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
     for i in range(0, len(todo), batch_meshes):
         batch = todo[i:i + batch_meshes]
         meshes = [load_obj_materials(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
-        images = render.render_meshes([m[0] for m in meshes], [m[1] for m in meshes], [m[2] for m in meshes], [m[3] for m in meshes],
-                                      num_views=num_views, image_size=render.IMAGE_SIZE, device=device).cpu().numpy()
+        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device)
+        images = render.render_batch(packed, num_views, render.IMAGE_SIZE).cpu().numpy()
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
-        made = voxelize_batch([meshes[k] for k in from_mesh], device) if from_mesh else {}
+        if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
+            packed = MeshBatch.pack(*zip(*(meshes[k][:4] for k in from_mesh)), device=device)
+        made = {f"voxel{v}": voxelize.voxelize_batch(packed, v, fill="carve").cpu().numpy() for v in VOXEL_SIZES} if from_mesh else {}
         for k, ((cat, mid), views) in enumerate(zip(batch, images)):
             if k in from_mesh:
                 grids = {name: g[from_mesh.index(k)] for name, g in made.items()}

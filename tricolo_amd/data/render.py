@@ -27,6 +27,8 @@ import math
 import numpy as np
 import torch
 
+from ..meshes import MeshBatch, clamp_index, cross, face_kd, host_boxes, pack_materials  # noqa: F401  (pack_materials: offered from here too)
+
 YFOV, ZNEAR, IMAGE_SIZE = math.pi / 3, 0.05, 224
 DISTANCE, ELEVATION = 0.85, math.pi / 5
 SNAP_MAX = float(2 ** 20)
@@ -52,10 +54,14 @@ def camera_poses(center, num_views, distance=DISTANCE, elevation=ELEVATION):
     return np.stack(eyes) if eyes else np.zeros((0, 3)), np.stack(rots) if rots else np.zeros((0, 3, 3))
 
 
+def box_centers(boxes):
+    """float64 [..., 3] from meshes.host_boxes' [..., 3, 2]."""
+    return 0.5 * (boxes[..., 0] + boxes[..., 1])
+
+
 def bbox_center(verts):
     """The centre of the bounding box of all vertices, float64 (zeros for a mesh without vertices)."""
-    v = verts.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(verts) else np.asarray(verts, dtype=np.float64)
-    return 0.5 * (v.min(0) + v.max(0)) if v.shape[0] else np.zeros(3)
+    return box_centers(host_boxes([verts])[0])
 
 
 def pack_cameras(centers, num_views, device=None):
@@ -166,11 +172,8 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis):
     if pix.numel() == 0:
         return out
     f = vis[pix]
-    a, b, c = verts[faces[f, 0]], verts[faces[f, 1]], verts[faces[f, 2]]
-    u, w = b - a, c - a
-    cx = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1]
-    cy = u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2]
-    cz = u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+    a = verts[faces[f, 0]]
+    cx, cy, cz = cross(a, verts[faces[f, 1]], verts[faces[f, 2]])
     length = torch.sqrt((cx * cx + cy * cy) + cz * cz)
     e = cam[:3] - a
     side = (cx * e[:, 0] + cy * e[:, 1]) + cz * e[:, 2]
@@ -178,13 +181,7 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis):
     ny = cy / torch.where(ok, length, torch.ones_like(length))
     ndl = torch.where(ok, torch.where(side < 0, -ny, ny).clamp(min=0.0), torch.zeros_like(ny))
     shade = 0.1 + _f32(KDIFF) * ndl
-    M = kd.shape[0]
-    if M > 0:
-        m = face_mat[f].to(torch.int64)
-        col = kd[torch.where(m < 0, torch.full_like(m, M - 1), m.clamp(max=M - 1))]
-    else:
-        col = torch.full((f.numel(), 3), 0.4, dtype=torch.float32)
-    rgb = torch.floor(255.0 * (col * shade[:, None]).clamp(0.0, 1.0) + 0.5).to(torch.uint8)
+    rgb = torch.floor(255.0 * (face_kd(face_mat[f], kd) * shade[:, None]).clamp(0.0, 1.0) + 0.5).to(torch.uint8)
     out[:, pix] = rgb.t()
     return out
 
@@ -198,10 +195,10 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
     vis = torch.full((N, views, H, W), -1, dtype=torch.int32)
     for n in range(N):
         v = verts[voff[n]:voff[n + 1]]
-        f = faces[foff[n]:foff[n + 1]].to(torch.int64)
+        f = faces[foff[n]:foff[n + 1]]
         if v.shape[0] == 0 or f.shape[0] == 0 or H * W == 0:
             continue
-        f = torch.where(f < 0, torch.full_like(f, v.shape[0] - 1), f.clamp(max=v.shape[0] - 1))     # the kernel's unsigned clamp
+        f = clamp_index(f, v.shape[0])
         fm, kd = face_mat[foff[n]:foff[n + 1]], mat_kd[moff[n]:moff[n + 1]]
         for k in range(views):
             keys = _visibility_one(v, f, cam[n, k], H, W, yfov, znear)
@@ -211,31 +208,17 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
     return (image, vis) if return_visibility else image
 
 
-# ------------------------------------------------------------------------------------------------ the convenient call
-def pack_materials(face_mat_list, kd_list, device=None):
-    """-> (face_mat int32 [sumF], mat_kd fp32 [sumM, 3], mat_off int64 [N + 1]); validated on the host."""
-    moff = [0]
-    for n, (fm, kd) in enumerate(zip(face_mat_list, kd_list)):
-        if kd.dim() != 2 or kd.shape[1] != 3 or kd.shape[0] < 1 or kd.dtype != torch.float32:
-            raise ValueError(f"mesh {n}: Kd must be a float32 tensor of shape [M >= 1, 3]")
-        if fm.numel() and (int(fm.min()) < 0 or int(fm.max()) >= kd.shape[0]):
-            raise ValueError(f"mesh {n}: material indices span {int(fm.min())} .. {int(fm.max())} but the mesh has {kd.shape[0]} materials")
-        moff.append(moff[-1] + kd.shape[0])
-    device = device or "cpu"
-    return (torch.cat([fm.to(device=device, dtype=torch.int32).reshape(-1) for fm in face_mat_list]).contiguous(),
-            torch.cat([kd.to(device) for kd in kd_list]).contiguous(), torch.tensor(moff, dtype=torch.int64, device=device))
+# ------------------------------------------------------------------------------------------------ the convenient calls
+def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False):
+    """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
+    [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
+    ops.render_views."""
+    from .. import ops
+    cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
+    H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
+    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility)
 
 
 def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False):
-    """The reference's num_views renderings of every mesh -> uint8 [N, num_views, 3, S, S] on `device` (where verts_list[0] lives
-    when None): packs the batch (evaluation.mesh.pack_meshes), places the cameras around every mesh's bounding-box centre and calls
-    ops.render_views."""
-    from .. import ops
-    from ..evaluation.mesh import pack_meshes
-    verts, faces, voff, foff, _ = pack_meshes(verts_list, faces_list, device)
-    if len(face_mat_list) != len(faces_list) or any(fm.shape[0] != f.shape[0] for fm, f in zip(face_mat_list, faces_list)):
-        raise ValueError("every mesh needs one material index per face")
-    fm, kd, moff = pack_materials(face_mat_list, kd_list, verts.device)
-    cam = pack_cameras([bbox_center(v) for v in verts_list], num_views, verts.device)
-    H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
-    return ops.render_views(verts, faces, voff, foff, fm, kd, moff, cam, H, W, YFOV, ZNEAR, return_visibility)
+    """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None)."""
+    return render_batch(MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device), num_views, image_size, return_visibility)

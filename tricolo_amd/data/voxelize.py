@@ -20,26 +20,30 @@ import math
 import numpy as np
 import torch
 
+from ..meshes import MeshBatch, clamp_index, face_kd, host_boxes
+
 SNAP_MAX = float(2 ** 17)
 CANDIDATES_PER_PASS = 1 << 19                       # (face, voxel) pairs the fallback expands at a time
 
 
 # ------------------------------------------------------------------------------------------------ frames
-def default_frames(verts_list, V):
-    """-> float32 [N, 4] = (origin x, y, z, cell size) per mesh, formed in float64 from the bounding box of all vertices: the grid
+def box_frames(boxes, V):
+    """meshes.host_boxes' float64 [N, 3, 2] -> float32 [N, 4] = (origin x, y, z, cell size) per mesh, formed in float64: the grid
     cube is centred on the box centre, its edge L is the box's longest side (no margin), cell = fl32(L / V) and origin = centre -
-    V cell / 2.  A mesh without vertices or of zero extent gets cell = 0 (an all-zero grid)."""
-    out = np.zeros((len(verts_list), 4), np.float64)
-    for n, verts in enumerate(verts_list):
-        v = verts.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(verts) else np.asarray(verts, dtype=np.float64)
-        if v.shape[0] == 0:
-            continue
-        lo, hi = v.min(0), v.max(0)
+    V cell / 2.  A mesh without vertices (a zero box) or of zero extent gets cell = 0 (an all-zero grid)."""
+    out = np.zeros((len(boxes), 4), np.float64)
+    for n, box in enumerate(boxes):
+        lo, hi = box[:, 0], box[:, 1]
         cell = float(np.float32((hi - lo).max() / V))
         centre = 0.5 * (lo + hi)
         out[n, :3] = centre - V * cell / 2.0 if cell > 0.0 else centre
         out[n, 3] = cell
     return torch.from_numpy(out.astype(np.float32))
+
+
+def default_frames(verts_list, V):
+    """box_frames of the bounding boxes of all vertices of every mesh."""
+    return box_frames(host_boxes(verts_list), V)
 
 
 # ------------------------------------------------------------------------------------------------ the torch fallback
@@ -55,12 +59,7 @@ def snap_vertices(verts, frame):
 
 def material_bytes(face_mat, kd):
     """q int64 [F, 3]: floor(255 clamp(Kd, 0, 1) + 0.5) of every face's material in fp32 (grey 0.4 without materials)."""
-    M = kd.shape[0]
-    if M > 0:
-        m = face_mat.to(torch.int64)
-        col = kd[torch.where(m < 0, torch.full_like(m, M - 1), m.clamp(max=M - 1))]
-    else:
-        col = torch.full((face_mat.shape[0], 3), 0.4, dtype=torch.float32)
+    col = face_kd(face_mat, kd)
     col = torch.where(col > 0, col, torch.zeros_like(col)).clamp(max=1.0)             # fminf(fmaxf(kd, 0), 1): NaN -> 0
     return torch.floor(255.0 * col + 0.5).to(torch.int64)
 
@@ -165,21 +164,19 @@ def voxelize_meshes_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_
     labels = torch.zeros((N, V, V, V), dtype=torch.uint8)
     for n in range(N):
         v = verts[voff[n]:voff[n + 1]]
-        f = faces[foff[n]:foff[n + 1]].to(torch.int64)
+        f = faces[foff[n]:foff[n + 1]]
         if v.shape[0] == 0 or f.shape[0] == 0:
             continue
-        f = torch.where(f < 0, torch.full_like(f, v.shape[0] - 1), f.clamp(max=v.shape[0] - 1))         # the kernel's unsigned clamp
-        grid[n], labels[n] = _voxelize_one(v, f, face_mat[foff[n]:foff[n + 1]], mat_kd[moff[n]:moff[n + 1]], frame[n], V, fill)
+        grid[n], labels[n] = _voxelize_one(v, clamp_index(f, v.shape[0]), face_mat[foff[n]:foff[n + 1]], mat_kd[moff[n]:moff[n + 1]], frame[n], V, fill)
     return (grid, labels) if return_labels else grid
 
 
-# ------------------------------------------------------------------------------------------------ the convenient call
-def voxelize_meshes(verts_list, faces_list, face_mat_list, kd_list, voxel_size, fill="carve", device=None, return_labels=False):
-    """Coloured voxel grids of every mesh -> uint8 [N, 4, V, V, V] on `device` (where verts_list[0] lives when None), indexed
-    [channel, x, y, z] as data.nrrd.read_nrrd returns the downloaded grids; with return_labels also uint8 [N, V, V, V] (0 exterior,
-    1 surface, 2 interior).  Packs the batch (evaluation.mesh.pack_meshes, data.render.pack_materials), frames every mesh by
-    default_frames - the grid cube spans the longest side of the bounding box, centred, without margin - and calls
-    ops.voxelize_meshes.
+# ------------------------------------------------------------------------------------------------ the convenient calls
+def voxelize_batch(batch, voxel_size, fill="carve", return_labels=False):
+    """Coloured voxel grids of every mesh of a meshes.MeshBatch packed with materials -> uint8 [N, 4, V, V, V] on the batch's device,
+    indexed [channel, x, y, z] as data.nrrd.read_nrrd returns the downloaded grids; with return_labels also uint8 [N, V, V, V]
+    (0 exterior, 1 surface, 2 interior).  Frames every mesh by box_frames - the grid cube spans the longest side of the bounding
+    box, centred, without margin - and calls ops.voxelize_meshes.
 
     What is defined (head of csrc/voxelize.hip): a voxel is on the surface when its closed box overlaps a face whose vertices were
     snapped to 1/256 voxel - touching counts, so a face in a boundary plane sets both layers; alpha is 255 there.  fill="carve"
@@ -190,12 +187,10 @@ def voxelize_meshes(verts_list, faces_list, face_mat_list, kd_list, voxel_size, 
     little of it lies in the voxel.  Textures (map_Kd) are ignored: a textured material contributes its Kd.  No grid has been
     compared with Text2Shape's (occupancy, axis orientation, interior colours)."""
     from .. import ops
-    from ..evaluation.mesh import pack_meshes
-    from .render import pack_materials
     V = int(voxel_size)
-    verts, faces, voff, foff, _ = pack_meshes(verts_list, faces_list, device)
-    if len(face_mat_list) != len(faces_list) or any(fm.shape[0] != f.shape[0] for fm, f in zip(face_mat_list, faces_list)):
-        raise ValueError("every mesh needs one material index per face")
-    fm, kd, moff = pack_materials(face_mat_list, kd_list, verts.device)
-    frame = default_frames(verts_list, V).to(verts.device)
-    return ops.voxelize_meshes(verts, faces, voff, foff, fm, kd, moff, frame, V, fill, return_labels)
+    return ops.voxelize_meshes(*batch.tensors, box_frames(batch.boxes, V).to(batch.verts.device), V, fill, return_labels)
+
+
+def voxelize_meshes(verts_list, faces_list, face_mat_list, kd_list, voxel_size, fill="carve", device=None, return_labels=False):
+    """voxelize_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None)."""
+    return voxelize_batch(MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device), voxel_size, fill, return_labels)

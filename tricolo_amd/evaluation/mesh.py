@@ -17,11 +17,9 @@ Here a cached cloud always carries its OWN gt-10 factor (longest bounding-box ed
 reference writes for every shape that occurs as a ground truth.  compare_meshes keeps the reference's exact pair semantics
 (prediction scaled by the ground truth's factor) for whoever wants them.
 """
-import re
-
-import numpy as np
 import torch
 
+from ..meshes import cross, load_obj, pack_meshes  # noqa: F401  (load_obj: part of what this module offers the shape-F1 command)
 from . import shape_f1 as _sf
 
 _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -29,78 +27,7 @@ _M32 = 0xFFFFFFFF
 SCAN_CHUNK = 2048                  # faces per chunk of the GPU scan (csrc/mesh_sample.hip MS_CHUNK): fixed, part of the CDF's bits
 
 
-# ------------------------------------------------------------------------------------------------ OBJ
-def load_obj(path):
-    """-> (verts float32 [V, 3], faces int64 [F, 3]), what pytorch3d's load_obj(path, load_textures=False) gives calculate_f1.py as
-    verts and faces.verts_idx.  `v x y z` lines (further values - vertex colours - ignored); `f` lines with tokens i, i/j, i/j/k, i//k:
-    1-based, negative = counted back from the vertices read so far, polygons split as a fan (0, k, k + 1).  Every other line is
-    ignored; CRLF is tolerated.  An index outside the file's vertices raises ValueError naming the line."""
-    with open(path, "rb") as f:
-        lines = [ln.strip() for ln in f.read().replace(b"\r", b"").split(b"\n")]
-    head = [ln[:2] for ln in lines]
-    is_v = np.fromiter((h == b"v " or h == b"v\t" for h in head), dtype=bool, count=len(lines))
-    is_f = np.fromiter((h == b"f " or h == b"f\t" for h in head), dtype=bool, count=len(lines))
-    v_lines, f_lines = np.flatnonzero(is_v), np.flatnonzero(is_f)
-    vtoks = [lines[i].split()[1:4] for i in v_lines]
-    for i, t in zip(v_lines, vtoks):
-        if len(t) != 3:
-            raise ValueError(f"{path}: line {i + 1}: a vertex needs three coordinates")
-    verts = np.array(vtoks, dtype="S").astype(np.float64).astype(np.float32).reshape(-1, 3)
-    V = verts.shape[0]
-    if f_lines.size == 0:
-        return torch.from_numpy(verts), torch.zeros((0, 3), dtype=torch.int64)
-    ftoks = [lines[i].split()[1:] for i in f_lines]
-    counts = np.fromiter((len(t) for t in ftoks), dtype=np.int64, count=len(ftoks))
-    if (counts < 3).any():
-        raise ValueError(f"{path}: line {f_lines[np.argmax(counts < 3)] + 1}: a face needs at least three vertices")
-    body = re.sub(rb"/\S*", b"", b" ".join(b" ".join(t) for t in ftoks))            # i/j/k -> i
-    raw = np.array(body.split(), dtype="S").astype(np.int64)
-    tok_line = np.repeat(np.arange(len(ftoks)), counts)
-    seen = np.cumsum(is_v)[f_lines][tok_line]                                       # vertices read before the token's line
-    idx = np.where(raw > 0, raw - 1, np.where(raw < 0, seen + raw, -1))
-    bad = (idx < 0) | (idx >= V)
-    if bad.any():
-        k = int(np.argmax(bad))
-        raise ValueError(f"{path}: line {f_lines[tok_line[k]] + 1}: face index {raw[k]} is outside the file's {V} vertices")
-    start = np.cumsum(counts) - counts                                               # the fan: (0, k, k + 1) for k = 1 .. count - 2
-    ntri = counts - 2
-    tri_start = np.repeat(start, ntri)
-    k = np.arange(int(ntri.sum())) - np.repeat(np.cumsum(ntri) - ntri, ntri) + 1
-    faces = np.stack([idx[tri_start], idx[tri_start + k], idx[tri_start + k + 1]], axis=1)
-    return torch.from_numpy(verts), torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int64))
-
-
-# ------------------------------------------------------------------------------------------------ packing and validation
-def pack_meshes(verts_list, faces_list, device=None):
-    """Validate (dtypes, shapes, index ranges - on the host, from the min / max of the faces, before anything is launched) and pack:
-    -> (verts fp32 [sumV, 3], faces int32 [sumF, 3] local indices, vert_off int64 [N + 1], face_off int64 [N + 1], max_faces)."""
-    if len(verts_list) != len(faces_list):
-        raise ValueError(f"{len(verts_list)} vertex arrays but {len(faces_list)} face arrays")
-    if not verts_list:
-        raise ValueError("an empty batch of meshes")
-    if device is None:
-        device = verts_list[0].device
-    device = torch.device(device)
-    voff, foff = [0], [0]
-    for n, (v, f) in enumerate(zip(verts_list, faces_list)):
-        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
-            raise ValueError(f"mesh {n}: verts must be a float32 tensor of shape [V, 3]")
-        if not torch.is_tensor(f) or f.dtype not in (torch.int64, torch.int32) or f.dim() != 2 or f.shape[1] != 3:
-            raise ValueError(f"mesh {n}: faces must be an int64 (or int32) tensor of shape [F, 3]")
-        if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
-            raise ValueError(f"mesh {n}: 2^31 or more vertices or faces")
-        if f.shape[0]:
-            lo, hi = int(f.min()), int(f.max())
-            if lo < 0 or hi >= v.shape[0]:
-                raise ValueError(f"mesh {n}: face indices span {lo} .. {hi} but the mesh has {v.shape[0]} vertices")
-        voff.append(voff[-1] + v.shape[0])
-        foff.append(foff[-1] + f.shape[0])
-    verts = torch.cat([v.to(device) for v in verts_list]).contiguous()
-    faces = torch.cat([f.to(device=device, dtype=torch.int32) for f in faces_list]).contiguous()
-    return (verts, faces, torch.tensor(voff, dtype=torch.int64, device=device), torch.tensor(foff, dtype=torch.int64, device=device),
-            max(b - a for a, b in zip(foff, foff[1:])))
-
-
+# ------------------------------------------------------------------------------------------------ bounding boxes and scale
 def _bbox(verts, vert_off):
     if verts.is_cuda:
         from .. import ops
@@ -183,12 +110,8 @@ def _scaled(verts, s):
 
 
 def face_areas(verts, faces):
-    """0.5 * |(b - a) x (c - a)| in fp32, every operation rounded on its own (the order of csrc/mesh_sample.hip)."""
-    a, b, c = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
-    u, v = b - a, c - a
-    cx = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
-    cy = u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2]
-    cz = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+    """0.5 * |(b - a) x (c - a)| in fp32, every operation rounded on its own (the order of csrc/mesh_batch.h)."""
+    cx, cy, cz = cross(verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]])
     return 0.5 * torch.sqrt((cx * cx + cy * cy) + cz * cz)
 
 

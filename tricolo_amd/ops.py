@@ -1580,10 +1580,15 @@ def _mesh_arg(x, name, dtype, shape_tail=None, numel=None):
     return x
 
 
-def _mesh_batch(verts, faces, vert_off, face_off, scale):
-    """The packed batch of csrc/mesh_sample.hip: verts fp32 [sumV, 3], faces int32 [sumF, 3] (local indices), offsets int64 [N + 1]."""
-    for x in (verts, faces, vert_off, face_off, scale):
-        ptr(x)                                                                   # host tensors: "no CPU fallback"
+def _mesh_batch(verts, faces, vert_off, face_off, scale=None, face_mat=None, mat_kd=None, mat_off=None, also=None, stage=None):
+    """Checks the packed batch of csrc/mesh_batch.h (meshes.MeshBatch) -> N.  stage: "render_views" or "voxelize_meshes", the calls that
+    need the material tensors and take CPU tensors (for their torch restatements), all on the device of `also`, their camera or frame
+    tensor; None for the sampler's calls, which have neither: a host tensor raises "no CPU fallback"."""
+    if stage is None:
+        for x in (verts, faces, vert_off, face_off, scale):
+            ptr(x)
+    elif len({x.device for x in (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, also)}) != 1:
+        raise ValueError(f"{stage}: all tensors must live on one device")
     _mesh_arg(verts, "verts", torch.float32, 3)
     if faces is not None:
         _mesh_arg(faces, "faces", torch.int32, 3)
@@ -1595,12 +1600,16 @@ def _mesh_batch(verts, faces, vert_off, face_off, scale):
         _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
     if scale is not None:
         _mesh_arg(scale, "scale", torch.float32, numel=N)
+    if stage is not None:
+        _mesh_arg(mat_off, "mat_off", torch.int64, numel=N + 1)
+        _mesh_arg(face_mat, "face_mat", torch.int32, numel=faces.shape[0])
+        _mesh_arg(mat_kd, "mat_kd", torch.float32, 3)
     return N
 
 
 def mesh_bbox(verts, vert_off):
     """verts fp32 [sumV, 3], vert_off int64 [N + 1] on the GPU -> bbox fp32 [N, 3, 2]: per-axis (min, max) over all vertices of a mesh."""
-    N = _mesh_batch(verts, None, vert_off, None, None)
+    N = _mesh_batch(verts, None, vert_off, None)
     bbox = torch.empty((N, 3, 2), dtype=torch.float32, device=verts.device)
     check(lib().tri_mesh_bbox(ptr(verts), ptr(vert_off), N, ptr(bbox), stream()), "tri_mesh_bbox")
     return bbox
@@ -1642,7 +1651,7 @@ RENDER_MAX_PIXELS = 2 ** 31                                                     
 
 def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=math.pi / 3, znear=0.05,
                  return_visibility=False):
-    """Render every mesh of a packed batch (evaluation.mesh.pack_meshes) from every camera -> images uint8 [N, views, 3, H, W], with
+    """Render every mesh of a packed batch (meshes.MeshBatch.pack) from every camera -> images uint8 [N, views, 3, H, W], with
     return_visibility also int32 [N, views, H, W]: the face seen at each pixel centre, local to its mesh, -1 for background.
     face_mat int32 [sumF]: a material per face, local to the mesh; mat_kd fp32 [sumM, 3] diffuse colours with mat_off int64 [N + 1];
     cam fp32 [N, views, 12]: eye, then the world-to-camera rotation row by row (data.render.pack_cameras).  The arithmetic is the
@@ -1652,17 +1661,7 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     (8 bytes of visibility key each); more raises before anything runs.  CPU tensors run data.render.render_views_cpu, the same
     arithmetic in torch (untuned, for checking)."""
     H, W = int(H), int(W)
-    tensors = (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("render_views: all tensors must live on one device")
-    N = vert_off.numel() - 1
-    _mesh_arg(verts, "verts", torch.float32, 3)
-    _mesh_arg(faces, "faces", torch.int32, 3)
-    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
-    _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
-    _mesh_arg(mat_off, "mat_off", torch.int64, numel=N + 1)
-    _mesh_arg(face_mat, "face_mat", torch.int32, numel=faces.shape[0])
-    _mesh_arg(mat_kd, "mat_kd", torch.float32, 3)
+    N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views")
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
     views, sumF = cam.shape[1], faces.shape[0]
@@ -1704,17 +1703,7 @@ def voxelize_meshes(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off,
     V = int(V)
     if fill not in VOXELIZE_FILL:
         raise ValueError(f"voxelize_meshes: fill must be one of {sorted(VOXELIZE_FILL)}, got {fill!r}")
-    tensors = (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, frame)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("voxelize_meshes: all tensors must live on one device")
-    N = vert_off.numel() - 1
-    _mesh_arg(verts, "verts", torch.float32, 3)
-    _mesh_arg(faces, "faces", torch.int32, 3)
-    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
-    _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
-    _mesh_arg(mat_off, "mat_off", torch.int64, numel=N + 1)
-    _mesh_arg(face_mat, "face_mat", torch.int32, numel=faces.shape[0])
-    _mesh_arg(mat_kd, "mat_kd", torch.float32, 3)
+    N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, frame, stage="voxelize_meshes")
     if frame.dtype != torch.float32 or frame.shape != (N, 4) or not frame.is_contiguous():
         raise ValueError(f"frame must be a contiguous float32 tensor of shape [{N}, 4], got {tuple(frame.shape)} {frame.dtype}")
     sumF = faces.shape[0]
