@@ -44,7 +44,7 @@ typedef struct TriConvDesc {
  * Layouts: spconv SubMConv3d weight [Cout,kd,kh,kw,Cin] (sparse_cnn.py:12-32), torchvision conv [Cout,Cin,kh,kw]
  * (mv_cnn.py:44), nn.Linear [out,in].
  * frag != 0 (rows % 16 == 0): the same elements in MFMA-FRAGMENT-MAJOR order for the kernels that load their weight fragments straight
- * into registers (tri_conv_kernel_family == 13 / 14 / 15): the [16 rows x 32 k] block (row tile rt, k-step ks) is 1 KiB at
+ * into registers (TRI_CONV_VOXG / VOXB / S2G): the [16 rows x 32 k] block (row tile rt, k-step ks) is 1 KiB at
  * ((rt * kpad / 32) + ks) * 512 elements, element (r, k) of it at ((k % 32) / 8 * 16 + r % 16) * 8 + k % 8 - lane (r, k / 8) of a
  * 16x16x32 A fragment reads its 8 elements as ONE contiguous 16-byte piece and a wave reads 1 KiB contiguously. */
 int tri_conv_kpad(int ntaps, int cin_stored);
@@ -100,17 +100,29 @@ int tri_conv_num_mtiles(const TriConvDesc* d, int split3);
 /* the same for a call that passes a compact row list (row_list = 1: row_pos + row_count): such launches are planned for the voxel
  * grids' occupancy (<= 25 %), so a small level may run split-K over its list where the dense call would not */
 int tri_conv_num_records(const TriConvDesc* d, int split3, int row_list);
-/* kernel family tri_conv_fwd (transposed = 0) / tri_conv_dgrad (transposed = 1) dispatches for this layer and mode:
- * 0 conv_igemm_kernel (register-staged im2col), 2 conv_dma_kernel (LDS-DMA staging); bits 8.. hold the output-channel
- * tile width; bit 16 set = the dense call of the layer runs split-K in this mode; 4 conv_stem_kernel, 3 / 5 the halo kernels,
- * 6 = the brick kernel of conv_vox.hip (voxel level 0; takes the site mask as row_mask, refuses a row list), 9 / 10 = the
- * register-stationary filter-bank kernels of conv_c64.hip (9 conv_c64_kernel: 64 -> 64 channels 3x3 / 1, both directions; 10 conv_s2d_kernel:
- * data gradient of the 64 -> 128 channel 3x3 / 2 layer), 12 conv_pw_kernel (1x1 / 2 shortcuts; 7 and 11 were A/B partners dropped in round 6),
- * 13 conv_voxg_kernel (conv_voxg.hip: SubMConv3d on 2^3 / 4^3 / 8^3 grids, both directions; takes the site mask as row_mask, refuses a
- * row list; bits 8..15 = output channels per workgroup, bits 24.. = samples per unit = per BatchNorm record), 14 conv_voxb_kernel (voxel
- * level 1 on 16^3 / 32^3 grids, forward only; site mask as row_mask), 15 conv_s2g_kernel (conv_s2g.hip: forward of the 3x3 / 2 layers with >= 128 input
- * channels - layer3 / layer4's opening convolutions; refuses row mask / list, bias, activation, accumulate; one BatchNorm record per unit of images).
- * Families 13 / 14 / 15 read FRAGMENT-MAJOR packed operands.  For profilers. */
+/* Kernel families of tri_conv_fwd / tri_conv_dgrad.  What each one serves, which calls it refuses or hands to the generic kernel, its
+ * BatchNorm record count and its packed-operand order are one table: conv_families[] in csrc/conv_igemm.hip (Python: ops.CONV_FAMILIES). */
+typedef enum TriConvFamily {
+    TRI_CONV_IGEMM = 0,      /* conv_igemm_kernel: register-staged im2col, every layer and mode */
+    TRI_CONV_DMA = 2,        /* conv_dma_kernel: LDS-DMA staging (16-bit storage, 64 | Cin) */
+    TRI_CONV_HALO2D = 3,     /* conv_halo2d_kernel: 2D 3x3 / 1 / pad 1 */
+    TRI_CONV_STEM = 4,       /* conv_stem_kernel: 4 stored input channels, stride 2, 64 outputs; forward only */
+    TRI_CONV_HALO_ROWS = 5,  /* conv_halo_rows_kernel: the row-unit pipeline of the same layers */
+    TRI_CONV_VOX0 = 6,       /* conv_vox0_kernel: voxel level 0; forward only; site mask as row_mask, refuses a row list */
+    TRI_CONV_C64 = 9,        /* conv_c64_kernel: 64 -> 64 channels 3x3 / 1, both directions (7, 8, 11: A/B partners dropped in round 6) */
+    TRI_CONV_S2D = 10,       /* conv_s2d_kernel: data gradient of the 64 -> 128 channel 3x3 / 2 layer */
+    TRI_CONV_PW = 12,        /* conv_pw_kernel: 1x1 / 2 shortcuts */
+    TRI_CONV_VOXG = 13,      /* conv_voxg_kernel: SubMConv3d on 2^3 / 4^3 / 8^3 grids, both directions; site mask, refuses a row list */
+    TRI_CONV_VOXB = 14,      /* conv_voxb_kernel: voxel level 1 on 16^3 / 32^3 grids; forward only; site mask */
+    TRI_CONV_S2G = 15        /* conv_s2g_kernel: forward of the 3x3 / 2 layers with >= 128 input channels; refuses row mask / list, bias,
+                                activation, accumulate.  13 / 14 / 15 read FRAGMENT-MAJOR packed operands */
+} TriConvFamily;
+/* the word tri_conv_kernel_family returns: family | tile << 8 | split-K << 16 | samples per unit << 24 */
+#define TRI_FAMILY_CODE_MASK 255     /* bits 0..7: TriConvFamily */
+#define TRI_FAMILY_TILE_SHIFT 8      /* bits 8..15: output-channel tile width (halo kernels: 64-position blocks per row tile) */
+#define TRI_FAMILY_SPLITK_SHIFT 16   /* bit 16 (IGEMM / DMA): the dense call runs split-K, or has more than 256 DMA k-steps: no row list */
+#define TRI_FAMILY_SPU_SHIFT 24      /* bits 24..30 (VOXG): samples per unit = per BatchNorm record */
+/* the family tri_conv_fwd (transposed = 0) / tri_conv_dgrad (transposed = 1) dispatches for this layer and mode.  For profilers. */
 int tri_conv_kernel_family(const TriConvDesc* d, int transposed, int split3);
 /* same for tri_conv_wgrad: 0 conv_wgrad_kernel, 2 conv_wgrad_dma_kernel (taken when act_fmt != 0 and the layer qualifies) */
 int tri_conv_wgrad_kernel_family(const TriConvDesc* d, int act_fmt);

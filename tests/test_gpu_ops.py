@@ -1168,6 +1168,20 @@ def test_conv_16bit_storage_integer_exact(case, store, prec):
             st = part.cpu().double().sum(0)
             np.testing.assert_allclose(st[0].numpy(), gm.reshape(-1, case[3]).sum(0).numpy(), rtol=1e-6, atol=1e-2)
             np.testing.assert_allclose(st[1].numpy(), (gm * yv.double()).reshape(-1, case[3]).sum(0).numpy(), rtol=1e-6, atol=1e-2)
+    if case[0] in ("c64k_16", "stem_3x3", "h_8x8", "s2d_16"):
+        # calls a family hands on to the generic kernel (conv_families[] `falls`): a row mask on the layers of conv_c64_kernel,
+        # conv_stem_kernel, the halo kernels and conv_s2d_kernel, forward and data gradient - rows with a zero mask byte come out as zeros
+        gen = torch.Generator().manual_seed(71)
+        mo = (torch.rand(ref.numel() // case[4], generator=gen) < 0.6).to(torch.uint8)
+        outm = ops.conv_fwd(xcl.to(DEV).to(store), g, packed, row_mask=mo.to(DEV))
+        assert torch.equal(outm.cpu().reshape(-1, case[4]), (ref.reshape(-1, case[4]) * mo[:, None].float()).to(store))
+        if case[3] != 3:
+            mi = (torch.rand(x.numel() // case[3], generator=gen) < 0.6).to(torch.uint8)
+            dxm = ops.conv_dgrad(cl3(dy).to(DEV).to(store), g, ops.pack_weight(wp.to(DEV), g, prec, transposed=True), row_mask=mi.to(DEV))
+            assert torch.equal(dxm.cpu().reshape(-1, case[3]), (cl3(xr.grad).reshape(-1, case[3]) * mi[:, None].float()).to(store))
+        if case[0] == "c64k_16":
+            with pytest.raises(RuntimeError, match="conv_c64_kernel"):     # the layer's record count is conv_c64_kernel's: no statistics from the generic kernel
+                ops.conv_fwd(xcl.to(DEV).to(store), g, packed, row_mask=mo.to(DEV), want_stats=True)
 
 
 @pytest.mark.parametrize("rows", ["0", "2", "2,tm2", "2,tm2,noprod"])
@@ -1857,6 +1871,8 @@ def test_voxel_level1_ranked_brick_kernel(B, V, store, prec):
     if B <= 5:
         out2 = ops.conv_fwd(xcl.to(DEV).to(store), g, packed)
         assert torch.equal(out2.cpu(), cl3(F.conv3d(x, w, padding=1)).to(store))
+    with pytest.raises(RuntimeError, match="conv_voxb_kernel"):               # a compact row list is refused (the kernel walks the grid by the mask)
+        ops.conv_fwd(xcl.to(DEV).to(store), g, packed, rows=ops.mask_compact(mask.to(DEV), M))
 
 
 VOXG_CASES = [

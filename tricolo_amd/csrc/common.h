@@ -31,6 +31,14 @@ static inline int tri_probe_ablation() {
 }
 int tri_check_launch(const char* what);
 
+// Environment switches (A/B partners, tuning aids): read once per call site, the first call decides for the life of the process.
+// tri_env_int: the variable's integer value, `dflt` when unset; tri_env_is: true when the variable is set and starts with `c`
+// ("=1 switches off" reads tri_env_is(name, '1'), "=0 switches off" reads tri_env_is(name, '0')).
+static inline int tri_env_read_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline bool tri_env_read_is(const char* name, char c) { const char* e = getenv(name); return e && e[0] == c; }
+#define tri_env_int(name, dflt) ([]() -> int { static const int v = tri_env_read_int(name, dflt); return v; }())
+#define tri_env_is(name, c) ([]() -> bool { static const bool v = tri_env_read_is(name, c); return v; }())
+
 // Unsigned division by a runtime constant (Granlund-Montgomery round-up form), valid for n < 2^31.
 struct FastDiv {
     uint32_t mul, shift, d;

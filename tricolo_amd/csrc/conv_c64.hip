@@ -255,27 +255,20 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const ConvC64Args p) {
     }
 }
 
-static bool c64_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_C64_CONV"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
-bool tri_internal_c64_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                               int pd, int ph, int pw, TriC64Geom* g) {
-    if (c64_disabled()) return false;
-    if (ID != 1 || OD != 1 || KD != 1 || KH != 3 || KW != 3 || stride != 1 || pd != 0 || ph != 1 || pw != 1) return false;
-    if (cin != 64 || cout != 64 || OH != IH || OW != IW) return false;
+bool tri_internal_c64_geometry(const TriConvDesc& d, TriC64Geom* g) {
+    if (tri_env_is("TRICOLO_NO_C64_CONV", '1')) return false;
+    if (d.ID != 1 || d.OD != 1 || d.KD != 1 || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad_d != 0 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if (d.Cin != 64 || d.Cout != 64 || d.OH != d.IH || d.OW != d.IW) return false;
     int ty;
-    if (IW == 32) ty = 4; else if (IW == 64 || IW == 56) ty = 2; else if (IW == 16) ty = 8; else return false;
-    if ((long)B * IH * IW * 128 >= (1L << 31)) return false;                  // 32-bit buffer offsets
+    if (d.IW == 32) ty = 4; else if (d.IW == 64 || d.IW == 56) ty = 2; else if (d.IW == 16) ty = 8; else return false;
+    if ((long)d.B * d.IH * d.IW * 128 >= (1L << 31)) return false;            // 32-bit buffer offsets
     const int slots = 2 * tri_internal_num_cus();
     // bricks of 8 runs when that gives every persistent workgroup >= 3 of them, else bricks of 4 (the bench shape: 768 bricks of 8 runs on
     // 512 workgroups are 2 rounds for 1.5 rounds of work; 1,536 bricks of 4 runs are 3 each)
-    if (IH % ty || (long)B * (IH / ty) < 3L * slots) ty /= 2;
-    if (IH % ty) return false;
-    g->W = IW; g->TY = ty;
-    g->nbricks = B * (IH / ty);
+    if (d.IH % ty || (long)d.B * (d.IH / ty) < 3L * slots) ty /= 2;
+    if (d.IH % ty) return false;
+    g->W = d.IW; g->TY = ty;
+    g->nbricks = d.B * (d.IH / ty);
     g->grid = g->nbricks < slots ? g->nbricks : slots;
     return true;
 }
@@ -502,30 +495,23 @@ __global__ __launch_bounds__(256, 2) void conv_s2d_kernel(const ConvS2dArgs p) {
     }
 }
 
-static bool s2d_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_S2D_CONV"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
 // GEMM view of the data-gradient call: "input" = dOut grid (128 channels), "output" = dx grid (64 channels), twice as large
-bool tri_internal_s2d_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                               int pd, int ph, int pw, TriC64Geom* g) {
-    if (s2d_disabled()) return false;
-    if (ID != 1 || OD != 1 || KD != 1 || KH != 3 || KW != 3 || stride != 2 || pd != 0 || ph != 1 || pw != 1) return false;
-    if (cin != 128 || cout != 64 || OH != 2 * IH || OW != 2 * IW) return false;
-    if (IW != 16 && IW != 32) return false;
-    if ((long)B * OH * OW * 128 >= (1L << 31) || (long)B * IH * IW * 256 >= (1L << 31)) return false;
+bool tri_internal_s2d_geometry(const TriConvDesc& d, TriC64Geom* g) {
+    if (tri_env_is("TRICOLO_NO_S2D_CONV", '1')) return false;
+    if (d.ID != 1 || d.OD != 1 || d.KD != 1 || d.KH != 3 || d.KW != 3 || d.stride != 2 || d.pad_d != 0 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if (d.Cin != 128 || d.Cout != 64 || d.OH != 2 * d.IH || d.OW != 2 * d.IW) return false;
+    if (d.IW != 16 && d.IW != 32) return false;
+    if ((long)d.B * d.OH * d.OW * 128 >= (1L << 31) || (long)d.B * d.IH * d.IW * 256 >= (1L << 31)) return false;
     const int slots = 2 * tri_internal_num_cus();
-    int ty = IW == 16 ? 8 : 4;
-    while (ty > 2 && (IH % ty || (long)B * (IH / ty) < 3L * slots)) ty /= 2;   // >= 3 bricks per persistent workgroup where the batch allows
+    int ty = d.IW == 16 ? 8 : 4;
+    while (ty > 2 && (d.IH % ty || (long)d.B * (d.IH / ty) < 3L * slots)) ty /= 2;   // >= 3 bricks per persistent workgroup where the batch allows
     if (const char* e = getenv("TRICOLO_S2D_TY")) {                            // tests: the larger bricks without a batch of hundreds
         const int v = atoi(e);
-        if ((v == 2 || v == 4 || (v == 8 && IW == 16)) && IH % v == 0) ty = v;
+        if ((v == 2 || v == 4 || (v == 8 && d.IW == 16)) && d.IH % v == 0) ty = v;
     }
-    if (IH % ty) return false;
-    g->W = IW; g->TY = ty;
-    g->nbricks = B * (IH / ty);
+    if (d.IH % ty) return false;
+    g->W = d.IW; g->TY = ty;
+    g->nbricks = d.B * (d.IH / ty);
     g->grid = g->nbricks < slots ? g->nbricks : slots;
     return true;
 }

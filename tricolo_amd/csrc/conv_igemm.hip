@@ -12,6 +12,7 @@
 // Precision modes: NSPLIT=1  bf16 operands;  NSPLIT=2  x = hi + lo split, acc += a_lo*b_hi + a_hi*b_lo + a_hi*b_hi
 // (three bf16 MFMAs, ~2^-17 relative operand error: fp32-grade parity at 3/16 of the f32-MFMA cost).
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <map>
 #include <mutex>
@@ -1978,28 +1979,42 @@ static int launch_conv(const ConvArgs& a, hipStream_t stream) {
 
 static int conv_bn(int cout) { return cout % 128 == 0 ? 128 : (cout % 64 == 0 ? 64 : 32); }
 
-// One plan per (geometry, direction), used by the launchers AND by the workspace / statistics-size queries.
+// GEMM view of a call: the descriptor itself for the forward; for the data gradient the gather source is the dOut grid and the rows are
+// the input positions, so grids and channel counts swap.  Plans, family geometries and ConvArgs are all made from the view.
+static TriConvDesc conv_view(const TriConvDesc& d, int transposed) {
+    if (!transposed) return d;
+    TriConvDesc v = d;
+    v.ID = d.OD; v.IH = d.OH; v.IW = d.OW; v.Cin = d.Cout;
+    v.OD = d.ID; v.OH = d.IH; v.OW = d.IW; v.Cout = d.Cin;
+    return v;
+}
+static int conv_kpad(const TriConvDesc& v) { return (v.KD * v.KH * v.KW * v.Cin + 31) / 32 * 32; }
+
+// halo kernels (2D 3x3 / 1 / pad 1, 16-bit storage, Cin % 64 == 0, Cout % 64 == 0): row tiles of 64 * TM positions
+struct HaloGeom {
+    int TM, tr, rows, slab_bytes, nr, mtiles, dbuf;
+    int v5;               // conv_halo_rows_kernel (row-unit pipeline, one workgroup per CU) instead of conv_halo2d_kernel
+    int grid;             // persistent workgroups of the launch (a multiple of the output-channel tiles nt)
+    int wgrec;            // 1: one BatchNorm record per workgroup (grid / nt records), 0: one per row tile (mtiles)
+    int nt;
+};
+
+// One plan per (GEMM view, operand mode, row list or not), used by the dispatch AND by the workspace / record / family queries.
+struct ConvFamily;
 struct ConvPlan {
+    const ConvFamily* family;     // row of conv_families[] that takes every call of this view it can take
+    unsigned fall_also;           // call features (CF_*) this plan hands to the generic kernel on top of the family's own `falls`
+    union {                       // the family's geometry, computed once here and carried to the launch
+        TriVox0Geom vox0; TriVoxbGeom voxb; TriVoxgGeom voxg; StemGeom stem; TriPwGeom pw; TriC64Geom c64; TriS2gGeom s2g;
+    } g;
+    HaloGeom halo;                // (the two halo rows share it: outside the union)
+    const ConvFamily* also;       // a family that takes some calls of this view ahead of `family` without ending the planning (s2d), or NULL
+    TriC64Geom also_g;
+    int tile, spu;                // tile / samples-per-unit fields of the family word (include/tricolo_hip.h)
+    // the generic kernel's plan, for the calls the family does not take (a generic family: for all of them)
+    int dma;              // 1: conv_dma_kernel (16-bit activation storage, Cin % 64 == 0, 64-wide k-steps), 0: conv_igemm_kernel (32-wide)
     int bn;               // output-channel tile
-    int halo;             // 0, or TM (4 / 2) of conv_halo2d_kernel: 2D 3x3 / 1 / pad 1, 16-bit storage, Cin % 64 == 0, Cout % 64 == 0
-    int h_tr, h_rows, h_slab_bytes, h_nr, h_mtiles, h_dbuf;
-    int h_v5;             // conv_halo_rows_kernel (row-unit pipeline, one workgroup per CU) instead of conv_halo2d_kernel
-    int h_grid;           // persistent workgroups of the halo launch (a multiple of the output-channel tiles)
-    int h_wgrec;          // 1: one BatchNorm record per workgroup (h_grid / (Cout / 64) records), 0: one per row tile (h_mtiles)
-    int stem;             // 1: conv_stem_kernel (2D, 4 stored input channels, stride 2, Cout 64, 16-bit storage); records = stem_grid
-    int stem_grid;
-    int vox0;             // 1: conv_vox0_kernel (conv_vox.hip: level 0 of the voxel tower, 16-bit storage); records = vox0_grid
-    int vox0_grid;
-    int voxb, voxb_grid;  // 1: conv_voxb_kernel (conv_voxg.hip: level 1 of the voxel tower, ranked active rows over bricks); records = voxb_grid
-    int s2g, s2g_units;   // 1: conv_s2g_kernel (conv_s2g.hip: forward of the 3x3 / 2 layers that open layer3 / layer4, 16-bit storage); records = s2g_units
-    int voxg;             // 1: conv_voxg_kernel (conv_voxg.hip: SubMConv3d on 2^3 / 4^3 / 8^3 grids, forward and data gradient, 16-bit storage);
-    int voxg_units, voxg_ct, voxg_spu;        // records = units
-    int c64;              // 1: conv_c64_kernel (conv_c64.hip: 64 -> 64 channels, 2D 3x3 / 1 / pad 1, 16-bit storage); records = c64_grid
-    int c64_grid;
-    int s2d;              // 1: conv_s2d_kernel (conv_c64.hip: data gradient of a 64 -> 128 channel 3x3 / 2 layer, 16-bit storage)
-    int pw, pw_tr;        // 1: conv_pw_kernel (conv_pw.hip: 1x1 / 2 shortcut convolution), pw_tr: the plan is the data gradient's; records = row tiles
-    int dma;              // 1: LDS-DMA kernel (16-bit activation storage, Cin % 64 == 0), 64-wide k-steps
-    int nunits;           // k-steps (32 wide, or 64 wide for the DMA kernel)
+    int nunits;           // k-steps
     int ksplit, per_split;
 };
 
@@ -2009,12 +2024,6 @@ static int conv_target_blocks() {                               // tuning aid: T
     static int v = -1;
     if (v < 0) v = 0;
     return v;
-}
-
-static bool halo_disabled() {                                   // A/B switch: TRICOLO_NO_HALO=1 keeps conv_dma_kernel for the 3x3 layers
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_HALO"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
 }
 
 static int num_cus() {
@@ -2031,7 +2040,8 @@ static int num_cus() {
 int tri_internal_num_cus() { return num_cus(); }                     // for conv_wgrad.hip (not part of the C ABI header)
 
 // geometry of conv_halo2d_kernel for row tiles of 64 * TM positions; false when the layer does not fit
-static bool halo_geometry(int B, int H, int W, int cin, int cout, int TM, ConvPlan* pl) {
+static bool halo_geometry(const TriConvDesc& d, int TM, HaloGeom* pl) {
+    const int B = d.B, H = d.IH, W = d.IW, cin = d.Cin, cout = d.Cout;
     const int BM = 64 * TM, P = W + 2;
     if (W > BM) return false;
     const int TR = BM / W;
@@ -2042,21 +2052,20 @@ static bool halo_geometry(int B, int H, int W, int cin, int cout, int TM, ConvPl
     const int rows = TR + 2 * k;
     const int slab = ((rows * P + 1) * 128 + 4095) / 4096 * 4096;
     if (slab / 4096 > 10) return false;                              // HALO_MAX_ROUNDS
-    (void)cout;
-    pl->halo = TM; pl->h_tr = TR; pl->h_rows = rows; pl->h_slab_bytes = slab; pl->h_nr = 3; pl->h_dbuf = 0;
-    pl->h_mtiles = (B * H + TR - 1) / TR;
+    pl->TM = TM; pl->tr = TR; pl->rows = rows; pl->slab_bytes = slab; pl->nr = 3; pl->dbuf = 0;
+    pl->mtiles = (B * H + TR - 1) / TR;
+    pl->nt = cout / 64;
     {
-        const int NT = cout / 64, items = pl->h_mtiles * NT;
+        const int NT = pl->nt, items = pl->mtiles * NT;
         const size_t smem = (size_t)slab + (size_t)HALO_NR * 8192 + 2048;
         int per_cu = (int)(163840 / (smem + 256));
         per_cu = per_cu < 1 ? 1 : (per_cu > 3 ? 3 : per_cu);
         int slots = num_cus() * per_cu / NT * NT;
         if (slots < NT) slots = NT;
-        pl->h_grid = items < slots ? items : slots;
-        pl->h_wgrec = items >= 4 * slots ? 1 : 0;
-        static int rows_kernel = -1;                                  // A/B switch: TRICOLO_HALO_ROWS=0 keeps conv_halo2d_kernel
-        if (rows_kernel < 0) { const char* e = getenv("TRICOLO_HALO_ROWS"); rows_kernel = e ? atoi(e) : 1; }
-        pl->h_v5 = 0;
+        pl->grid = items < slots ? items : slots;
+        pl->wgrec = items >= 4 * slots ? 1 : 0;
+        const int rows_kernel = tri_env_int("TRICOLO_HALO_ROWS", 1);  // A/B switch: TRICOLO_HALO_ROWS=0 keeps conv_halo2d_kernel
+        pl->v5 = 0;
         // where the row-unit pipeline runs (TRICOLO_HALO_ROWS: 0 nowhere, 2 everywhere it fits): 64 input channels (resident filter
         // bank, only slabs stream: layer1 27 against 34 us) and launches with at most 1.5 tiles per workgroup (layer4 of the bench
         // shape 27 against 45 us, layer3 29 / 27 against 30 / 28).  With more weight-streaming tiles per workgroup its one workgroup
@@ -2072,23 +2081,20 @@ static bool halo_geometry(int B, int H, int W, int cin, int cout, int TM, ConvPl
         if (deep < 0) deep = 1;
         if (rows_kernel && (cin == 64 || (deep && cin >= 256) || 2 * items <= half_tiles * g || rows_kernel == 2) && (TM == 2 || (TM == 3 && cin != 64)) &&
             2 * (size_t)slab + 3 * (size_t)HROWS_SLOT + 8192 <= 163840) {
-            pl->h_v5 = 1;
-            pl->h_grid = items < g ? items : g;
-            pl->h_wgrec = 1;                                          // one BatchNorm record per workgroup
+            pl->v5 = 1;
+            pl->grid = items < g ? items : g;
+            pl->wgrec = 1;                                            // one BatchNorm record per workgroup
         }
     }
     return true;
 }
 
-static bool stem_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_STEM"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-static bool stem_geometry(int B, int IH, int IW, int cin, int OH, int OW, int cout, int KD, int KH, int KW, int stride, int pd, int ph, int pw,
-                          StemGeom* g) {
-    if (KD != 1 || pd != 0 || cin != 4 || stride != 2 || cout != 64 || (KH != 3 && KH != 5 && KH != 7) || KW > 8 || OW % 16 || IW % 2) return false;
-    if (pw < 0 || ph < 0 || IW + pw > 2 * OW + 6 || (long)B * IH * IW * 8 >= ((long)1 << 31)) return false;
+// geometry of conv_stem_kernel (2D, 4 stored input channels, stride 2, 64 outputs, 16-bit storage); false when the layer does not fit
+static bool stem_geometry(const TriConvDesc& d, StemGeom* g) {
+    if (tri_env_is("TRICOLO_NO_STEM", '1') || d.ID != 1 || d.OD != 1) return false;
+    const int B = d.B, IH = d.IH, IW = d.IW, OH = d.OH, OW = d.OW, KH = d.KH;
+    if (d.KD != 1 || d.pad_d != 0 || d.Cin != 4 || d.stride != 2 || d.Cout != 64 || (KH != 3 && KH != 5 && KH != 7) || d.KW > 8 || OW % 16 || IW % 2) return false;
+    if (d.pad_w < 0 || d.pad_h < 0 || IW + d.pad_w > 2 * OW + 6 || (long)B * IH * IW * 8 >= ((long)1 << 31)) return false;
     const int per_row = OW / 16;
     static int npt = -1;                                             // position tiles per wave: 2 (two workgroups per CU) unless overridden
     if (npt < 0) npt = 2;
@@ -2109,169 +2115,6 @@ static bool stem_geometry(int B, int IH, int IW, int cin, int OH, int OW, int co
     return true;
 }
 
-static bool dma_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_DMA"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
-// split_mode: 0 bf16 operands / fp32 activations, 1 bf16x3 (hi + lo operands), 2 16-bit operands AND activation storage
-// (bf16 or f16: same kernels, same plans)
-// row_list: the launch walks a compact active-row list (voxel levels): the workgroups past ceil(count / 128) leave at once, so the
-// dense tile count overstates the launch.  The count lives on the device; the plan assumes the usual occupancy of the voxel grids
-// (<= 25 % at every level of the synthetic and ShapeNet-like shapes) when it sizes split-K - a denser list just runs more
-// workgroups than planned.
-static ConvPlan conv_make_plan(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                               int pd, int ph, int pw, int split_mode, int row_list = 0) {
-    ConvPlan pl{};
-    long M = (long)B * OD * OH * OW;
-    int ntaps = KD * KH * KW;
-    int kpad = (ntaps * cin + 31) / 32 * 32;
-    int bn = conv_bn(cout);
-    int blocks = (int)((M + 127) / 128) * (cout / bn);
-    const int blocks_dense = blocks;                                          // the tile-width rule below keeps using the dense count
-    int occ_div = 1;
-    if (row_list) {
-        // measured occupancies of the voxel levels (synthetic shapes, 32^3 and 64^3 inputs): 13-18 % on 16^3 and finer grids, ~25 % at 8^3,
-        // ~45 % at 4^3, ~95 % at 2^3 (coarse levels fill up)
-        const int side = OD > OH ? (OD > OW ? OD : OW) : (OH > OW ? OH : OW);
-        occ_div = side >= 8 ? 4 : (side >= 4 ? 2 : 1);
-        blocks = (blocks + occ_div - 1) / occ_div;
-    }
-    // (round 3: 32-wide output tiles exist too - built for the data gradient of voxel level 1, 64 -> 32 channels, the slowest kernel of
-    // the voxel backward on the register-staged gather: 43-57 -> 24 us.  Config 2's step does not move (1.050-1.063 against 1.058-1.061 ms),
-    // config 4's - where the voxel backward is the tail since the image tower got shorter - gains 0.02 ms in three of three pairs
-    // (2.896-2.922 against 2.920-2.944): on by default, TRICOLO_DMA32=0 switches them off)
-    static int no32 = -1;
-    if (no32 < 0) no32 = 0;
-    if (split_mode == 2 && cin % 64 == 0 && (cout % 64 == 0 || (cout % 32 == 0 && !no32)) && !dma_disabled()) pl.dma = 1;
-    pl.bn = bn;
-    {
-        TriVox0Geom vg;
-        if (split_mode == 2 && tri_internal_vox0_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &vg)) {
-            pl.vox0 = 1; pl.vox0_grid = vg.grid; pl.bn = 32; pl.nunits = 4; pl.ksplit = 1; pl.per_split = 4;
-            return pl;
-        }
-        TriVoxbGeom vb;
-        if (split_mode == 2 && tri_internal_voxb_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &vb)) {
-            pl.voxb = 1; pl.voxb_grid = vb.grid; pl.bn = 64; pl.nunits = 27; pl.ksplit = 1; pl.per_split = 27;
-            return pl;
-        }
-        TriVoxgGeom vgg;
-        if (split_mode == 2 && tri_internal_voxg_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &vgg)) {
-            // coarse voxel grids: activations stationary in LDS, weights straight into MFMA registers (forward and data gradient;
-            // the launch walks the grid by the site mask, one BatchNorm record per unit of samples)
-            pl.voxg = 1; pl.voxg_units = vgg.nunits; pl.voxg_ct = vgg.ct; pl.voxg_spu = vgg.spu;
-            pl.bn = vgg.ct; pl.nunits = kpad / 32; pl.ksplit = 1; pl.per_split = pl.nunits;
-            return pl;
-        }
-    }
-    {
-        StemGeom sgm;
-        if (split_mode == 2 && !stem_disabled() && ID == 1 && OD == 1 &&
-            stem_geometry(B, IH, IW, cin, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &sgm)) {
-            pl.stem = 1; pl.stem_grid = sgm.grid; pl.bn = 64; pl.nunits = KH; pl.ksplit = 1; pl.per_split = KH;
-            return pl;
-        }
-    }
-    {
-        TriPwGeom pg;
-        if (pl.dma && split_mode == 2 && !row_list && tri_internal_pw_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &pg)) {
-            // 1x1 / 2 shortcut convolution: conv_pw_kernel; a call it does not take (row mask / bias / activation / accumulate) runs
-            // conv_dma_kernel without split-K (the fields below are its plan; same record count: one per 128-row tile)
-            pl.pw = 1; pl.pw_tr = pg.transposed; pl.bn = pg.bn; pl.nunits = kpad / 64; pl.ksplit = 1; pl.per_split = pl.nunits;
-            return pl;
-        }
-    }
-    {
-        TriC64Geom cg;
-        if (pl.dma && split_mode == 2 && tri_internal_c64_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &cg)) {
-            // 64 -> 64 channels: conv_c64_kernel (filter bank in registers; conv_c64.hip), forward and data gradient; a call with a
-            // row mask / bias / activation takes conv_dma_kernel (nunits etc. below are its plan)
-            pl.c64 = 1; pl.c64_grid = cg.grid; pl.bn = 64; pl.nunits = kpad / 64; pl.ksplit = 1; pl.per_split = pl.nunits;
-            return pl;
-        }
-    }
-    {
-        TriS2gGeom g2;
-        if (pl.dma && split_mode == 2 && tri_internal_s2g_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &g2)) {
-            // 3x3 / 2 layers with >= 128 input channels: conv_s2g_kernel (space-to-depth slab, weights straight into MFMA registers); a call with a
-            // row mask / list / bias / activation / accumulate is refused (the layer's operand is packed fragment-major).  Planned whether or
-            // not the call carries a row list: the family query packs the operand without knowing, so a row-list call must reach
-            // conv_dispatch's refusal instead of reading the fragment-major operand row-major in conv_dma_kernel
-            pl.s2g = 1; pl.s2g_units = g2.nunits; pl.bn = 64; pl.nunits = kpad / 32; pl.ksplit = 1; pl.per_split = pl.nunits;
-            return pl;
-        }
-    }
-    {
-        TriC64Geom sg;
-        // GEMM view of a data-gradient call (the output grid is twice the input grid: no forward layer looks like this)
-        if (pl.dma && split_mode == 2 && tri_internal_s2d_geometry(B, ID, IH, IW, cin, OD, OH, OW, cout, KD, KH, KW, stride, pd, ph, pw, &sg))
-            pl.s2d = 1;                                                        // (a call with a row mask / list takes conv_dma_kernel: its plan below)
-    }
-    if (pl.dma && cout % 64 == 0 && !halo_disabled() && KD == 1 && KH == 3 && KW == 3 && stride == 1 && pd == 0 && ph == 1 && pw == 1 && ID == 1 && OD == 1 &&
-        IH == OH && IW == OW && (long)B * IH * IW * cin * 2 < ((long)1 << 31)) {
-        // 128-position tiles: a ~25 KB slab + 24 KB ring lets three workgroups share a CU (the kernel is bound by instruction
-        // issue and latency, not by operand bytes: occupancy matters more than the bigger tile's reuse)
-        ConvPlan t2{}, t3{};
-        const ConvPlan* pick = halo_geometry(B, IH, IW, cin, cout, 2, &t2) ? &t2 : nullptr;
-        // 192-position tiles on the row-unit kernel where they save a ROUND of workgroups: a tile of 1.5 x the positions costs ~1.2 x the
-        // time (1.5 x the MFMAs per barrier, weight piece and DMA wait), so they win when 1.2 x their rounds < the 128-position rounds
-        // (layer3 of the bench shape: 384 tiles on 256 CUs -> 256 tiles, 26.5 -> 19.7 us forward, 24.9 -> 18.1 us data gradient; 384 images:
-        // 768 tiles in three rounds -> 512 in two, 47 (conv_halo2d_kernel) -> 32 us; round 4, TRICOLO_HALO_TM3=0 switches them off)
-        static int tm3 = -1;
-        if (tm3 < 0) { const char* e = getenv("TRICOLO_HALO_TM3"); tm3 = (e && e[0] == '0') ? 0 : 1; }
-        if (pick && pick->h_v5 && tm3 && cin != 64 && halo_geometry(B, IH, IW, cin, cout, 3, &t3) && t3.h_v5) {
-            const int nt = cout / 64, g = t2.h_grid > t3.h_grid ? t2.h_grid : t3.h_grid;
-            const int r2 = (t2.h_mtiles * nt + g - 1) / g, r3 = (t3.h_mtiles * nt + g - 1) / g;
-            if (12 * r3 < 10 * r2) pick = &t3;
-        }
-        // (round 6: 192 x 32 tiles - TN = 2 fragments per wave - for launches whose 64-channel tiles leave CUs idle were built and measured:
-        //  layer4 of the bench shape, 256 tiles instead of 192, ran 26 / 25 us against 24 / 23: six MFMAs per five fragment reads and the
-        //  same barriers per k-step cost more than the idle quarter of the GPU; dropped)
-        if (pick) {
-            pl.halo = pick->halo; pl.h_tr = pick->h_tr; pl.h_rows = pick->h_rows; pl.h_slab_bytes = pick->h_slab_bytes;
-            pl.h_nr = pick->h_nr; pl.h_mtiles = pick->h_mtiles; pl.h_dbuf = pick->h_dbuf; pl.h_grid = pick->h_grid; pl.h_wgrec = pick->h_wgrec; pl.h_v5 = pick->h_v5;
-            pl.bn = 64; pl.nunits = 9 * (cin / 64); pl.ksplit = 1; pl.per_split = pl.nunits;
-            return pl;
-        }
-    }
-    {   // The DMA kernel is latency-bound, not MFMA-bound, at this workload's layer sizes: 128x64 tiles (24 KiB stages, three
-        // workgroups per CU, twice the workgroups) beat 128x128 on every layer measured up to 384 wide tiles (sweep in
-        // profiles/r1/README.md).  Wide tiles are kept for launches that fill the GPU several times over anyway.
-        static int narrow = -1;
-        if (narrow < 0) narrow = 1024;
-        // (decided on the DENSE tile count also for row-list launches: 64^3 level 2 - 2,048 dense tiles, 365 live - takes 42 us with
-        // 128-wide tiles against 54 with 64-wide ones; the occupancy discount is for the split-K decision only)
-        if (pl.dma && bn == 128 && blocks_dense < narrow) { pl.bn = 64; blocks *= 2; }
-    }
-    // (round 5) dense layers with a short K on the register-staged kernel (fp32 storage: the GRU's input projection, 3,072 x 256 x 768 at the
-    // bench shape): 64-wide tiles that fill the GPU once instead of 128-wide tiles split over K with a finish launch (two launches, a
-    // 19 MB round trip of partial sums for 8 k-steps of work)
-    static int lin64 = -1;
-    if (lin64 < 0) lin64 = 1;
-    const bool short_linear = lin64 && !pl.dma && !row_list && ntaps == 1 && kpad <= 256 && cout % 64 == 0;
-    if (short_linear && bn == 128 && blocks < num_cus() && 2 * blocks >= num_cus()) { pl.bn = 64; blocks *= 2; }
-    pl.nunits = pl.dma ? kpad / 64 : kpad / 32;
-    int ks = 1;
-    int min_per = pl.dma ? 2 : 4;                                              // at least this many units per split
-    if (blocks < 384 && pl.nunits >= 2 * min_per && cout % 64 == 0 && !(short_linear && blocks >= num_cus())) {
-        const int target = conv_target_blocks() ? conv_target_blocks() : (split_mode == 2 ? 256 : 768);
-        ks = (target + blocks - 1) / blocks;
-        if (ks > pl.nunits / min_per) ks = pl.nunits / min_per;
-        if (ks > 32) ks = 32;
-        if (ks < 1) ks = 1;
-    }
-    if (row_list) {
-        // the fp32 slabs of a row-list launch are sized for the DENSE row count (the live count is a device value): keep them under 48 MB
-        const long per_split = M * cout * (long)sizeof(float);
-        while (ks > 1 && ks * per_split > (48L << 20)) --ks;
-    }
-    pl.per_split = (pl.nunits + ks - 1) / ks;
-    pl.ksplit = (pl.nunits + pl.per_split - 1) / pl.per_split;
-    return pl;
-}
-
 // Pipeline depth of conv_dma_kernel (stages of [128 x 64] + [BN x 64] operand tiles in LDS, NST - 1 of them in flight under the
 // MFMAs).  Launches that fill the GPU several times over run 2 stages x 3 workgroups per CU (profiles/r1/README.md: 2.01 vs 2.24 ms
 // over the ResNet layers).  Launches that cannot - the deep voxel levels over a compact row list, split-K layers, small data
@@ -2280,16 +2123,10 @@ static ConvPlan conv_make_plan(int B, int ID, int IH, int IW, int cin, int OD, i
 // 64^3 level 3 (268 live workgroups) at 56 / 47 / 85 us with 2 / 3 / 4 stages - four stages leave one workgroup per CU and the
 // launch a second, nearly empty round.  128-wide tiles (32 KiB stages) keep 2.  TRICOLO_DMA_STAGES = 2 | 3 | 4 forces one depth
 // everywhere, TRICOLO_DMA_STAGES_ROWS the depth of the row-list launches.
-static int dma_stages_env(const char* name) {
-    const char* e = getenv(name);
-    int v = e ? atoi(e) : 0;
-    return (v >= 2 && v <= 4) ? v : 0;
-}
 static int dma_stages_for(const ConvArgs& a, int bn) {
-    static int forced = -1, rows = -1;
-    if (forced < 0) { forced = dma_stages_env("TRICOLO_DMA_STAGES"); rows = dma_stages_env("TRICOLO_DMA_STAGES_ROWS"); }
-    if (forced) return forced;
-    if (a.row_count && rows) return rows;
+    const int forced = tri_env_int("TRICOLO_DMA_STAGES", 0), rows = tri_env_int("TRICOLO_DMA_STAGES_ROWS", 0);
+    if (forced >= 2 && forced <= 4) return forced;
+    if (a.row_count && rows >= 2 && rows <= 4) return rows;
     const long wgs = (long)((a.M + 127) / 128) * (a.Cout / bn) * a.ksplit;
     const bool small = a.row_count != nullptr || wgs <= 2L * num_cus();
     return (small && bn <= 64) ? 3 : 2;
@@ -2357,28 +2194,28 @@ static int halo_swizzle(int W, int H, int TM) {
 static long long* g_halo_dbg = nullptr;
 #endif
 template <int TM, typename AT>
-static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
-    a.h_tr = pl.h_tr; a.h_rows = pl.h_rows; a.h_slab_bytes = pl.h_slab_bytes; a.h_nr = pl.h_nr; a.h_mtiles = pl.h_mtiles;
-    a.h_dbuf = pl.h_dbuf;
+static int launch_halo(ConvArgs& a, const HaloGeom& pl, hipStream_t stream) {
+    a.h_tr = pl.tr; a.h_rows = pl.rows; a.h_slab_bytes = pl.slab_bytes; a.h_nr = pl.nr; a.h_mtiles = pl.mtiles;
+    a.h_dbuf = pl.dbuf;
     a.h_abl = tri_probe_ablation();
+    a.row_pos = nullptr;
     a.dP = make_fastdiv(a.IW + 2); a.dH2 = make_fastdiv(a.IH + 2);
-    a.h_swz = halo_swizzle(a.IW, a.IH, pl.halo);
+    a.h_swz = halo_swizzle(a.IW, a.IH, pl.TM);
 #ifdef HALO_STAMPS
     a.h_dbg = g_halo_dbg;
-    const size_t smem = (size_t)pl.h_slab_bytes + (size_t)HALO_NR * 8192 + 2048 + 2048;
+    const size_t smem = (size_t)pl.slab_bytes + (size_t)HALO_NR * 8192 + 2048 + 2048;
 #else
-    const size_t smem = (size_t)pl.h_slab_bytes + (size_t)HALO_NR * 8192 + 2048;
+    const size_t smem = (size_t)pl.slab_bytes + (size_t)HALO_NR * 8192 + 2048;
 #endif
     a.h_xcg = 0; a.h_touch = 0;
-    if (pl.h_v5) {
+    if (pl.v5) {
         // XCD blocks + L2 warm-up of the weights (one tile per workgroup, a whole number of workgroups per XCD): the channel-group width cg that
         // moves the fewest bytes into the eight L2s - weights x (row groups = 8 cg / NT) + input rows x (channel groups = NT / cg)
         // (TRICOLO_HALO_XCG=0 keeps the linear tile order, TRICOLO_HALO_TOUCH=0 the cold start: A/B partners)
-        static int xcg_on = -1, touch_on = -1;
-        if (xcg_on < 0) { const char* e = getenv("TRICOLO_HALO_XCG"); xcg_on = e ? atoi(e) : -1; if (xcg_on < 0) xcg_on = 99; }
-        if (touch_on < 0) { const char* e = getenv("TRICOLO_HALO_TOUCH"); touch_on = (e && e[0] == '0') ? 0 : 1; }
-        const int NT = a.Cout / 64, G = pl.h_grid;
-        if (xcg_on && G == pl.h_mtiles * NT && G % 8 == 0 && a.Cin != 64) {
+        const int xcg_env = tri_env_int("TRICOLO_HALO_XCG", -1), xcg_on = xcg_env < 0 ? 99 : xcg_env;
+        const int touch_on = tri_env_is("TRICOLO_HALO_TOUCH", '0') ? 0 : 1;
+        const int NT = a.Cout / 64, G = pl.grid;
+        if (xcg_on && G == pl.mtiles * NT && G % 8 == 0 && a.Cin != 64) {
             const double wb = (double)a.Cout * a.Kpad * 2, ib = (double)a.M * a.Cin * 2;
             double best = 0;
             for (int cg = 1; cg <= NT; ++cg) {
@@ -2395,15 +2232,15 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
 #else
         const size_t extra = 0;
 #endif
-        const bool drip = 2 * (size_t)pl.h_slab_bytes + 3 * (size_t)HROWS_SLOT + 16384 + extra <= 163840 && !a.accumulate && pl.halo != 3;
-        const size_t smem5 = 2 * (size_t)pl.h_slab_bytes + 3 * (size_t)HROWS_SLOT + (drip ? 16384 : 8192) + extra;
+        const bool drip = 2 * (size_t)pl.slab_bytes + 3 * (size_t)HROWS_SLOT + 16384 + extra <= 163840 && !a.accumulate && pl.TM != 3;
+        const size_t smem5 = 2 * (size_t)pl.slab_bytes + 3 * (size_t)HROWS_SLOT + (drip ? 16384 : 8192) + extra;
         // weights: resident filter bank (64 input channels: NTL 1) or streamed (NTL 0).  The kernel also runs groups of 2 / 4 tiles per
         // resident chunk (NTL 2 / 4, TRICOLO_HALO_NTL): measured no better than streaming on any configuration (profiles/r2/NOTES), so
         // those instantiations are only built with -DHALO_NTL_EXPERIMENT
         int ntl = a.Cin == 64 ? 1 : 0;
 #ifdef HALO_NTL_EXPERIMENT
         { static int f = -1; if (f < 0) f = 0;
-          const int items = pl.h_mtiles * (a.Cout / 64), per_wg = (items + pl.h_grid - 1) / pl.h_grid;
+          const int items = pl.mtiles * (a.Cout / 64), per_wg = (items + pl.grid - 1) / pl.grid;
           if (f && a.Cin != 64 && per_wg > 1) ntl = per_wg == 2 ? 2 : 4; }
 #endif
 #define TRI_ROWS_LAUNCH(DRIP_, ACC_, NTL_, ...)                                                                                     \
@@ -2414,7 +2251,7 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
                                     (int)smem5);                                                                                    \
                 attr5 = smem5;                                                                                                      \
             }                                                                                                                       \
-            conv_halo_rows_kernel<AT, DRIP_, ACC_, NTL_, ##__VA_ARGS__><<<pl.h_grid, 256, smem5, stream>>>(a);                       \
+            conv_halo_rows_kernel<AT, DRIP_, ACC_, NTL_, ##__VA_ARGS__><<<pl.grid, 256, smem5, stream>>>(a);                       \
         } while (0)
 #define TRI_ROWS_MODE(NTL_)                                                                                                         \
         do {                                                                                                                        \
@@ -2424,9 +2261,8 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
         } while (0)
         // producer waves for the streamed 128-position tiles (layer4 of the bench shape: 23.0 -> 20.5 us forward, 21.8 -> 19.1 us data gradient;
         // config 3 3.771 -> 3.748 ms, three of three alternating pairs); TRICOLO_HALO_PROD=0 is the A/B partner
-        static int prod = -1;
-        if (prod < 0) { const char* e = getenv("TRICOLO_HALO_PROD"); prod = (e && e[0] == '0') ? 0 : 1; }
-        if (prod && pl.halo == 2 && ntl == 0) {
+        const bool prod = !tri_env_is("TRICOLO_HALO_PROD", '0');
+        if (prod && pl.TM == 2 && ntl == 0) {
 #define TRI_ROWS_LAUNCH_P(DRIP_, ACC_)                                                                                              \
         do {                                                                                                                        \
             static size_t attrp = 0;                                                                                                \
@@ -2435,7 +2271,7 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
                                     (int)smem5);                                                                                    \
                 attrp = smem5;                                                                                                      \
             }                                                                                                                       \
-            conv_halo_rows_kernel<AT, DRIP_, ACC_, 0, 2, true><<<pl.h_grid, 512, smem5, stream>>>(a);                                \
+            conv_halo_rows_kernel<AT, DRIP_, ACC_, 0, 2, true><<<pl.grid, 512, smem5, stream>>>(a);                                \
         } while (0)
             if (a.accumulate) TRI_ROWS_LAUNCH_P(false, true);
             else if (drip) TRI_ROWS_LAUNCH_P(true, false);
@@ -2443,7 +2279,7 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
 #undef TRI_ROWS_LAUNCH_P
             return tri_check_launch("tri_conv(halo rows, producer waves)");
         }
-        if (pl.halo == 3) {                                           // 192-position tiles (streamed weights, epilogue stores)
+        if (pl.TM == 3) {                                           // 192-position tiles (streamed weights, epilogue stores)
             if (a.accumulate) TRI_ROWS_LAUNCH(false, true, 0, 3);
             else TRI_ROWS_LAUNCH(false, false, 0, 3);
         }
@@ -2463,18 +2299,15 @@ static int launch_halo(ConvArgs& a, const ConvPlan& pl, hipStream_t stream) {
         hipFuncSetAttribute((const void*)conv_halo2d_kernel<TM, true, AT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr = smem;
     }
-    if (pl.h_wgrec && a.stats) conv_halo2d_kernel<TM, true, AT><<<pl.h_grid, 256, smem, stream>>>(a);   // persistent workgroups
-    else conv_halo2d_kernel<TM, false, AT><<<pl.h_grid, 256, smem, stream>>>(a);
+    if (pl.wgrec && a.stats) conv_halo2d_kernel<TM, true, AT><<<pl.grid, 256, smem, stream>>>(a);   // persistent workgroups
+    else conv_halo2d_kernel<TM, false, AT><<<pl.grid, 256, smem, stream>>>(a);
     return tri_check_launch("tri_conv(halo)");
 }
 
 template <typename AT>
-static int launch_stem(ConvArgs& a, hipStream_t stream) {
-    StemGeom sg;
+static int launch_stem(ConvArgs& a, const StemGeom& sg, hipStream_t stream) {
     a.h_abl = tri_probe_ablation();
-    if (!stem_geometry(a.B, a.IH, a.IW, a.Cin, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &sg)) {
-        tri_set_error("conv(stem): geometry changed between plan and launch"); return TRI_ERR_ARG;
-    }
+    a.row_pos = nullptr;
     const size_t smem = (size_t)2 * sg.slab_rows * sg.row_bytes + 4 * 64 * 2 * sizeof(float);
 #define TRI_STEM(KH_)                                                                                                     \
     case KH_: {                                                                                                           \
@@ -2507,7 +2340,279 @@ static int launch_dma_any(const ConvArgs& a, int bn, hipStream_t stream) {
     }
 }
 
-static int conv_dispatch(ConvArgs& a, int act_fmt, void* workspace, size_t workspace_bytes, hipStream_t stream, const TriConvBnSums* bs = nullptr) {
+// ------------------------------------------------------------------------------------------- kernel families: one table
+// Which kernel runs a tri_conv_fwd / tri_conv_dgrad call is decided here and nowhere else: conv_families[] has one row per family, tried
+// in table order by conv_make_plan (precedence = row order), and conv_dispatch, the record / family / BatchNorm-sums queries and the
+// refusal message read that row.  A new family is one row (and its launch adapter); ops.CONV_FAMILIES mirrors what Python needs of it.
+
+// features of a call, as the rows name them
+enum : unsigned {
+    CF_FWD = 1, CF_DGRAD = 2,                          // direction
+    CF_MASK = 4,                                       // row_mask
+    CF_ROWS = 8,                                       // compact row list (row_pos + row_count)
+    CF_BIAS_ACT = 16, CF_ACCUM = 32, CF_STATS = 64,
+    CF_BNSUMS = 128,                                   // BatchNorm-backward sums (tri_conv_dgrad_bn)
+    CF_EPI = CF_MASK | CF_ROWS | CF_BIAS_ACT,
+};
+enum ConvNeeds { ANY_MODE, MODE16, MODE16_DMA };        // any operand mode / 16-bit storage / 16-bit storage that conv_dma_kernel could run
+enum { PLAN_NO = 0, PLAN_TAKES = 1, PLAN_ALSO = 2 };    // plan(): not this family / chosen, planning ends / marks the view, planning goes on
+
+struct ConvFamily {
+    TriConvFamily code;
+    const char* kernel;               // name stem of its kernel
+    ConvNeeds needs;
+    int (*plan)(const TriConvDesc& v, int split_mode, int row_list, ConvPlan* pl);    // fills its geometry (and bn / tile / spu / fall_also)
+    unsigned falls;                   // features it cannot take: such a call runs the generic kernel on this plan
+    unsigned refuses;                 // features it cannot take: such a call is refused (TRI_ERR_ARG)
+    unsigned fall_refuses;            // features refused once a call has fallen through (the record count of the layer is the family's)
+    bool fall_drops_order;            // a call that falls through keeps row_pos only as a row list, not as an order hint
+    bool frag;                        // reads the packed operand fragment-major (tri_weight_prep frag = 1)
+    bool site_mask;                   // walks the dense grid by the site mask passed as row_mask
+    int (*records)(const ConvPlan& pl);   // BatchNorm records of a launch; NULL: the generic rule (one per 128-row tile, per 32 rows under split-K)
+    int (*launch)(ConvArgs& a, const ConvPlan& pl, int act_fmt, const TriConvBnSums* bs, hipStream_t stream);    // NULL: the generic kernels
+};
+
+// The DMA kernel is latency-bound, not MFMA-bound, at this workload's layer sizes; split-K fills the GPU for small-M layers.
+// row_list: the launch walks a compact active-row list (voxel levels): the workgroups past ceil(count / 128) leave at once, so the
+// dense tile count overstates the launch.  The count lives on the device; the plan assumes the usual occupancy of the voxel grids
+// (<= 25 % at every level of the synthetic and ShapeNet-like shapes) when it sizes split-K - a denser list just runs more
+// workgroups than planned.
+static int plan_generic(const TriConvDesc& v, int split_mode, int row_list, ConvPlan* pl) {
+    const int cout = v.Cout, ntaps = v.KD * v.KH * v.KW, kpad = conv_kpad(v), bn = conv_bn(cout);
+    const long M = (long)v.B * v.OD * v.OH * v.OW;
+    int blocks = (int)((M + 127) / 128) * (cout / bn);
+    const int blocks_dense = blocks;                                          // the tile-width rule below keeps using the dense count
+    if (row_list) {
+        // measured occupancies of the voxel levels (synthetic shapes, 32^3 and 64^3 inputs): 13-18 % on 16^3 and finer grids, ~25 % at 8^3,
+        // ~45 % at 4^3, ~95 % at 2^3 (coarse levels fill up)
+        const int side = v.OD > v.OH ? (v.OD > v.OW ? v.OD : v.OW) : (v.OH > v.OW ? v.OH : v.OW);
+        const int occ_div = side >= 8 ? 4 : (side >= 4 ? 2 : 1);
+        blocks = (blocks + occ_div - 1) / occ_div;
+    }
+    {   // 128x64 tiles (24 KiB stages, three workgroups per CU, twice the workgroups) beat 128x128 on every layer measured up to 384 wide
+        // tiles (sweep in profiles/r1/README.md).  Wide tiles are kept for launches that fill the GPU several times over anyway.
+        static int narrow = -1;
+        if (narrow < 0) narrow = 1024;
+        // (decided on the DENSE tile count also for row-list launches: 64^3 level 2 - 2,048 dense tiles, 365 live - takes 42 us with
+        // 128-wide tiles against 54 with 64-wide ones; the occupancy discount is for the split-K decision only)
+        if (pl->dma && bn == 128 && blocks_dense < narrow) { pl->bn = 64; blocks *= 2; }
+    }
+    // (round 5) dense layers with a short K on the register-staged kernel (fp32 storage: the GRU's input projection, 3,072 x 256 x 768 at the
+    // bench shape): 64-wide tiles that fill the GPU once instead of 128-wide tiles split over K with a finish launch (two launches, a
+    // 19 MB round trip of partial sums for 8 k-steps of work)
+    static int lin64 = -1;
+    if (lin64 < 0) lin64 = 1;
+    const bool short_linear = lin64 && !pl->dma && !row_list && ntaps == 1 && kpad <= 256 && cout % 64 == 0;
+    if (short_linear && bn == 128 && blocks < num_cus() && 2 * blocks >= num_cus()) { pl->bn = 64; blocks *= 2; }
+    pl->nunits = pl->dma ? kpad / 64 : kpad / 32;
+    int ks = 1;
+    int min_per = pl->dma ? 2 : 4;                                             // at least this many units per split
+    if (blocks < 384 && pl->nunits >= 2 * min_per && cout % 64 == 0 && !(short_linear && blocks >= num_cus())) {
+        const int target = conv_target_blocks() ? conv_target_blocks() : (split_mode == 2 ? 256 : 768);
+        ks = (target + blocks - 1) / blocks;
+        if (ks > pl->nunits / min_per) ks = pl->nunits / min_per;
+        if (ks > 32) ks = 32;
+        if (ks < 1) ks = 1;
+    }
+    if (row_list) {
+        // the fp32 slabs of a row-list launch are sized for the DENSE row count (the live count is a device value): keep them under 48 MB
+        const long per_split = M * cout * (long)sizeof(float);
+        while (ks > 1 && ks * per_split > (48L << 20)) --ks;
+    }
+    pl->per_split = (pl->nunits + ks - 1) / ks;
+    pl->ksplit = (pl->nunits + pl->per_split - 1) / pl->per_split;
+    return PLAN_TAKES;
+}
+
+static int plan_vox0(const TriConvDesc& v, int, int, ConvPlan* pl) { return tri_internal_vox0_geometry(v, &pl->g.vox0); }
+static int plan_voxb(const TriConvDesc& v, int, int, ConvPlan* pl) { return tri_internal_voxb_geometry(v, &pl->g.voxb); }
+// coarse voxel grids: activations stationary in LDS, weights straight into MFMA registers (forward and data gradient; the launch walks
+// the grid by the site mask, one BatchNorm record per unit of samples)
+static int plan_voxg(const TriConvDesc& v, int, int, ConvPlan* pl) {
+    if (!tri_internal_voxg_geometry(v, &pl->g.voxg)) return PLAN_NO;
+    pl->bn = pl->g.voxg.ct; pl->spu = pl->g.voxg.spu;
+    return PLAN_TAKES;
+}
+static int plan_stem(const TriConvDesc& v, int, int, ConvPlan* pl) { return stem_geometry(v, &pl->g.stem); }
+// 1x1 / 2 shortcut convolution, planned only without a row list; serves the direction its geometry read off the two grids
+static int plan_pw(const TriConvDesc& v, int, int row_list, ConvPlan* pl) {
+    if (row_list || !tri_internal_pw_geometry(v, &pl->g.pw)) return PLAN_NO;
+    pl->bn = pl->g.pw.bn; pl->fall_also = pl->g.pw.transposed ? CF_FWD : CF_DGRAD;
+    return PLAN_TAKES;
+}
+// 64 -> 64 channels: filter bank in registers (conv_c64.hip), forward and data gradient
+static int plan_c64(const TriConvDesc& v, int, int, ConvPlan* pl) {
+    if (!tri_internal_c64_geometry(v, &pl->g.c64)) return PLAN_NO;
+    if (pl->g.c64.W > 32) pl->fall_also = CF_BNSUMS;                  // (conv_c64.hip: the sums forms exist for 16- and 32-wide images)
+    return PLAN_TAKES;
+}
+// 3x3 / 2 layers with >= 128 input channels: space-to-depth slab, weights straight into MFMA registers.  Planned whether or not the call
+// carries a row list: the family query packs the operand fragment-major without knowing, so a row-list call must reach the
+// refusal instead of reading that operand row-major in conv_dma_kernel
+static int plan_s2g(const TriConvDesc& v, int, int, ConvPlan* pl) {
+    if (!tri_internal_s2g_geometry(v, &pl->g.s2g)) return PLAN_NO;
+    pl->bn = 64;
+    return PLAN_TAKES;
+}
+// GEMM view of a data-gradient call (the output grid is twice the input grid: no forward layer looks like this); not exclusive: a call
+// conv_s2d_kernel does not take runs conv_dma_kernel or a halo kernel on the plan made below
+static int plan_s2d(const TriConvDesc& v, int, int, ConvPlan* pl) { return tri_internal_s2d_geometry(v, &pl->also_g) ? PLAN_ALSO : PLAN_NO; }
+// 2D 3x3 / 1 / pad 1: the two halo rows share one geometry - the row-unit row computes it (TM = 0: the layer does not fit), the 2D row
+// right below it in the table reads it
+static int plan_halo_rows(const TriConvDesc& v, int, int, ConvPlan* pl) {
+    HaloGeom& h = pl->halo;
+    if (v.Cout % 64 || tri_env_is("TRICOLO_NO_HALO", '1') || v.KD != 1 || v.KH != 3 || v.KW != 3 || v.stride != 1 || v.pad_d != 0 || v.pad_h != 1 ||
+        v.pad_w != 1 || v.ID != 1 || v.OD != 1 || v.IH != v.OH || v.IW != v.OW || (long)v.B * v.IH * v.IW * v.Cin * 2 >= ((long)1 << 31))
+        return PLAN_NO;                                               // A/B switch: TRICOLO_NO_HALO=1 keeps conv_dma_kernel for the 3x3 layers
+    // 128-position tiles: a ~25 KB slab + 24 KB ring lets three workgroups share a CU (the kernel is bound by instruction
+    // issue and latency, not by operand bytes: occupancy matters more than the bigger tile's reuse)
+    HaloGeom t3{};
+    if (!halo_geometry(v, 2, &h)) return PLAN_NO;
+    // 192-position tiles on the row-unit kernel where they save a ROUND of workgroups: a tile of 1.5 x the positions costs ~1.2 x the
+    // time (1.5 x the MFMAs per barrier, weight piece and DMA wait), so they win when 1.2 x their rounds < the 128-position rounds
+    // (layer3 of the bench shape: 384 tiles on 256 CUs -> 256 tiles, 26.5 -> 19.7 us forward, 24.9 -> 18.1 us data gradient; 384 images:
+    // 768 tiles in three rounds -> 512 in two, 47 (conv_halo2d_kernel) -> 32 us; round 4, TRICOLO_HALO_TM3=0 switches them off)
+    if (h.v5 && !tri_env_is("TRICOLO_HALO_TM3", '0') && v.Cin != 64 && halo_geometry(v, 3, &t3) && t3.v5) {
+        const int g = h.grid > t3.grid ? h.grid : t3.grid;
+        const int r2 = (h.mtiles * h.nt + g - 1) / g, r3 = (t3.mtiles * h.nt + g - 1) / g;
+        if (12 * r3 < 10 * r2) h = t3;
+    }
+    // (round 6: 192 x 32 tiles - TN = 2 fragments per wave - for launches whose 64-channel tiles leave CUs idle were built and measured:
+    //  layer4 of the bench shape, 256 tiles instead of 192, ran 26 / 25 us against 24 / 23: six MFMAs per five fragment reads and the
+    //  same barriers per k-step cost more than the idle quarter of the GPU; dropped)
+    if (!h.v5) return PLAN_NO;
+    pl->bn = 64; pl->tile = h.TM;
+    return PLAN_TAKES;
+}
+static int plan_halo2d(const TriConvDesc&, int, int, ConvPlan* pl) {
+    if (!pl->halo.TM) return PLAN_NO;
+    pl->bn = 64; pl->tile = pl->halo.TM;
+    return PLAN_TAKES;
+}
+
+static int halo_records(const ConvPlan& pl) { return pl.halo.wgrec ? pl.halo.grid / pl.halo.nt : pl.halo.mtiles; }
+
+// launch adapters: the call's ConvArgs + the plan's geometry -> the family's launcher
+static int run_vox0(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_vox0_launch(pl.g.vox0, a.B, a.in, a.w_hi, a.Kpad, a.out, a.row_mask, a.stats, fmt, s);
+}
+static int run_voxb(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_voxb_launch(pl.g.voxb, a.B, a.in, a.w_hi, a.out, a.row_mask, a.stats, fmt, s);
+}
+static int run_voxg(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_voxg_launch(pl.g.voxg, a.B, a.Cin, a.Cout, a.Kpad, a.in, a.w_hi, a.out, a.row_mask, a.stats, a.transposed, fmt, s);
+}
+static int run_stem(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return fmt == TRI_FMT_F16 ? launch_stem<f16_t>(a, pl.g.stem, s) : launch_stem<bf16_t>(a, pl.g.stem, s);
+}
+static int run_pw(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_pw_launch(pl.g.pw, a.B, a.in, a.w_hi, a.Cin, a.Cout, a.Kpad, a.out, a.stats, a.transposed ? 1 : 0, fmt, s);
+}
+static int run_c64(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums* bs, hipStream_t s) {
+    return tri_internal_c64_launch(pl.g.c64, a.B, a.IH, a.in, a.w_hi, a.out, bs ? bs->partial : a.stats, a.transposed, a.accumulate, fmt, bs, s);
+}
+static int run_s2g(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_s2g_launch(pl.g.s2g, a.B, a.IH, a.IW, a.Cin, a.Cout, a.Kpad, a.in, a.w_hi, a.out, a.stats, fmt, s);
+}
+static int run_s2d(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return tri_internal_s2d_launch(pl.also_g, a.B, a.IH, a.in, a.w_hi, a.out, a.accumulate, fmt, s);
+}
+static int run_halo(ConvArgs& a, const ConvPlan& pl, int fmt, const TriConvBnSums*, hipStream_t s) {
+    return fmt == TRI_FMT_F16 ? launch_halo<2, f16_t>(a, pl.halo, s) : launch_halo<2, bf16_t>(a, pl.halo, s);
+}
+
+#define CONV_RECORDS(member) [](const ConvPlan& pl) -> int { return pl.g.member; }
+static const ConvFamily conv_families[] = {
+    // code, kernel, needs, plan | falls | refuses | fall_refuses, fall_drops_order | frag, site_mask | records, launch
+    {TRI_CONV_VOX0, "conv_vox0_kernel", MODE16, plan_vox0, CF_DGRAD | CF_BNSUMS, CF_ROWS | CF_BIAS_ACT | CF_ACCUM, 0, false,
+     false, true, CONV_RECORDS(vox0.grid), run_vox0},
+    {TRI_CONV_VOXB, "conv_voxb_kernel", MODE16, plan_voxb, CF_DGRAD | CF_BNSUMS, CF_ROWS | CF_BIAS_ACT | CF_ACCUM, 0, false,
+     true, true, CONV_RECORDS(voxb.grid), run_voxb},
+    {TRI_CONV_VOXG, "conv_voxg_kernel", MODE16, plan_voxg, CF_BNSUMS, CF_ROWS | CF_BIAS_ACT | CF_ACCUM, 0, false,
+     true, true, CONV_RECORDS(voxg.nunits), run_voxg},
+    {TRI_CONV_STEM, "conv_stem_kernel", MODE16, plan_stem, CF_DGRAD | CF_EPI | CF_ACCUM | CF_BNSUMS, 0, 0, false,
+     false, false, CONV_RECORDS(stem.grid), run_stem},
+    {TRI_CONV_PW, "conv_pw_kernel", MODE16_DMA, plan_pw, CF_EPI | CF_ACCUM | CF_BNSUMS, 0, 0, false,
+     false, false, nullptr, run_pw},
+    {TRI_CONV_C64, "conv_c64_kernel", MODE16_DMA, plan_c64, CF_EPI, 0, CF_STATS, true,
+     false, false, CONV_RECORDS(c64.grid), run_c64},
+    {TRI_CONV_S2G, "conv_s2g_kernel", MODE16_DMA, plan_s2g, CF_BNSUMS, CF_DGRAD | CF_EPI | CF_ACCUM, 0, false,
+     true, false, CONV_RECORDS(s2g.nunits), run_s2g},
+    {TRI_CONV_S2D, "conv_s2d_kernel", MODE16_DMA, plan_s2d, CF_FWD | CF_EPI | CF_STATS | CF_BNSUMS, 0, 0, false,
+     false, false, nullptr, run_s2d},
+    {TRI_CONV_HALO_ROWS, "conv_halo_rows_kernel", MODE16_DMA, plan_halo_rows, CF_EPI | CF_BNSUMS, 0, 0, false,
+     false, false, halo_records, run_halo},
+    {TRI_CONV_HALO2D, "conv_halo2d_kernel", MODE16_DMA, plan_halo2d, CF_EPI | CF_BNSUMS, 0, 0, false,
+     false, false, halo_records, run_halo},
+    {TRI_CONV_DMA, "conv_dma_kernel", MODE16_DMA, plan_generic, 0, 0, 0, false, false, false, nullptr, nullptr},
+    {TRI_CONV_IGEMM, "conv_igemm_kernel", ANY_MODE, plan_generic, 0, 0, 0, false, false, false, nullptr, nullptr},
+};
+#undef CONV_RECORDS
+
+// split_mode: 0 bf16 operands / fp32 activations, 1 bf16x3 (hi + lo operands), 2 16-bit operands AND activation storage
+// (bf16 or f16: same kernels, same plans)
+static ConvPlan conv_make_plan(const TriConvDesc& v, int split_mode, int row_list = 0) {
+    ConvPlan pl{};
+    // (round 3: 32-wide output tiles exist too - built for the data gradient of voxel level 1, 64 -> 32 channels, the slowest kernel of
+    // the voxel backward on the register-staged gather: 43-57 -> 24 us.  Config 2's step does not move (1.050-1.063 against 1.058-1.061 ms),
+    // config 4's - where the voxel backward is the tail since the image tower got shorter - gains 0.02 ms in three of three pairs
+    // (2.896-2.922 against 2.920-2.944): on by default, TRICOLO_DMA32=0 switches them off)
+    static int no32 = -1;
+    if (no32 < 0) no32 = 0;
+    if (split_mode == 2 && v.Cin % 64 == 0 && (v.Cout % 64 == 0 || (v.Cout % 32 == 0 && !no32)) && !tri_env_is("TRICOLO_NO_DMA", '1')) pl.dma = 1;
+    pl.bn = conv_bn(v.Cout);
+    for (const ConvFamily& f : conv_families) {
+        if ((f.needs == MODE16 && split_mode != 2) || (f.needs == MODE16_DMA && !pl.dma)) continue;
+        const int r = f.plan(v, split_mode, row_list, &pl);
+        if (r == PLAN_ALSO) pl.also = &f;
+        if (r == PLAN_TAKES) { pl.family = &f; break; }
+    }
+    if (pl.family->launch) {
+        // the generic kernel's plan for the calls the family hands on: the family's channel tile, the whole K in one pass
+        pl.nunits = conv_kpad(v) / (pl.dma ? 64 : 32); pl.ksplit = 1; pl.per_split = pl.nunits;
+    }
+    if (!pl.tile) pl.tile = pl.bn;
+    return pl;
+}
+
+// true when the family of the plan runs a call with these features itself
+static bool conv_takes(const ConvPlan& pl, unsigned feat) {
+    const ConvFamily& f = *pl.family;
+    return f.launch && !(feat & (f.falls | f.refuses | pl.fall_also));
+}
+
+static int conv_refuse(const ConvFamily& f, unsigned what, unsigned wanting) {
+    static const char* const names[] = {"forward", "data gradient", "row mask", "row list", "bias / activation", "accumulate", "statistics",
+                                        "BatchNorm-backward sums"};
+    char msg[400];
+    int n = snprintf(msg, sizeof(msg), "conv: this layer runs %s (tri_conv_kernel_family == %d), which takes no", f.kernel, (int)f.code);
+    for (int pass = 0; pass < 2; ++pass) {
+        const unsigned bits = pass ? wanting : what;
+        if (pass && bits) n += snprintf(msg + n, sizeof(msg) - n, " in a call that wants");
+        const char* sep = " ";
+        for (int b = 0; b < 8; ++b)
+            if (bits >> b & 1) { n += snprintf(msg + n, sizeof(msg) - n, "%s%s", sep, names[b]); sep = ", "; }
+    }
+    if (f.site_mask) snprintf(msg + n, sizeof(msg) - n, "; pass the site mask as row_mask");
+    tri_set_error(msg);
+    return TRI_ERR_ARG;
+}
+
+static ConvArgs conv_args(const TriConvDesc* d, int transposed) {
+    const TriConvDesc v = conv_view(*d, transposed);
+    ConvArgs a{};
+    a.B = v.B; a.ID = v.ID; a.IH = v.IH; a.IW = v.IW; a.Cin = v.Cin;
+    a.OD = v.OD; a.OH = v.OH; a.OW = v.OW; a.Cout = v.Cout;
+    a.KD = v.KD; a.KH = v.KH; a.KW = v.KW; a.stride = v.stride; a.pd = v.pad_d; a.ph = v.pad_h; a.pw = v.pad_w;
+    a.transposed = transposed;
+    a.ntaps = v.KD * v.KH * v.KW;
+    a.M = v.B * v.OD * v.OH * v.OW;
+    return a;
+}
+
+// `a`: conv_args(d, transposed) + the call's pointers, act and accumulate
+static int conv_dispatch(const TriConvDesc* d, ConvArgs& a, int act_fmt, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                         const TriConvBnSums* bs = nullptr) {
     if (a.Cin % 4 != 0) { tri_set_error("conv: stored input channels must be a multiple of 4"); return TRI_ERR_ARG; }
     if (a.Cout % 32 != 0) { tri_set_error("conv: output channels must be a multiple of 32"); return TRI_ERR_ARG; }
     if (a.ntaps > 64) { tri_set_error("conv: more than 64 taps unsupported"); return TRI_ERR_UNSUPPORTED; }
@@ -2521,8 +2626,7 @@ static int conv_dispatch(ConvArgs& a, int act_fmt, void* workspace, size_t works
     a.in_bytes = (unsigned)in_bytes;
     const bool split = a.w_lo != nullptr;
     if (act_fmt && split) { tri_set_error("conv: 16-bit activation storage takes single operands (no lo part)"); return TRI_ERR_ARG; }
-    ConvPlan pl = conv_make_plan(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, act_fmt ? 2 : (split ? 1 : 0),
-                                 a.row_count ? 1 : 0);
+    const ConvPlan pl = conv_make_plan(conv_view(*d, a.transposed), act_fmt ? 2 : (split ? 1 : 0), a.row_count ? 1 : 0);
     a.ksplit = pl.ksplit;
     a.steps_per_split = pl.per_split;
     a.nunits = pl.nunits;
@@ -2547,81 +2651,21 @@ static int conv_dispatch(ConvArgs& a, int act_fmt, void* workspace, size_t works
     } else if (a.row_pos && !(pl.dma && pl.ksplit == 1 && !a.row_mask && !a.stats && a.Kpad / 64 <= 256)) {
         a.row_pos = nullptr;          // a pure visiting-order hint: honoured by the DMA kernel without split-K, dropped elsewhere
     }
-    if (pl.vox0 && !a.transposed) {
-        // the brick kernel walks the dense grid by the SITE MASK (rows of inactive sites are neither computed nor written); its
-        // BatchNorm records are one per workgroup, which is what tri_conv_num_mtiles reports for this layer
-        if (a.row_count || a.bias || a.act != 0 || a.accumulate) {
-            tri_set_error("conv: this layer runs the brick kernel (tri_conv_kernel_family == 6): pass the site mask as row_mask, no row list, "
-                          "bias, activation or accumulate");
-            return TRI_ERR_ARG;
+    const unsigned feat = (a.transposed ? CF_DGRAD : CF_FWD) | (a.row_mask ? CF_MASK : 0) | (a.row_count ? CF_ROWS : 0) |
+                          ((a.bias || a.act != 0) ? CF_BIAS_ACT : 0) | (a.accumulate ? CF_ACCUM : 0) | (a.stats ? CF_STATS : 0) | (bs ? CF_BNSUMS : 0);
+    if (pl.also && !(feat & pl.also->falls)) return pl.also->launch(a, pl, act_fmt, bs, stream);
+    const ConvFamily& f = *pl.family;
+    if (f.launch) {
+        if (!(feat & (f.falls | pl.fall_also))) {
+            if (feat & f.refuses) return conv_refuse(f, f.refuses, 0);
+            return f.launch(a, pl, act_fmt, bs, stream);
         }
-        TriVox0Geom vg;
-        tri_internal_vox0_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &vg);
-        return tri_internal_vox0_launch(vg, a.B, a.in, a.w_hi, a.Kpad, a.out, a.row_mask, a.stats, act_fmt, stream);
-    }
-    if (pl.voxb && !a.transposed) {
-        if (a.row_count || a.bias || a.act != 0 || a.accumulate) {
-            tri_set_error("conv: this layer runs conv_voxb_kernel (tri_conv_kernel_family == 14): pass the site mask as row_mask, no row list, "
-                          "bias, activation or accumulate");
-            return TRI_ERR_ARG;
-        }
-        TriVoxbGeom vb;
-        tri_internal_voxb_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &vb);
-        return tri_internal_voxb_launch(vb, a.B, a.in, a.w_hi, a.out, a.row_mask, a.stats, act_fmt, stream);
-    }
-    if (pl.voxg) {
-        if (a.row_count || a.bias || a.act != 0 || a.accumulate) {
-            tri_set_error("conv: this layer runs conv_voxg_kernel (tri_conv_kernel_family == 13): pass the site mask as row_mask, no row list, "
-                          "bias, activation or accumulate");
-            return TRI_ERR_ARG;
-        }
-        TriVoxgGeom vgg;
-        tri_internal_voxg_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &vgg);
-        return tri_internal_voxg_launch(vgg, a.B, a.Cin, a.Cout, a.Kpad, a.in, a.w_hi, a.out, a.row_mask, a.stats, a.transposed, act_fmt, stream);
-    }
-    if (pl.c64) {
-        if (!a.row_mask && !a.row_count && !a.bias && a.act == 0) {
-            TriC64Geom cg;
-            tri_internal_c64_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &cg);
-            return tri_internal_c64_launch(cg, a.B, a.IH, a.in, a.w_hi, a.out, bs ? bs->partial : a.stats, a.transposed, a.accumulate, act_fmt, bs, stream);
-        }
-        if (a.stats) {                                                // (the record count of this layer is conv_c64_kernel's)
-            tri_set_error("conv: this layer runs conv_c64_kernel (tri_conv_kernel_family == 9): statistics only without row mask / bias / activation");
-            return TRI_ERR_ARG;
-        }
-        a.row_pos = a.row_count ? a.row_pos : nullptr;
-    }
-    if (pl.s2g) {
-        if (a.transposed || a.row_mask || a.row_count || a.bias || a.act != 0 || a.accumulate) {
-            tri_set_error("conv: this layer runs conv_s2g_kernel (tri_conv_kernel_family == 15): forward only, no row mask / list, bias, activation "
-                          "or accumulate");
-            return TRI_ERR_ARG;
-        }
-        TriS2gGeom g2;
-        tri_internal_s2g_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &g2);
-        return tri_internal_s2g_launch(g2, a.B, a.IH, a.IW, a.Cin, a.Cout, a.Kpad, a.in, a.w_hi, a.out, a.stats, act_fmt, stream);
-    }
-    if (pl.s2d && a.transposed && !bs && !a.row_mask && !a.row_count && !a.bias && a.act == 0 && !a.stats) {
-        TriC64Geom sg;
-        tri_internal_s2d_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &sg);
-        return tri_internal_s2d_launch(sg, a.B, a.IH, a.in, a.w_hi, a.out, a.accumulate, act_fmt, stream);
+        if (feat & f.fall_refuses) return conv_refuse(f, f.falls & ~CF_BNSUMS, f.fall_refuses);
+        if (f.fall_drops_order && !a.row_count) a.row_pos = nullptr;
     }
     if (bs) {
         tri_set_error("conv: this layer's data-gradient kernel takes no BatchNorm-backward sums (tri_conv_dgrad_bn_records == 0)");
         return TRI_ERR_UNSUPPORTED;
-    }
-    if (pl.stem && !a.transposed && !a.row_mask && !a.row_count && !a.bias && a.act == 0 && !a.accumulate) {
-        a.row_pos = nullptr;
-        return act_fmt == TRI_FMT_F16 ? launch_stem<f16_t>(a, stream) : launch_stem<bf16_t>(a, stream);
-    }
-    if (pl.halo && !a.row_mask && !a.row_count && !a.bias && a.act == 0) {
-        a.row_pos = nullptr;
-        return act_fmt == TRI_FMT_F16 ? launch_halo<2, f16_t>(a, pl, stream) : launch_halo<2, bf16_t>(a, pl, stream);
-    }
-    if (pl.pw && pl.pw_tr == (a.transposed ? 1 : 0) && !a.row_mask && !a.row_count && !a.bias && a.act == 0 && !a.accumulate) {
-        TriPwGeom pg;
-        tri_internal_pw_geometry(a.B, a.ID, a.IH, a.IW, a.Cin, a.OD, a.OH, a.OW, a.Cout, a.KD, a.KH, a.KW, a.stride, a.pd, a.ph, a.pw, &pg);
-        return tri_internal_pw_launch(pg, a.B, a.in, a.w_hi, a.Cin, a.Cout, a.Kpad, a.out, a.stats, a.transposed ? 1 : 0, act_fmt, stream);
     }
     if (pl.dma) return act_fmt == TRI_FMT_F16 ? launch_dma_any<f16_t>(a, pl.bn, stream) : launch_dma_any<bf16_t>(a, pl.bn, stream);
 #define TRI_CONV(BN_)                                                                                     \
@@ -2636,40 +2680,28 @@ static int conv_dispatch(ConvArgs& a, int act_fmt, void* workspace, size_t works
 
 extern "C" int tri_conv_kpad(int ntaps, int cin_stored) { return (ntaps * cin_stored + 31) / 32 * 32; }
 
-// number of [2][Cout] statistic records tri_conv_fwd writes for this layer: one per 128-row tile, or one per 32-row
-// chunk when the layer runs split-K (the finish kernel produces them).  tri_bn_finalize just sums all records.
+// number of [2][Cout] statistic records tri_conv_fwd writes for this layer: the family's own count, or - the generic rule - one per
+// 128-row tile, one per 32-row chunk when the layer runs split-K (the finish kernel produces them).  tri_bn_finalize just sums all records.
 // split3: 0 bf16 operands / fp32 activations, 1 bf16x3 (hi + lo operands), 2 16-bit operands and activation storage.
-extern "C" int tri_conv_num_records(const TriConvDesc* d, int split3, int row_list) {
-    long M = (long)d->B * d->OD * d->OH * d->OW;
-    ConvPlan pl = conv_make_plan(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                 d->pad_h, d->pad_w, split3, row_list);
-    if (pl.stem) return pl.stem_grid;
-    if (pl.vox0) return pl.vox0_grid;
-    if (pl.voxb) return pl.voxb_grid;
-    if (pl.voxg) return pl.voxg_units;
-    if (pl.c64) return pl.c64_grid;
-    if (pl.s2g) return pl.s2g_units;
-    if (pl.halo) return pl.h_wgrec ? pl.h_grid / (d->Cout / 64) : pl.h_mtiles;
+static int conv_records(const TriConvDesc& v, const ConvPlan& pl) {
+    if (pl.family->records) return pl.family->records(pl);
+    const long M = (long)v.B * v.OD * v.OH * v.OW;
     return pl.ksplit > 1 ? (int)((M + 31) / 32) : (int)((M + 127) / 128);
 }
+extern "C" int tri_conv_num_records(const TriConvDesc* d, int split3, int row_list) { return conv_records(*d, conv_make_plan(*d, split3, row_list)); }
 extern "C" int tri_conv_num_mtiles(const TriConvDesc* d, int split3) { return tri_conv_num_records(d, split3, 0); }
 
-// kernel family the dispatch picks (for profilers): low byte 0 conv_igemm_kernel / 2 conv_dma_kernel, bits 8.. = channel tile
+// kernel family the dispatch picks (for profilers): the word laid out in include/tricolo_hip.h
+static int conv_family_word(int code, int tile, int spu, bool splitk) {
+    return code | (tile << TRI_FAMILY_TILE_SHIFT) | ((splitk ? 1 : 0) << TRI_FAMILY_SPLITK_SHIFT) | (spu << TRI_FAMILY_SPU_SHIFT);
+}
 extern "C" int tri_conv_kernel_family(const TriConvDesc* d, int transposed, int split3) {
-    ConvPlan pl = transposed ? conv_make_plan(d->B, d->OD, d->OH, d->OW, d->Cout, d->ID, d->IH, d->IW, d->Cin, d->KD, d->KH, d->KW, d->stride,
-                                              d->pad_d, d->pad_h, d->pad_w, split3)
-                             : conv_make_plan(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride,
-                                              d->pad_d, d->pad_h, d->pad_w, split3);
-    if (pl.stem && !transposed) return 4 | (64 << 8);
-    if (pl.vox0 && !transposed) return 6 | (32 << 8);
-    if (pl.voxb && !transposed) return 14 | (64 << 8);
-    if (pl.voxg) return 13 | (pl.voxg_ct << 8) | (pl.voxg_spu << 24);      // (bits 24..: samples per unit)
-    if (pl.c64) return 9 | (64 << 8);
-    if (pl.s2d && transposed) return 10 | (64 << 8);
-    if (pl.s2g && !transposed) return 15 | (64 << 8);
-    if (pl.halo) return (pl.h_v5 ? 5 : 3) | (pl.halo << 8);
-    if (pl.pw) return 12 | (pl.bn << 8);
-    return (pl.dma ? 2 : 0) | (pl.bn << 8) | ((pl.ksplit > 1 || (pl.dma && tri_conv_kpad(d->KD * d->KH * d->KW, transposed ? d->Cout : d->Cin) / 64 > 256)) ? (1 << 16) : 0);
+    const TriConvDesc v = conv_view(*d, transposed);
+    const ConvPlan pl = conv_make_plan(v, split3);
+    const unsigned dir = transposed ? CF_DGRAD : CF_FWD;
+    if (pl.also && !(dir & pl.also->falls)) return conv_family_word(pl.also->code, pl.bn, 0, false);
+    if (conv_takes(pl, dir)) return conv_family_word(pl.family->code, pl.tile, pl.spu, false);
+    return conv_family_word(pl.dma ? TRI_CONV_DMA : TRI_CONV_IGEMM, pl.bn, 0, pl.ksplit > 1 || (pl.dma && conv_kpad(v) / 64 > 256));
 }
 
 // out[B,OD,OH,OW,Cout] = conv(in[B,ID,IH,IW,Cin], W) (+bias, act 0 none / 1 relu / 2 tanh); rows with row_mask==0 are
@@ -2677,23 +2709,14 @@ extern "C" int tri_conv_kernel_family(const TriConvDesc* d, int transposed, int 
 // bytes of split-K scratch tri_conv_fwd (transposed = 0) / tri_conv_dgrad (transposed = 1) can use for this layer
 // (0 when the layer already fills the GPU) and therefore REQUIRES.
 extern "C" size_t tri_conv_workspace(const TriConvDesc* d, int transposed) {
+    const TriConvDesc v = conv_view(*d, transposed);
+    const long M = (long)v.B * v.OD * v.OH * v.OW;
     size_t need = 0;
     for (int mode = 0; mode < 6; ++mode) {                                   // three operand modes x (dense | compact row list)
-        ConvPlan pl;
-        long M;
-        int cout;
         const int rl = mode / 3;
         if (rl && (d->KD != 3 || d->stride != 1)) continue;                  // row lists are a voxel-level (3D submanifold) thing
-        if (transposed) {
-            M = (long)d->B * d->ID * d->IH * d->IW; cout = d->Cin;
-            pl = conv_make_plan(d->B, d->OD, d->OH, d->OW, d->Cout, d->ID, d->IH, d->IW, d->Cin, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                d->pad_h, d->pad_w, mode % 3, rl);
-        } else {
-            M = (long)d->B * d->OD * d->OH * d->OW; cout = d->Cout;
-            pl = conv_make_plan(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                d->pad_h, d->pad_w, mode % 3, rl);
-        }
-        size_t n = pl.ksplit > 1 ? (size_t)pl.ksplit * M * cout * sizeof(float) : 0;
+        const ConvPlan pl = conv_make_plan(v, mode % 3, rl);
+        size_t n = pl.ksplit > 1 ? (size_t)pl.ksplit * M * v.Cout * sizeof(float) : 0;
         if (n > need) need = n;
     }
     return need;
@@ -2702,16 +2725,11 @@ extern "C" size_t tri_conv_workspace(const TriConvDesc* d, int transposed) {
 extern "C" int tri_conv_fwd(const TriConvDesc* d, const void* in, const void* w_hi, const void* w_lo, void* out,
                             const uint8_t* row_mask, const float* bias, int act, int accumulate, float* stats, int act_fmt,
                             void* workspace, size_t workspace_bytes, const int* row_pos, const int* row_count, void* stream) {
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 0);
     a.in = in; a.w_hi = w_hi; a.w_lo = w_lo; a.out = out;
     a.row_mask = row_mask; a.bias = bias; a.stats = stats; a.row_pos = row_pos; a.row_count = row_count;
-    a.B = d->B; a.ID = d->ID; a.IH = d->IH; a.IW = d->IW; a.Cin = d->Cin;
-    a.OD = d->OD; a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout;
-    a.KD = d->KD; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pd = d->pad_d; a.ph = d->pad_h; a.pw = d->pad_w;
-    a.transposed = 0; a.act = act; a.accumulate = accumulate;
-    a.ntaps = d->KD * d->KH * d->KW;
-    a.M = d->B * d->OD * d->OH * d->OW;
-    return conv_dispatch(a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream);
+    a.act = act; a.accumulate = accumulate;
+    return conv_dispatch(d, a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // din[B,ID,IH,IW,Cin] (+)= conv_transpose(dout[B,OD,OH,OW,Cout], Wt), Wt packed [Cin][taps*Cout] by tri_weight_prep
@@ -2719,26 +2737,20 @@ extern "C" int tri_conv_fwd(const TriConvDesc* d, const void* in, const void* w_
 extern "C" int tri_conv_dgrad(const TriConvDesc* d, const void* dout, const void* wt_hi, const void* wt_lo, void* din,
                               const uint8_t* row_mask, int accumulate, int act_fmt, void* workspace, size_t workspace_bytes,
                               const int* row_pos, const int* row_count, void* stream) {
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 1);
     a.in = dout; a.w_hi = wt_hi; a.w_lo = wt_lo; a.out = din;
-    a.row_mask = row_mask; a.bias = nullptr; a.stats = nullptr; a.row_pos = row_pos; a.row_count = row_count;
-    a.B = d->B; a.ID = d->OD; a.IH = d->OH; a.IW = d->OW; a.Cin = d->Cout;       // gather source = dout grid
-    a.OD = d->ID; a.OH = d->IH; a.OW = d->IW; a.Cout = d->Cin;                   // rows = input positions
-    a.KD = d->KD; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pd = d->pad_d; a.ph = d->pad_h; a.pw = d->pad_w;
-    a.transposed = 1; a.act = 0; a.accumulate = accumulate;
-    a.ntaps = d->KD * d->KH * d->KW;
-    a.M = d->B * d->ID * d->IH * d->IW;
-    return conv_dispatch(a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream);
+    a.row_mask = row_mask; a.row_pos = row_pos; a.row_count = row_count;
+    a.accumulate = accumulate;
+    return conv_dispatch(d, a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // Data gradient + the BatchNorm-backward sums of the pass that would read din next (include/tricolo_hip.h, TriConvBnSums)
 extern "C" int tri_conv_dgrad_bn_records(const TriConvDesc* d, int accumulate, int act_fmt) {
     (void)accumulate;
     if (act_fmt != TRI_FMT_BF16 && act_fmt != TRI_FMT_F16) return 0;
-    ConvPlan pl = conv_make_plan(d->B, d->OD, d->OH, d->OW, d->Cout, d->ID, d->IH, d->IW, d->Cin, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                 d->pad_h, d->pad_w, 2, 0);
-    if (pl.c64 && d->IW <= 32) return pl.c64_grid;              // (conv_c64.hip: the sums forms exist for 16- and 32-wide images)
-    return 0;
+    const TriConvDesc v = conv_view(*d, 1);
+    const ConvPlan pl = conv_make_plan(v, 2, 0);
+    return conv_takes(pl, CF_DGRAD | CF_BNSUMS) ? conv_records(v, pl) : 0;
 }
 extern "C" int tri_conv_dgrad_bn(const TriConvDesc* d, const void* dout, const void* wt_hi, const void* wt_lo, void* din, int accumulate,
                                  int act_fmt, void* workspace, size_t workspace_bytes, const int* row_pos, const TriConvBnSums* sums,
@@ -2751,14 +2763,9 @@ extern "C" int tri_conv_dgrad_bn(const TriConvDesc* d, const void* dout, const v
         tri_set_error("tri_conv_dgrad_bn: no fused form for this layer (tri_conv_dgrad_bn_records == 0)");
         return TRI_ERR_UNSUPPORTED;
     }
-    ConvArgs a{};
+    ConvArgs a = conv_args(d, 1);
     a.in = dout; a.w_hi = wt_hi; a.w_lo = wt_lo; a.out = din;
     a.row_pos = row_pos;
-    a.B = d->B; a.ID = d->OD; a.IH = d->OH; a.IW = d->OW; a.Cin = d->Cout;
-    a.OD = d->ID; a.OH = d->IH; a.OW = d->IW; a.Cout = d->Cin;
-    a.KD = d->KD; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pd = d->pad_d; a.ph = d->pad_h; a.pw = d->pad_w;
-    a.transposed = 1; a.act = 0; a.accumulate = accumulate;
-    a.ntaps = d->KD * d->KH * d->KW;
-    a.M = d->B * d->ID * d->IH * d->IW;
-    return conv_dispatch(a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream, sums);
+    a.accumulate = accumulate;
+    return conv_dispatch(d, a, act_fmt, workspace, workspace_bytes, (hipStream_t)stream, sums);
 }

@@ -150,27 +150,21 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs p) {
     }
 }
 
-static bool pw_disabled() {                                            // A/B switch: TRICOLO_NO_PW_CONV=1 keeps conv_dma_kernel for the 1x1 / 2 layers
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_PW_CONV"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
 // (arguments in the GEMM view of conv_make_plan: for the data gradient the "input" grid is dOut's and the "output" grid twice as large -
 //  the direction is read off the two grids)
-bool tri_internal_pw_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride, int pd,
-                              int ph, int pw, TriPwGeom* g) {
-    if (pw_disabled() || KD != 1 || KH != 1 || KW != 1 || stride != 2 || pd || ph || pw || ID != 1 || OD != 1) return false;
-    if (cin % 64 || cin > 512 || cout % 64) return false;
+bool tri_internal_pw_geometry(const TriConvDesc& d, TriPwGeom* g) {
+    // A/B switch: TRICOLO_NO_PW_CONV=1 keeps conv_dma_kernel for the 1x1 / 2 layers
+    if (tri_env_is("TRICOLO_NO_PW_CONV", '1') || d.KD != 1 || d.KH != 1 || d.KW != 1 || d.stride != 2 || d.pad_d || d.pad_h || d.pad_w || d.ID != 1 || d.OD != 1) return false;
+    if (d.Cin % 64 || d.Cin > 512 || d.Cout % 64) return false;
     int transposed;
-    if (IH == 2 * OH && IW == 2 * OW) transposed = 0;
-    else if (OH == 2 * IH && OW == 2 * IW) transposed = 1;
+    if (d.IH == 2 * d.OH && d.IW == 2 * d.OW) transposed = 0;
+    else if (d.OH == 2 * d.IH && d.OW == 2 * d.IW) transposed = 1;
     else return false;
-    const int GH = transposed ? IH : OH, GW = transposed ? IW : OW;
-    const long M = (long)B * GH * GW;
-    if (M * 4 * (cin > cout ? cin : cout) * 2 >= ((long)1 << 31)) return false;
+    const int GH = transposed ? d.IH : d.OH, GW = transposed ? d.IW : d.OW;
+    const long M = (long)d.B * GH * GW;
+    if (M * 4 * (d.Cin > d.Cout ? d.Cin : d.Cout) * 2 >= ((long)1 << 31)) return false;
     const int mtiles = (int)((M + 127) / 128);
-    const int bn = (cout % 128 == 0 && (long)128 * cin * 2 <= 65536 && (long)mtiles * (cout / 128) >= 256) ? 128 : 64;
+    const int bn = (d.Cout % 128 == 0 && (long)128 * d.Cin * 2 <= 65536 && (long)mtiles * (d.Cout / 128) >= 256) ? 128 : 64;
     g->bn = bn; g->mtiles = mtiles; g->GH = GH; g->GW = GW; g->transposed = transposed;
     return true;
 }

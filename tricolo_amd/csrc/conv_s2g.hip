@@ -299,23 +299,16 @@ __global__ __launch_bounds__(256, 1) void conv_s2g_kernel(const S2gArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ plan + launch
-static bool s2g_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_S2G"); v = (e && e[0] == '1') ? 1 : 0; }       // A/B switch: these layers stay on conv_dma_kernel
-    return v == 1;
-}
-
-bool tri_internal_s2g_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                               int pd, int ph, int pw, TriS2gGeom* g) {
-    if (s2g_disabled()) return false;
-    if (ID != 1 || OD != 1 || KD != 1 || KH != 3 || KW != 3 || stride != 2 || pd != 0 || ph != 1 || pw != 1) return false;
-    if (IH % 2 || IW % 2 || OH != IH / 2 || OW != IW / 2) return false;
-    if (cin % 64 != 0 || cin < 128 || cout % 64 != 0) return false;           // (64-channel inputs: layer2's opening layer has kernels of its own)
-    const int opi = OH * OW, ppi = IH * IW;
+bool tri_internal_s2g_geometry(const TriConvDesc& d, TriS2gGeom* g) {
+    if (tri_env_is("TRICOLO_NO_S2G", '1')) return false;                      // A/B switch: these layers stay on conv_dma_kernel
+    if (d.ID != 1 || d.OD != 1 || d.KD != 1 || d.KH != 3 || d.KW != 3 || d.stride != 2 || d.pad_d != 0 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if (d.IH % 2 || d.IW % 2 || d.OH != d.IH / 2 || d.OW != d.IW / 2) return false;
+    if (d.Cin % 64 != 0 || d.Cin < 128 || d.Cout % 64 != 0) return false;           // (64-channel inputs: layer2's opening layer has kernels of its own)
+    const int opi = d.OH * d.OW, ppi = d.IH * d.IW;
     if (opi > 192 || opi < 4) return false;
-    if (ppi <= 64 ? 64 % ppi != 0 : (32 % IW != 0 || ppi % 64 != 0)) return false;      // the slab pieces of a thread step uniformly (see the kernel)
-    if ((long)B * IH * IW * cin * 2 >= (1L << 31) || (long)cout * 9 * cin * 2 >= (1L << 31)) return false;      // 32-bit buffer offsets
-    const int cus = tri_internal_num_cus(), nct = cout / 64;
+    if (ppi <= 64 ? 64 % ppi != 0 : (32 % d.IW != 0 || ppi % 64 != 0)) return false;      // the slab pieces of a thread step uniformly (see the kernel)
+    if ((long)d.B * d.IH * d.IW * d.Cin * 2 >= (1L << 31) || (long)d.Cout * 9 * d.Cin * 2 >= (1L << 31)) return false;      // 32-bit buffer offsets
+    const int cus = tri_internal_num_cus(), nct = d.Cout / 64;
     if (nct >= 8 ? nct % 8 : 8 % nct) return false;
     // Measured at the bench shape (profiles/r5/NOTES_voxel.md): layer4's opening layer (8x8 maps, units of 6 images = 96 rows) 27 -> 20 us against
     // conv_dma_kernel; layer3's (16x16 maps, units of 3 images = 192 rows, a 12-fragment variant of this kernel) 25 against 21 us - a chunk's
@@ -325,11 +318,11 @@ bool tri_internal_s2g_geometry(int B, int ID, int IH, int IW, int cin, int OD, i
     // images per unit: up to 96 rows, halved while the launch would leave CUs without a workgroup
     int ipu = 96 / opi;
     if (ipu < 1) return false;
-    if (ipu > B) ipu = B;
-    while (ipu > 1 && (long)((B + ipu - 1) / ipu) * nct < cus) ipu = (ipu + 1) / 2;
-    const int PW = OW + 1, PS = (OH + 1) * PW;
+    if (ipu > d.B) ipu = d.B;
+    while (ipu > 1 && (long)((d.B + ipu - 1) / ipu) * nct < cus) ipu = (ipu + 1) / 2;
+    const int PW = d.OW + 1, PS = (d.OH + 1) * PW;
     const int NSP = (ipu * PS + 31) / 32 * 32;
-    g->ipu = ipu; g->nunits = (B + ipu - 1) / ipu; g->nrt = 6;
+    g->ipu = ipu; g->nunits = (d.B + ipu - 1) / ipu; g->nrt = 6;
     g->PW = PW; g->PS = PS; g->NSP = NSP; g->HB = NSP * 32 + 128;          // (+128: the two halves of a site - lanes fq 0,1 / 2,3 of a fragment read - land on different banks)
     g->grid = nct >= 8 ? g->nunits * nct : 8 * ((g->nunits + 8 / nct - 1) / (8 / nct));
     size_t smem = (size_t)2 * 8 * g->HB;

@@ -472,11 +472,6 @@ __global__ __launch_bounds__(256, 3) void conv_vox0_wgrad_kernel(const Vox0Wgrad
     }
 }
 
-static bool vox_disabled(const char* name) {
-    const char* e = getenv(name);
-    return e && e[0] == '1';
-}
-
 // brick rows per workgroup: 32^3 -> 16 (64 runs), 64^3 -> 8 (64 runs; TRICOLO_VOX0_TY=16: 128 runs), 128^3 -> 8 (128 runs)
 static int vox0_ty(int V) {
     static int env = -1;
@@ -485,18 +480,15 @@ static int vox0_ty(int V) {
     return V == 32 ? 16 : 8;
 }
 
-bool tri_internal_vox0_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                                int pd, int ph, int pw, TriVox0Geom* g) {
-    static int off = -1;
-    if (off < 0) off = vox_disabled("TRICOLO_NO_VOX0") ? 1 : 0;               // A/B switch: level 0 stays on conv_igemm_kernel
-    if (off) return false;
-    const int V = ID;
-    if (IH != V || IW != V || OD != V || OH != V || OW != V || (V != 32 && V != 64 && V != 128)) return false;
-    if (cin != 4 || cout != 32 || KD != 3 || KH != 3 || KW != 3 || stride != 1 || pd != 1 || ph != 1 || pw != 1) return false;
-    if ((long)B * V * V * V * 8 >= (1L << 31)) return false;                  // 32-bit buffer offsets
+bool tri_internal_vox0_geometry(const TriConvDesc& d, TriVox0Geom* g) {
+    if (tri_env_is("TRICOLO_NO_VOX0", '1')) return false;                     // A/B switch: level 0 stays on conv_igemm_kernel
+    const int V = d.ID;
+    if (d.IH != V || d.IW != V || d.OD != V || d.OH != V || d.OW != V || (V != 32 && V != 64 && V != 128)) return false;
+    if (d.Cin != 4 || d.Cout != 32 || d.KD != 3 || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad_d != 1 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if ((long)d.B * V * V * V * 8 >= (1L << 31)) return false;                // 32-bit buffer offsets
     g->V = V;
     g->TY = vox0_ty(V);
-    g->grid = B * (V / 2) * (V / g->TY);
+    g->grid = d.B * (V / 2) * (V / g->TY);
     return true;
 }
 
@@ -548,9 +540,7 @@ static int vox0_wgrad_launch_t(const Vox0WgradArgs& a, int grid, hipStream_t str
 }
 // workgroups (= fp32 slabs [32][144]) of the level-0 weight-gradient kernel: persistent, three per CU
 int tri_internal_vox0_wgrad_grid(const TriVox0Geom& g) {
-    static int off = -1;
-    if (off < 0) off = vox_disabled("TRICOLO_NO_VOX0_WGRAD") ? 1 : 0;         // A/B switch: level 0 stays on conv_wgrad_kernel
-    if (off) return 0;
+    if (tri_env_is("TRICOLO_NO_VOX0_WGRAD", '1')) return 0;                   // A/B switch: level 0 stays on conv_wgrad_kernel
     const int slots = 3 * tri_internal_num_cus();
     return g.grid < slots ? g.grid : slots;
 }

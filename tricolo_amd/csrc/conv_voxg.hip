@@ -401,39 +401,30 @@ __global__ __launch_bounds__(256, 1) void conv_voxg_kernel(const VoxgArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ plan + launch
-static bool voxg_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_VOXG"); v = (e && e[0] == '1') ? 1 : 0; }      // A/B switch: these levels stay on conv_dma_kernel
-    return v == 1;
-}
-
-bool tri_internal_voxg_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                                int pd, int ph, int pw, TriVoxgGeom* g) {
-    if (voxg_disabled()) return false;
-    const int D = ID;
-    if (IH != D || IW != D || OD != D || OH != D || OW != D || (D != 2 && D != 4 && D != 8)) return false;
-    if (KD != 3 || KH != 3 || KW != 3 || stride != 1 || pd != 1 || ph != 1 || pw != 1) return false;
-    if (cin % 64 != 0 || cout % 16 != 0) return false;                        // (two 32-channel chunks per loop iteration)
-    if ((long)B * D * D * D * cin * 2 >= (1L << 31) || (long)cout * 27 * cin * 2 >= (1L << 31)) return false;   // 32-bit buffer offsets
+bool tri_internal_voxg_geometry(const TriConvDesc& d, TriVoxgGeom* g) {
+    if (tri_env_is("TRICOLO_NO_VOXG", '1')) return false;                     // A/B switch: these levels stay on conv_dma_kernel
+    const int D = d.ID;
+    if (d.IH != D || d.IW != D || d.OD != D || d.OH != D || d.OW != D || (D != 2 && D != 4 && D != 8)) return false;
+    if (d.KD != 3 || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad_d != 1 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if (d.Cin % 64 != 0 || d.Cout % 16 != 0) return false;                        // (two 32-channel chunks per loop iteration)
+    if ((long)d.B * D * D * D * d.Cin * 2 >= (1L << 31) || (long)d.Cout * 27 * d.Cin * 2 >= (1L << 31)) return false;   // 32-bit buffer offsets
     const int D3 = D * D * D;
     // samples per unit: about 128 active sites at the occupancies these grids have (25 % at 8^3, 45 % at 4^3, 95 % at 2^3), at most 512
     // dense sites, halved while the launch would leave CUs without a workgroup of 16 output channels
     const double occ = D == 8 ? 0.25 : (D == 4 ? 0.45 : 0.95);
     int spu = 1;
-    while (2 * spu * D3 <= 512 && occ * 2 * spu * D3 <= 128.0 && 2 * spu <= B) spu *= 2;
+    while (2 * spu * D3 <= 512 && occ * 2 * spu * D3 <= 128.0 && 2 * spu <= d.B) spu *= 2;
     const int cus = tri_internal_num_cus();
-    while (spu > 1 && (long)((B + spu - 1) / spu) * (cout / 16) < cus) spu /= 2;
-    const int nunits = (B + spu - 1) / spu;
+    while (spu > 1 && (long)((d.B + spu - 1) / spu) * (d.Cout / 16) < cus) spu /= 2;
+    const int nunits = (d.B + spu - 1) / spu;
     // output channels per workgroup: as many as keep one workgroup per CU (fewer weight re-reads of the slab, fewer partial-sum waves)
     int ct = 16;
-    while (ct < 64 && cout % (2 * ct) == 0 && (long)nunits * (cout / (2 * ct)) >= cus) ct *= 2;
-    static int force_ct = -1, force_spu = -1;                                 // tuning aids
-    if (force_ct < 0) { const char* e = getenv("TRICOLO_VOXG_CT"); force_ct = e ? atoi(e) : 0; }
-    if (force_spu < 0) { const char* e = getenv("TRICOLO_VOXG_SPU"); force_spu = e ? atoi(e) : 0; }
-    if (force_ct == 16 || force_ct == 32 || force_ct == 64) { if (cout % force_ct == 0) ct = force_ct; }
+    while (ct < 64 && d.Cout % (2 * ct) == 0 && (long)nunits * (d.Cout / (2 * ct)) >= cus) ct *= 2;
+    const int force_ct = tri_env_int("TRICOLO_VOXG_CT", 0), force_spu = tri_env_int("TRICOLO_VOXG_SPU", 0);    // tuning aids
+    if (force_ct == 16 || force_ct == 32 || force_ct == 64) { if (d.Cout % force_ct == 0) ct = force_ct; }
     if (force_spu > 0 && force_spu * D3 <= 512) { spu = force_spu; }
-    g->D = D; g->spu = spu; g->nunits = (B + spu - 1) / spu; g->ct = ct;
-    const int nct = cout / ct;
+    g->D = D; g->spu = spu; g->nunits = (d.B + spu - 1) / spu; g->ct = ct;
+    const int nct = d.Cout / ct;
     if (nct >= 8) { if (nct % 8) return false; g->grid = g->nunits * nct; }
     else { if (8 % nct) return false; const int r = 8 / nct; g->grid = 8 * ((g->nunits + r - 1) / r); }
     const VoxgGeom vg = voxg_geom(D, spu);
@@ -768,27 +759,19 @@ __global__ __launch_bounds__(256, 2) void conv_voxb_kernel(const VoxbArgs p) {
     }
 }
 
-static bool voxb_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_VOXB"); v = (e && e[0] == '1') ? 1 : 0; }      // A/B switch: level 1 stays on conv_igemm_kernel
-    return v == 1;
-}
-
-bool tri_internal_voxb_geometry(int B, int ID, int IH, int IW, int cin, int OD, int OH, int OW, int cout, int KD, int KH, int KW, int stride,
-                                int pd, int ph, int pw, TriVoxbGeom* g) {
-    if (voxb_disabled()) return false;
-    const int D = ID;
+bool tri_internal_voxb_geometry(const TriConvDesc& d, TriVoxbGeom* g) {
+    if (tri_env_is("TRICOLO_NO_VOXB", '1')) return false;                     // A/B switch: level 1 stays on conv_igemm_kernel
+    const int D = d.ID;
     // 16^3 grids (32^3 inputs) by default: 15.1 / 23.4 us against conv_vox1_kernel's 16.4 / 26.0 at batch 32 / 64.  On 32^3 grids (64^3
     // inputs, 8,192 bricks, three quarters of them empty) the per-brick chain - mask, two rankings, tables, slab gather, three barriers,
     // and a B-fragment read per MFMA with two workgroups sharing the LDS (stamps: 11 k cycles per non-empty brick against 2.6 k of
     // MFMAs) - makes it 100 us against conv_igemm_kernel's 88: TRICOLO_VOXB_32=1 plans it there anyway (tests do, in a child process)
-    static int big = -1;
-    if (big < 0) { const char* e = getenv("TRICOLO_VOXB_32"); big = (e && e[0] == '1') ? 1 : 0; }
-    if (IH != D || IW != D || OD != D || OH != D || OW != D || (D != 16 && !(D == 32 && big))) return false;
-    if (cin != 32 || cout != 64 || KD != 3 || KH != 3 || KW != 3 || stride != 1 || pd != 1 || ph != 1 || pw != 1) return false;
-    if ((long)B * D * D * D * 64 >= (1L << 31)) return false;                 // 32-bit buffer offsets
+    const bool big = tri_env_is("TRICOLO_VOXB_32", '1');
+    if (d.IH != D || d.IW != D || d.OD != D || d.OH != D || d.OW != D || (D != 16 && !(D == 32 && big))) return false;
+    if (d.Cin != 32 || d.Cout != 64 || d.KD != 3 || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad_d != 1 || d.pad_h != 1 || d.pad_w != 1) return false;
+    if ((long)d.B * D * D * D * 64 >= (1L << 31)) return false;                 // 32-bit buffer offsets
     g->D = D;
-    g->nbricks = B * (D / 2) * (D / (D == 16 ? 4 : 128 / D));
+    g->nbricks = d.B * (D / 2) * (D / (D == 16 ? 4 : 128 / D));
     int grid = 2 * tri_internal_num_cus();                                    // persistent: two workgroups per CU
     if (grid > g->nbricks) grid = g->nbricks;
     g->grid = grid;

@@ -1424,11 +1424,7 @@ static int wgrad_target_blocks() {                             // tuning aid: TR
     return v;
 }
 
-static bool wgrad_dma_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_DMA"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
+static bool wgrad_dma_disabled() { return tri_env_is("TRICOLO_NO_DMA", '1'); }
 
 // act_fmt != 0 asks for the plan of the bf16-storage call; *dma is set when that call runs the LDS-DMA kernel
 // (64-position steps), and steps_per_split is then in 64-position units.
@@ -1473,11 +1469,7 @@ static void wgrad_plan(const TriConvDesc* d, int act_fmt, int rowlist, int* BI, 
 }
 
 int tri_internal_num_cus();                                         // conv_igemm.hip
-static bool stem_wgrad_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_STEM_WGRAD"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
+static bool stem_wgrad_disabled() { return tri_env_is("TRICOLO_NO_STEM_WGRAD", '1'); }
 // geometry of conv_stem_wgrad_kernel; false when the layer does not qualify (it then runs conv_wgrad_kernel)
 static bool stem_wgrad_geometry(const TriConvDesc* d, int act_fmt, StemWgradArgs* g, int* grid) {
     if (!act_fmt || stem_wgrad_disabled()) return false;
@@ -1500,11 +1492,7 @@ static bool stem_wgrad_geometry(const TriConvDesc* d, int act_fmt, StemWgradArgs
     return true;
 }
 
-static bool krow_wgrad_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("TRICOLO_NO_KROW_WGRAD"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
+static bool krow_wgrad_disabled() { return tri_env_is("TRICOLO_NO_KROW_WGRAD", '1'); }
 static bool c64_wgrad_disabled() {
     static int v = -1;
     if (v < 0) v = 0;
@@ -1636,8 +1624,7 @@ extern "C" size_t tri_conv_wgrad_workspace(const TriConvDesc* d) {
         C64WgradArgs cg;
         if (c64_wgrad_geometry(d, 1, &cg, &grid)) need = (size_t)grid * 64 * 576 * sizeof(float);
         TriVox0Geom vg;
-        if (tri_internal_vox0_geometry(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                       d->pad_h, d->pad_w, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
+        if (tri_internal_vox0_geometry(*d, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
             need = (size_t)tri_internal_vox0_wgrad_grid(vg) * 32 * 144 * sizeof(float);
         KrowArgs kg; int co_t, tiles, steps;
         if (krow_geometry(d, 1, &kg, &co_t, &tiles, &steps)) {
@@ -1660,8 +1647,7 @@ extern "C" size_t tri_conv_wgrad_workspace(const TriConvDesc* d) {
 extern "C" int tri_conv_wgrad_kernel_family(const TriConvDesc* d, int act_fmt) {
     {
         TriVox0Geom vg;
-        if (act_fmt && tri_internal_vox0_geometry(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride,
-                                                  d->pad_d, d->pad_h, d->pad_w, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
+        if (act_fmt && tri_internal_vox0_geometry(*d, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
             return 6;                                              // conv_vox0_wgrad_kernel when the call passes a site mask
     }
     {
@@ -1886,8 +1872,7 @@ extern "C" int tri_conv_wgrad_partial(const TriConvDesc* d, const void* in, cons
     {   // voxel level 0 over a site mask: conv_vox0_wgrad_kernel (conv_vox.hip)
         TriVox0Geom vg; int grid;
         if (row_mask && !row_count && !split3 && act_fmt &&
-            tri_internal_vox0_geometry(d->B, d->ID, d->IH, d->IW, d->Cin, d->OD, d->OH, d->OW, d->Cout, d->KD, d->KH, d->KW, d->stride, d->pad_d,
-                                       d->pad_h, d->pad_w, &vg) && (grid = tri_internal_vox0_wgrad_grid(vg)) > 0) {
+            tri_internal_vox0_geometry(*d, &vg) && (grid = tri_internal_vox0_wgrad_grid(vg)) > 0) {
             const size_t need = (size_t)grid * 32 * 144 * sizeof(float);
             if (workspace_bytes < need) { tri_set_error("wgrad(vox0): workspace too small"); return TRI_ERR_ARG; }
             int rc = tri_internal_vox0_wgrad_launch(vg, grid, d->B, in, dout, row_mask, (float*)workspace, act_fmt, (hipStream_t)stream);

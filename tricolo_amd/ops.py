@@ -10,6 +10,7 @@ current torch stream (so the calls can be captured into a HIP graph together wit
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 
@@ -130,34 +131,33 @@ def _flops_sum(items):
 _TNAME = {torch.float32: "float", torch.bfloat16: "bf16", torch.float16: "f16"}
 
 
+# Kernel families of tri_conv_fwd / tri_conv_dgrad by code (TriConvFamily in include/tricolo_hip.h; the C side's table is conv_families[]
+# in csrc/conv_igemm.hip): what rocprofv3 calls the kernel (variants of one family under one name), whether it reads the packed operand
+# fragment-major (tri_weight_prep frag), and whether it walks the dense grid by the SITE MASK passed as row_mask.
+ConvFamily = collections.namedtuple("ConvFamily", "symbol frag site_mask")
+CONV_FAMILIES = {
+    0: ConvFamily("conv_igemm_kernel<{tile}, {nsplit}, {t}>", False, False),
+    2: ConvFamily("conv_dma_kernel<{tile}, {t}>", False, False),
+    3: ConvFamily("conv_halo2d_kernel<{tile}, {t}>", False, False),
+    4: ConvFamily("conv_stem_kernel<{kh}, {t}>", False, False),
+    5: ConvFamily("conv_halo_rows_kernel<{t}>", False, False),
+    6: ConvFamily("conv_vox0_kernel<{t}>", False, True),
+    9: ConvFamily("conv_c64_kernel<{t}>", False, False),
+    10: ConvFamily("conv_s2d_kernel<{t}>", False, False),
+    12: ConvFamily("conv_pw_kernel<{tile}, {t}>", False, False),
+    13: ConvFamily("conv_voxg_kernel<{tile}, {t}>", True, True),
+    14: ConvFamily("conv_voxb_kernel<{t}>", True, True),
+    15: ConvFamily("conv_s2g_kernel<{t}>", True, False),
+}
+# the word tri_conv_kernel_family returns (TRI_FAMILY_* in include/tricolo_hip.h)
+FAMILY_CODE_MASK, FAMILY_TILE_SHIFT, FAMILY_SPLITK_SHIFT, FAMILY_SPU_SHIFT = 255, 8, 16, 24
+
+
 def _igemm_symbol(g, transposed, split, t):
     """Name of the kernel the C dispatch picks for this layer (what rocprofv3 reports), for the KernelTimer."""
-    h16 = t.dtype != torch.float32
-    code = g.kernel_family[(transposed, 1 if split else (2 if h16 else 0))]
-    fam, bn = code & 255, (code >> 8) & 255
-    if fam == 6:
-        return f"conv_vox0_kernel<{_TNAME[t.dtype]}>"
-    if fam == 14:
-        return f"conv_voxb_kernel<{_TNAME[t.dtype]}>"
-    if fam == 13:
-        return f"conv_voxg_kernel<{bn}, {_TNAME[t.dtype]}>"                # (forward and data gradient under one name)
-    if fam == 9:
-        return f"conv_c64_kernel<{_TNAME[t.dtype]}>"                 # (forward / data gradient (+ accumulate) under one name)
-    if fam == 10:
-        return f"conv_s2d_kernel<{_TNAME[t.dtype]}>"
-    if fam == 15:
-        return f"conv_s2g_kernel<{_TNAME[t.dtype]}>"
-    if fam == 12:
-        return f"conv_pw_kernel<{bn}, {_TNAME[t.dtype]}>"                # (forward and data gradient under one name)
-    if fam == 4:
-        return f"conv_stem_kernel<{g.kernel[1]}, {_TNAME[t.dtype]}>"
-    if fam == 5:
-        return f"conv_halo_rows_kernel<{_TNAME[t.dtype]}>"          # (store / accumulate variants under one name)
-    if fam == 3:
-        return f"conv_halo2d_kernel<{bn}, {_TNAME[t.dtype]}>"     # (both record variants under one name)
-    if fam == 2:
-        return f"conv_dma_kernel<{bn}, {_TNAME[t.dtype]}>"           # (pipeline depths 2 / 3 / 4 under one name)
-    return f"conv_igemm_kernel<{bn}, {2 if split else 1}, {_TNAME[t.dtype]}>"
+    code = g.kernel_family[(transposed, 1 if split else (2 if t.dtype != torch.float32 else 0))]
+    return CONV_FAMILIES[code & FAMILY_CODE_MASK].symbol.format(tile=(code >> FAMILY_TILE_SHIFT) & 255, nsplit=2 if split else 1,
+                                                                t=_TNAME[t.dtype], kh=g.kernel[1])
 
 
 def _f32(t):
@@ -202,9 +202,6 @@ def grad_scale(precision: str) -> float:
 def _conv_mode(x, lo) -> int:
     """Plan index of the conv entry points: 0 bf16 operands / fp32 storage, 1 bf16x3, 2 16-bit storage."""
     return 1 if lo is not None else (2 if x.dtype != torch.float32 else 0)
-
-
-_FRAG_FAMILIES = (13, 14, 15)        # kernel families that read the packed operand fragment-major: conv_voxg / conv_voxb / conv_s2g
 
 
 class ConvGeom:
@@ -261,11 +258,15 @@ class ConvGeom:
             self._plans[("rowpos", device)] = t
         return t
 
+    def family(self, transposed: bool, mode: int) -> ConvFamily:
+        """Row of CONV_FAMILIES for the kernel tri_conv_fwd / tri_conv_dgrad runs this layer on in plan `mode` (_conv_mode)."""
+        return CONV_FAMILIES[self.kernel_family[(transposed, mode)] & FAMILY_CODE_MASK]
+
     def brick(self, transposed: bool, mode: int) -> bool:
         """True when tri_conv_fwd / tri_conv_dgrad runs this layer on a kernel that walks the dense grid by the SITE MASK (the brick kernels
         of conv_vox.hip, conv_voxg_kernel on the coarse grids): such launches take the mask as row_mask (rows of inactive sites are then
         neither computed nor written), not a compact row list."""
-        return (self.kernel_family[(transposed, mode)] & 255) in (6, 7, 13, 14)
+        return self.family(transposed, mode).site_mask
 
     def packed_frag(self, transposed: bool, precision: str, storage=None) -> int:
         """1 when the kernel that consumes this layer's packed operand (forward / data gradient) reads it in MFMA-fragment-major order
@@ -273,24 +274,23 @@ class ConvGeom:
         activation storage the operand will meet (default: the precision mode's own)."""
         storage = storage or act_dtype(precision)
         mode = 1 if precision == "bf16x3" else (2 if storage != torch.float32 else 0)
-        return 1 if (self.kernel_family[(transposed, mode)] & 255) in _FRAG_FAMILIES else 0
+        return int(self.family(transposed, mode).frag)
 
     def check_packed(self, packed, transposed: bool, x):
         """The packed operand must be in the order this call's kernel reads (see pack_weight's `storage`)."""
-        need = 1 if (self.kernel_family[(transposed, _conv_mode(x, packed[1]))] & 255) in _FRAG_FAMILIES else 0
+        need = int(self.family(transposed, _conv_mode(x, packed[1])).frag)
         if getattr(packed[0], "tri_frag", 0) != need:
             raise RuntimeError("conv: the packed operand was ordered for another plan (row-major vs fragment-major): pack it with "
                                "pack_weight(..., storage=<dtype of the activations>)")
 
     def voxg_spu(self, transposed: bool, mode: int) -> int:
         """Samples per unit of conv_voxg_kernel for this layer (0: another kernel runs it)."""
-        code = self.kernel_family[(transposed, mode)]
-        return (code >> 24) & 127 if (code & 255) == 13 else 0
+        return (self.kernel_family[(transposed, mode)] >> FAMILY_SPU_SHIFT) & 127
 
     def splitk(self, transposed: bool, mode: int) -> bool:
         """True when tri_conv_fwd / tri_conv_dgrad runs this layer split-K in plan `mode` (_conv_mode): such launches take
         row_mask, not a compact row list."""
-        return bool(self.kernel_family[(transposed, mode)] >> 16 & 1)
+        return bool(self.kernel_family[(transposed, mode)] >> FAMILY_SPLITK_SHIFT & 1)
 
     def dgrad_bn_records(self, accumulate: bool, fmt: int) -> int:
         """Records tri_conv_dgrad_bn writes for this layer (0: its data-gradient kernel has no fused BatchNorm-backward sums), cached."""
