@@ -124,7 +124,31 @@ typedef enum TriConvFamily {
 #define TRI_FAMILY_SPU_SHIFT 24      /* bits 24..30 (VOXG): samples per unit = per BatchNorm record */
 /* the family tri_conv_fwd (transposed = 0) / tri_conv_dgrad (transposed = 1) dispatches for this layer and mode.  For profilers. */
 int tri_conv_kernel_family(const TriConvDesc* d, int transposed, int split3);
-/* same for tri_conv_wgrad: 0 conv_wgrad_kernel, 2 conv_wgrad_dma_kernel (taken when act_fmt != 0 and the layer qualifies) */
+/* Kernel families of the weight gradient (tri_conv_wgrad, tri_conv_wgrad_partial, tri_conv_stem_wgrad_bn).  Which calls each one takes,
+ * its slab layout and its grouping family are one table: wgrad_families[] in csrc/conv_wgrad.hip (Python: ops.WGRAD_FAMILIES). */
+typedef enum TriWgradFamily {
+    TRI_WGRAD_STAGED = 0,    /* conv_wgrad_kernel: register-staged im2col, every layer and mode */
+    TRI_WGRAD_DMA = 2,       /* conv_wgrad_dma_kernel: LDS-DMA staging (16-bit storage, 8 | Cin, whole channel tiles) */
+    TRI_WGRAD_STEM = 4,      /* conv_stem_wgrad_kernel: 4 stored input channels, stride 2, 64 outputs; dense calls, fused or not */
+    TRI_WGRAD_VOX0 = 6,      /* conv_vox0_wgrad_kernel: voxel level 0; only with the site mask as row_mask */
+    TRI_WGRAD_KROW = 7,      /* conv_wgrad_krow_kernel: resolution-keeping 3x3 layers, 64 | channels; dense calls */
+    TRI_WGRAD_C64 = 9        /* conv_wgrad_c64_kernel: 64 -> 64 channels 3x3 / 1 from 6 row tiles per compute unit on; dense calls */
+} TriWgradFamily;
+/* features of a weight-gradient call */
+#define TRI_WGRAD_MASK 1             /* row_mask */
+#define TRI_WGRAD_ROWS 2             /* compact row list (row_pos + row_count) */
+#define TRI_WGRAD_SPLIT3 4           /* 3-product split (fp32 storage) */
+#define TRI_WGRAD_BNF 8              /* tri_conv_stem_wgrad_bn: dOut formed from the BatchNorm-backward inputs; no other feature */
+/* the word tri_conv_wgrad_route returns: family | grouping family << 8 | tile rows << 12 | tile columns << 21 */
+#define TRI_WGRAD_ROUTE_CODE_MASK 255    /* bits 0..7: TriWgradFamily */
+#define TRI_WGRAD_ROUTE_GROUP_SHIFT 8    /* bits 8..11: the tri_conv_wgrad_group_info family whose launches this call may join (0: none) */
+#define TRI_WGRAD_ROUTE_ROWS_SHIFT 12    /* bits 12..20: output channels of the dW tile one workgroup forms */
+#define TRI_WGRAD_ROUTE_COLS_SHIFT 21    /* bits 21..30: its columns of K = (tap, channel); persistent kernels: the whole padded K */
+/* the kernel a call with these features runs on this layer in this storage format, or the negative TRI_ERR_* it is refused with (text via
+ * tri_last_error).  For profilers and timers. */
+int tri_conv_wgrad_route(const TriConvDesc* d, int act_fmt, int features);
+/* the layer's class, for callers that choose what to pass: 6 brick layer (conv_vox0_wgrad_kernel when the call passes the site mask),
+ * 7 kernel-row layer, 2 DMA-capable, 0 otherwise.  Not the kernel of a particular call: that is tri_conv_wgrad_route. */
 int tri_conv_wgrad_kernel_family(const TriConvDesc* d, int act_fmt);
 /* split-K scratch a small-M layer needs (0 = none): pass at least this many bytes to tri_conv_fwd / tri_conv_dgrad */
 size_t tri_conv_workspace(const TriConvDesc* d, int transposed);

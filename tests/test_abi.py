@@ -51,6 +51,23 @@ def test_host_helpers_without_gpu():
     assert not ds.wgrad_krow and ds.wgrad_group(2)[0] in (1, 2)                # 1x1 shortcuts stay on the im2col family
     assert l1.wgrad_group(0) == (0, 0, 0)                                      # fp32 storage: no grouped family
     import torch
+    # the kernel a weight-gradient call runs, one layer per row of wgrad_families[]: the symbol ops formats from tri_conv_wgrad_route
+    bf, hf, f32 = torch.bfloat16, torch.float16, torch.float32
+    c64 = ops.ConvGeom(192, (1, 56, 56), 64, 64, 64, (1, 3, 3), 1, (0, 1, 1), (576, 1, 9))          # 14 row tiles x 192 images >= 6 x 256
+    lin = ops.ConvGeom(512, (1, 1, 1), 512, 512, 512, (1, 1, 1), 1, (0, 0, 0), (512, 1, 1))
+    named = [(g2, 1, 0, bf, False, "conv_stem_wgrad_kernel<7, bf16>"),
+             (c64, 1, 0, bf, False, "conv_wgrad_c64_kernel<bf16>"),
+             (l1, 2, 0, hf, False, "conv_wgrad_krow_kernel<64, f16>"),
+             (ds, 1, 0, bf, False, "conv_wgrad_dma_kernel<64, 128, bf16>"),
+             (lin, 0, ops.WGRAD_SPLIT3, f32, True, "conv_wgrad_kernel<128, 128, 2, float>"),
+             (g, 1, ops.WGRAD_MASK, bf, False, "conv_vox0_wgrad_kernel<bf16>")]
+    for geom, fmt, feat, dtype, split, want in named:
+        assert ops._wgrad_symbol(geom, geom.wgrad_route(fmt, feat), dtype, split) == want
+    assert sorted(ops.WGRAD_FAMILIES) == sorted({geom.wgrad_route(fmt, feat) & 255 for geom, fmt, feat, _, _, _ in named})
+    assert g.wgrad_brick and not g.wgrad_krow and not c64.wgrad_krow and not c64.wgrad_brick
+    assert c64.wgrad_route(1, ops.WGRAD_MASK) & 255 == 2 and g.wgrad_route(1, 0) & 255 == 0       # the other calls of those layers: im2col kernels
+    with pytest.raises(RuntimeError, match="3-product split"):
+        l1.wgrad_route(1, ops.WGRAD_SPLIT3)
     with pytest.raises(RuntimeError, match="no CPU"):
         _C.ptr(torch.zeros(3))
 

@@ -2,8 +2,9 @@
 
 Which kernel family runs a tri_conv_fwd / tri_conv_dgrad / weight-gradient call, how many BatchNorm records it writes and how much
 scratch it needs are host decisions: the planner answers them without a GPU (256 compute units assumed, the MI355X's).  The table
-was recorded before the routing code was rewritten around one family table; every cell must come out the same, by default and
-under every A/B switch that shows in a plan query.  TRICOLO_S2D_TY, TRICOLO_HALO_PROD and TRICOLO_HALO_XCG act at launch time only
+was recorded before the routing code was rewritten around one family table (route_table: before the weight gradient's was, through a literal
+copy of its if-chain); every cell must come out the same, by default and under every A/B switch that shows in
+a plan query.  TRICOLO_S2D_TY, TRICOLO_HALO_PROD and TRICOLO_HALO_XCG act at launch time only
 and stay with their GPU tests.
 
 Where the GPU suite reaches each outcome of each row of conv_families[] (csrc/conv_igemm.hip), bit for bit against torch on integer
@@ -38,7 +39,8 @@ gen = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(gen)
 
 FWD_DGRAD_FAMILIES = {0, 2, 3, 4, 5, 6, 9, 10, 12, 13, 14, 15}
-WGRAD_FAMILIES = {0, 2, 6, 7}
+WGRAD_FAMILIES = {0, 2, 6, 7}                                   # tri_conv_wgrad_kernel_family: the layer's class
+WGRAD_ROUTE_FAMILIES = {0, 2, 4, 6, 7, 9}                       # tri_conv_wgrad_route: the kernel of a call, every row of wgrad_families[]
 GROUP_FAMILIES = {0, 1, 2, 4, 5, 7}
 
 
@@ -74,8 +76,15 @@ def test_recorded_table_covers_every_family(rec):
     assert set(_col(rec, "wgrad_family_").ravel().tolist()) == WGRAD_FAMILIES
     rc = _col(rec, "wgrad_group_rc_")
     assert set(_col(rec, "wgrad_group_family_")[rc == 0].tolist()) == GROUP_FAMILIES
+    assert list(rec["route_columns"]) == gen.ROUTE_COLUMNS and rec["route_table"].shape == (len(rec["desc"]), len(gen.ROUTE_COLUMNS))
+    route = {k: rec["route_table"][:, [str(c).endswith(k) for c in rec["route_columns"]]] for k in ("dense", "mask", "rows")}
+    codes = {k: set((v[v >= 0] & 255).tolist()) for k, v in route.items()}
+    assert codes["dense"] | codes["mask"] | codes["rows"] == WGRAD_ROUTE_FAMILIES
+    assert {4, 9} <= codes["dense"] and not {4, 9} & (codes["mask"] | codes["rows"])    # stem and c64: dense calls only
+    assert 6 in codes["mask"] and (rec["route_table"] < 0).any()                        # the brick kernel; refused calls
     assert (_col(rec, "dgrad_bn_records_") > 0).any() and (_col(rec, "workspace_") > 0).any()
     assert len(set(rec["switch_sha256"].tolist())) > 1 and gen.table_sha256(rec["table"]) not in set(rec["switch_sha256"].tolist())
+    assert gen.table_sha256(np.hstack([rec["table"], rec["route_table"]])) not in set(rec["switch_sha256_all"].tolist())
 
 
 def test_default_table_reproduces(rec):
@@ -86,14 +95,22 @@ def test_default_table_reproduces(rec):
     for i, c in bad[:20]:
         print(f"desc {rec['desc'][i].tolist()} column {rec['columns'][c]}: recorded {want[i, c]}, computed {got[i, c]}")
     assert len(bad) == 0, f"{len(bad)} cells of the plan table changed"
+    got, want = gen.compute_routes(rec["desc"]), rec["route_table"]
+    bad = np.argwhere(got != want)
+    for i, c in bad[:20]:
+        print(f"desc {rec['desc'][i].tolist()} column {rec['route_columns'][c]}: recorded {want[i, c]}, computed {got[i, c]}")
+    assert len(bad) == 0, f"{len(bad)} cells of the weight-gradient route table changed"
 
 
 @pytest.mark.parametrize("switch", gen.SWITCHES)
 def test_switch_table_reproduces(rec, switch):
-    """One A/B switch, set in a fresh child process (the library reads each switch once): the whole table's SHA-256."""
+    """One A/B switch, set in a fresh child process (the library reads each switch once): the table's SHA-256, and that of the table
+    and the weight-gradient route table side by side."""
     _skip_unless_reference_machine()
     want = dict(zip(rec["switches"].tolist(), rec["switch_sha256"].tolist()))[switch]
     assert gen.switch_sha256(switch) == want, f"the plan table under {switch} changed"
+    want = dict(zip(rec["switches"].tolist(), rec["switch_sha256_all"].tolist()))[switch]
+    assert gen.switch_sha256(switch, all_columns=True) == want, f"the weight-gradient route table under {switch} changed"
 
 
 def test_python_family_table_matches_recorded_codes(rec):

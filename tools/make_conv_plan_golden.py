@@ -1,9 +1,9 @@
 """Generate tests/golden/conv_plan.npz: what the conv planner answers for a sweep of layer shapes.  TEST INFRASTRUCTURE.
 
     python tools/make_conv_plan_golden.py            # record the table of the library that is built now
-    python tools/make_conv_plan_golden.py --sha256   # print the SHA-256 of the table under the current environment
+    python tools/make_conv_plan_golden.py --sha256   # print the SHA-256s of the table under the current environment
 
-The planner (conv_make_plan / wgrad_plan and the queries on top of them) answers without a GPU: the compute-unit count falls back
+The planner (conv_make_plan / wgrad_make_plan and the queries on top of them) answers without a GPU: the compute-unit count falls back
 to 256, the MI355X's.  The file pins those answers so that a change to the routing code shows as a changed cell, not as a slower or
 wrong layer somewhere else.  It holds
 
@@ -12,10 +12,14 @@ wrong layer somewhere else.  It holds
     table           int64 [N, C]    every query's answer with no TRICOLO_* variable set
     switches        str   [S]       "NAME=value" A/B settings (SWITCHES below)
     switch_sha256   str   [S]       SHA-256 of the table recomputed with that one variable set
+    route_columns   str   [R]       name of each column of the weight-gradient route table (ROUTE_COLUMNS below)
+    route_table     int64 [N, R]    tri_conv_wgrad_route's answers with no TRICOLO_* variable set
+    switch_sha256_all str [S]       SHA-256 of table and route_table side by side, recomputed with that one variable set
 
 tests/test_conv_plan.py recomputes all of it.  Re-record only when a plan is MEANT to change, and say so in the commit.
 """
 import argparse
+import functools
 import hashlib
 import os
 import subprocess
@@ -39,6 +43,12 @@ COLUMNS = ([f"family_{'dgrad' if tr else 'fwd'}_m{m}" for tr in (0, 1) for m in 
            [f"dgrad_bn_records_acc{a}_fmt{f}" for a in (0, 1) for f in (0, 1, 2)] +
            ["wgrad_workspace", "plan_bytes", "wgrad_family_fmt0", "wgrad_family_fmt1"] +
            [f"wgrad_group_{k}_fmt{f}" for f in (0, 1, 2) for k in ("rc", "family", "tiles", "steps")])
+# tri_conv_wgrad_route per storage format and call features (ops.WGRAD_MASK / WGRAD_ROWS); the last three: the 3-product split on fp32
+# storage.  A table of their own (route_table), recorded later than `table`: switch_sha256 stays the hash of `table` alone,
+# switch_sha256_all is the hash of the two side by side.
+ROUTE_FEATURES = (("dense", 0), ("mask", 1), ("rows", 2))
+ROUTE_COLUMNS = ([f"wgrad_route_fmt{f}_{k}" for f in (0, 1, 2) for k, _ in ROUTE_FEATURES] +
+                 [f"wgrad_route_fmt0_split3_{k}" for k, _ in ROUTE_FEATURES])
 
 
 def _desc(B, grid, cin_stored, cout, kernel, stride, pad):
@@ -98,36 +108,59 @@ def compute_table(desc):
     return table
 
 
+def compute_routes(desc):
+    """int64 [N, len(ROUTE_COLUMNS)]: tri_conv_wgrad_route's word (negative: the call is refused), under the environment of this process."""
+    import ctypes as C
+
+    from tricolo_amd import _C
+    lib = _C.lib()
+    table = np.zeros((len(desc), len(ROUTE_COLUMNS)), dtype=np.int64)
+    for i, row in enumerate(desc):
+        d = C.byref(_C.make_desc(*(int(v) for v in row)))
+        table[i] = ([lib.tri_conv_wgrad_route(d, f, feat) for f in (0, 1, 2) for _, feat in ROUTE_FEATURES] +
+                    [lib.tri_conv_wgrad_route(d, 0, feat | 4) for _, feat in ROUTE_FEATURES])
+    return table
+
+
 def table_sha256(table):
     return hashlib.sha256(np.ascontiguousarray(table, dtype=np.int64).tobytes()).hexdigest()
 
 
-def switch_sha256(switch):
-    """SHA-256 of the table in a fresh process with `switch` ("NAME=value") as its only TRICOLO_* variable."""
+def switch_sha256(switch, all_columns=False):
+    """SHA-256 of the table (or of table and route table side by side) in a fresh process with `switch` ("NAME=value") as its
+    only TRICOLO_* variable."""
+    return _switch_sha256s(switch)[1 if all_columns else 0]
+
+
+@functools.lru_cache(maxsize=None)
+def _switch_sha256s(switch):
     env = {k: v for k, v in os.environ.items() if not k.startswith("TRICOLO_")}
     name, value = switch.split("=", 1)
     env[name] = value
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--sha256"], env=env, check=True, capture_output=True, text=True)
-    return out.stdout.split()[-1]
+    return tuple(out.stdout.split()[-2:])
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--sha256", action="store_true", help="print the table's SHA-256 under the current environment and exit")
+    ap.add_argument("--sha256", action="store_true", help="print the table's SHA-256s (table; table and route table) under the current environment and exit")
     args = ap.parse_args()
     desc = descriptors()
     if args.sha256:
-        print(table_sha256(compute_table(desc)))
+        table = compute_table(desc)
+        print(table_sha256(table), table_sha256(np.hstack([table, compute_routes(desc)])))
         return
     if any(k.startswith("TRICOLO_") for k in os.environ):
         sys.exit("unset every TRICOLO_* variable before recording the default table")
     table = compute_table(desc)
     default = table_sha256(table)
-    shas = [switch_sha256(s) for s in SWITCHES]
-    same = [s for s, h in zip(SWITCHES, shas) if h == default]
+    shas = [_switch_sha256s(s) for s in SWITCHES]
+    same = [s for s, h in zip(SWITCHES, shas) if h[0] == default]
     if same:
         sys.exit(f"switches that do not change the table (drop them or extend the sweep): {same}")
-    np.savez_compressed(OUT, desc=desc, columns=np.asarray(COLUMNS), table=table, switches=np.asarray(SWITCHES), switch_sha256=np.asarray(shas))
+    np.savez_compressed(OUT, desc=desc, columns=np.asarray(COLUMNS), table=table, switches=np.asarray(SWITCHES),
+                        switch_sha256=np.asarray([h[0] for h in shas]), route_columns=np.asarray(ROUTE_COLUMNS),
+                        route_table=compute_routes(desc), switch_sha256_all=np.asarray([h[1] for h in shas]))
     fams = sorted(set((table[:, :6] & 255).ravel().tolist()))
     print(f"{len(desc)} descriptors x {len(COLUMNS)} columns -> {OUT} ({os.path.getsize(OUT)} bytes); conv families {fams}")
 

@@ -67,6 +67,7 @@ SIGNATURES = {
     "tri_conv_workspace": (Z, [DP, I]),
     "tri_conv_kernel_family": (I, [DP, I, I]),
     "tri_conv_wgrad_kernel_family": (I, [DP, I]),
+    "tri_conv_wgrad_route": (I, [DP, I, I]),
     "tri_conv_fwd": (I, [DP, P, P, P, P, P, P, I, I, P, I, P, Z, P, P, P]),
     "tri_conv_dgrad": (I, [DP, P, P, P, P, P, I, I, P, Z, P, P, P]),
     "tri_conv_dgrad_bn_records": (I, [DP, I, I]),

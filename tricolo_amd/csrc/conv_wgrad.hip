@@ -1413,6 +1413,55 @@ extern "C" int tri_conv_plan_build(const TriConvDesc* d, void* plan, void* strea
     return tri_check_launch("tri_conv_plan_build");
 }
 
+// ------------------------------------------------------------------------------------------- kernel families: one table
+// Which kernel runs a weight-gradient call is decided here and nowhere else, as conv_families[] / conv_make_plan (conv_igemm.hip) decide
+// it for tri_conv_fwd / tri_conv_dgrad: wgrad_families[] has one row per family, tried in table order by wgrad_make_plan (precedence = row
+// order), and tri_conv_wgrad_partial, tri_conv_stem_wgrad_bn, the workspace / family / route / group queries and the grouped launch read
+// the plan it returns.  A new family is one row: its planner and its launch adapter; ops.WGRAD_FAMILIES names its kernel for Python.
+
+// features of a call, as the rows name them (TRI_WGRAD_* in the header)
+enum : unsigned { WF_MASK = TRI_WGRAD_MASK, WF_ROWS = TRI_WGRAD_ROWS, WF_SPLIT3 = TRI_WGRAD_SPLIT3, WF_BNF = TRI_WGRAD_BNF };
+
+struct WgradFamily;
+struct WgradPlan {
+    const WgradFamily* family;        // row of wgrad_families[] that runs the call; NULL: refused before any row was asked
+    int rc;                           // 0, or the TRI_ERR_* this call is refused with ...
+    const char* refusal;              // ... and the text for tri_last_error
+    union { StemWgradArgs stem; C64WgradArgs c64; TriVox0Geom vox0; KrowArgs krow; } g;   // the family's geometry; pointers are the launch's to fill
+    int BI, BJ;                       // dW tile of one workgroup: output channels x columns of K
+    int dma;                          // wgrad_tile_plan: the LDS-DMA kernel takes the tiles
+    int tiles, steps;                 // workgroups per position split; steps of the contraction (64 positions; register-staged: 32)
+    int splits, steps_per_split;      // position splits = fp32 slabs [Cout][Kpad] (persistent kernels: one per workgroup)
+    int Kpad;
+    size_t slab_bytes;                // splits x Cout x Kpad fp32: what the call needs of its workspace
+    int group, group_tiles;           // grouping family of the layer (tri_conv_wgrad_group_info; 0: none) and the tiles one job of it counts
+};
+struct WgradCall {                    // what a call passes besides the descriptor and the storage format
+    const void *in, *dout;
+    const uint8_t* row_mask;
+    const void* plan;
+    const int *row_pos, *row_count;
+    float* slab;
+    int split3;
+    const void* y; const uint8_t* arg; const void* dpool; const float *c1, *c2, *c3, *rs, *rb;    // WF_BNF (tri_conv_stem_wgrad_bn)
+};
+struct WgradFamily {
+    TriWgradFamily code;
+    const char* kernel;               // name stem of its kernel
+    int (*plan)(const TriConvDesc* d, int act_fmt, unsigned feat, WgradPlan* pl);   // 0: not this layer; 1: takes it (plan filled); < 0: takes
+                                      // it and refuses the call (plan filled as far as the workspace query needs it, pl->refusal set)
+    unsigned skips;                   // features it cannot take: such a call goes on to the next row
+    unsigned needs;                   // features it cannot do without
+    bool ch4;                         // from this row on, channels must be multiples of 4 (TRI_ERR_ARG)
+    // slab layout for the reduce: [splits][Cout][Kpad] in k = (tap, stored channel) order, kernel rows padded to 1 << kw_shift taps
+    // (0: unpadded) - everything else follows from the descriptor (wgrad_fill_pending); row_form: the reduce may take its row form
+    int kw_shift;
+    bool row_form;
+    int (*launch)(const TriConvDesc* d, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t stream);
+    // jobs of one grouping family in one launch: cuts every job into its splits, checks its workspace, fills pending[i]; NULL: not groupable
+    int (*launch_group)(const TriWgradJob* jobs, const WgradPlan* pl, int n, int act_fmt, TriWgradReduce* pending, hipStream_t stream);
+};
+
 #ifndef WGRAD_TARGET_BLOCKS
 #define WGRAD_TARGET_BLOCKS 768
 #endif
@@ -1426,59 +1475,92 @@ static int wgrad_target_blocks() {                             // tuning aid: TR
 
 static bool wgrad_dma_disabled() { return tri_env_is("TRICOLO_NO_DMA", '1'); }
 
-// act_fmt != 0 asks for the plan of the bf16-storage call; *dma is set when that call runs the LDS-DMA kernel
-// (64-position steps), and steps_per_split is then in 64-position units.
-static void wgrad_plan(const TriConvDesc* d, int act_fmt, int rowlist, int* BI, int* BJ_out, int* tiles, int* splits, int* steps_per_split,
-                       int* Kpad, int* dma) {
+// tile and split plan of the im2col kernels; act_fmt != 0 asks for the plan of the 16-bit-storage call; pl->dma is set when that call
+// runs the LDS-DMA kernel (64-position steps), and steps / steps_per_split are then in 64-position units.
+static void wgrad_tile_plan(const TriConvDesc* d, int act_fmt, int rowlist, WgradPlan* pl) {
     int ntaps = d->KD * d->KH * d->KW;
-    *Kpad = (ntaps * d->Cin + 31) / 32 * 32;
-    *BI = (d->Cout % 128 == 0 && *Kpad >= 128) ? 128 : 64;
+    pl->Kpad = (ntaps * d->Cin + 31) / 32 * 32;
+    pl->BI = (d->Cout % 128 == 0 && pl->Kpad >= 128) ? 128 : 64;
     // 64-row tiles: K <= 256 is one 256-wide column tile of the register-staged kernel - unless the LDS-DMA kernel can take the
     // layer (16-bit storage, 8-channel pieces): then 128-wide tiles (layer2's 1x1/2 shortcut: K = 64, 39 -> ~8 us at the bench shape)
     const bool dma64 = act_fmt && d->Cin % 8 == 0 && d->Cout % 64 == 0 && !wgrad_dma_disabled();
-    int BJ = *BI == 128 ? 128 : ((*Kpad <= 256 && !dma64) ? 256 : 128);
-    *BJ_out = BJ;
-    int it = (d->Cout + *BI - 1) / *BI, jt = (*Kpad + BJ - 1) / BJ;
-    *tiles = it * jt;
+    const int BI = pl->BI, BJ = BI == 128 ? 128 : ((pl->Kpad <= 256 && !dma64) ? 256 : 128);
+    pl->BJ = BJ;
+    int it = (d->Cout + BI - 1) / BI, jt = (pl->Kpad + BJ - 1) / BJ;
+    pl->tiles = it * jt;
     long M = (long)d->B * d->OD * d->OH * d->OW;
-    *dma = (act_fmt && BJ == 128 && d->Cin % 8 == 0 && d->Cout % *BI == 0 && !wgrad_dma_disabled()) ? 1 : 0;
-    const int unit = *dma ? 64 : 32;
-    int steps = (int)((M + unit - 1) / unit);
+    const int dma = pl->dma = (act_fmt && BJ == 128 && d->Cin % 8 == 0 && d->Cout % BI == 0 && !wgrad_dma_disabled()) ? 1 : 0;
+    const int unit = dma ? 64 : 32;
+    int steps = pl->steps = (int)((M + unit - 1) / unit);
     int max_by_steps = steps / 4 > 0 ? steps / 4 : 1;           // at least 4 k-steps per split
     int s, cap;
-    if (act_fmt && *BI == 128 && wgrad_target_blocks() == WGRAD_TARGET_BLOCKS) {
+    if (act_fmt && BI == 128 && wgrad_target_blocks() == WGRAD_TARGET_BLOCKS) {
         // 128x128 bf16-storage tiles (64 KiB of operand stages -> 2 workgroups per CU): at most ONE resident round of
         // workgroups, and not quite full (7/8 of the 512 slots).  More splits only add slab traffic (splits x Cout x K
         // fp32 written + re-read by the reduce) and a second, partly empty round; measured sweep in profiles/r1/README.md.
-        const int fixed = (*dma ? 2 * 64 * (*BI * 2 + BJ * 2) : 2 * (32 * *BI * 2 + 32 * BJ * 2)) + 512;
-        cap = (163840 / 2 - fixed) / ((*dma ? 512 : 256) * (rowlist ? 3 : 2) / 2);   // gather plan: 8 B per position of the split (+ 4 B: row list)
+        const int fixed = (dma ? 2 * 64 * (BI * 2 + BJ * 2) : 2 * (32 * BI * 2 + 32 * BJ * 2)) + 512;
+        cap = (163840 / 2 - fixed) / ((dma ? 512 : 256) * (rowlist ? 3 : 2) / 2);   // gather plan: 8 B per position of the split (+ 4 B: row list)
         if (cap > 96) cap = 96;
-        s = 448 / *tiles;
+        s = 448 / pl->tiles;
     } else {
-        cap = *dma ? 60 : 96;
+        cap = dma ? 60 : 96;
         // register-staged kernels (fp32 storage, 4-channel layers): ~3 workgroups per CU; 64-row DMA tiles: 448 (same sweep)
-        const int target = (*dma && wgrad_target_blocks() == WGRAD_TARGET_BLOCKS) ? 448 : wgrad_target_blocks();
-        s = (target + *tiles - 1) / *tiles;
+        const int target = (dma && wgrad_target_blocks() == WGRAD_TARGET_BLOCKS) ? 448 : wgrad_target_blocks();
+        s = (target + pl->tiles - 1) / pl->tiles;
     }
     if (s > max_by_steps) s = max_by_steps;
     if (s < 1) s = 1;
     if (s > 1024) s = 1024;
-    *steps_per_split = (steps + s - 1) / s;
-    if (*steps_per_split > cap) *steps_per_split = cap;
-    *splits = (steps + *steps_per_split - 1) / *steps_per_split;
+    pl->steps_per_split = (steps + s - 1) / s;
+    if (pl->steps_per_split > cap) pl->steps_per_split = cap;
+    pl->splits = (steps + pl->steps_per_split - 1) / pl->steps_per_split;
 }
+// TRICOLO_WGRAD_WIDE=1: grouped jobs with Cout % 256 == 0 take 256 x 128 tiles (512-thread workgroups, one per CU).  Measured at the
+// bench shape: the launches themselves 0.286 -> 0.266 ms per step, the STEP 3.08 -> 3.12 ms (a 104 KB workgroup per CU leaves the
+// other towers' kernels no room beside it) - so it stays an experiment switch (profiles/r3/NOTES_wgrad.md).
+static bool wgrad_wide_tiles() {
+    static int v = -1;
+    if (v < 0) v = 0;
+    return v == 1;
+}
+// conv_wgrad_dma_kernel (want_dma) / conv_wgrad_kernel: whichever of the two the tile plan names takes every layer
+static int plan_tiled(const TriConvDesc* d, int act_fmt, unsigned feat, bool want_dma, WgradPlan* pl) {
+    wgrad_tile_plan(d, act_fmt, (feat & WF_ROWS) != 0, pl);
+    if ((pl->dma != 0) != want_dma) return 0;
+    if (pl->dma) {
+        // grouping family: 1 = conv_wgrad_dma_kernel<128,128>, 2 = <64,128>, 3 = <256,128> (512-thread workgroups, TRICOLO_WGRAD_WIDE)
+        pl->group = pl->BI == 128 ? 1 : 2;
+        pl->group_tiles = pl->tiles;
+        if (pl->BI == 128 && d->Cout % 256 == 0 && wgrad_wide_tiles()) {
+            pl->group = 3;
+            pl->group_tiles = (d->Cout / 256) * ((pl->Kpad + 127) / 128);
+        }
+    }
+    if (d->KD * d->KH * d->KW > 64) { pl->refusal = "wgrad: more than 64 taps unsupported"; return TRI_ERR_UNSUPPORTED; }
+    if (act_fmt && (feat & WF_SPLIT3)) { pl->refusal = "wgrad: 16-bit activation storage takes single operands (no 3-product split)"; return TRI_ERR_ARG; }
+    if ((size_t)d->B * d->ID * d->IH * d->IW * d->Cin * (act_fmt ? 2 : 4) >= ((size_t)1 << 31)) {
+        pl->refusal = "wgrad: input tensor >= 2 GiB (32-bit buffer offsets)"; return TRI_ERR_UNSUPPORTED;
+    }
+    if (pl->dma && (size_t)d->B * d->OD * d->OH * d->OW * d->Cout * 2 >= ((size_t)1 << 31)) {
+        pl->refusal = "wgrad: dOut tensor >= 2 GiB (32-bit buffer offsets)"; return TRI_ERR_UNSUPPORTED;
+    }
+    return 1;
+}
+static int plan_dma(const TriConvDesc* d, int act_fmt, unsigned feat, WgradPlan* pl) { return plan_tiled(d, act_fmt, feat, true, pl); }
+static int plan_staged(const TriConvDesc* d, int act_fmt, unsigned feat, WgradPlan* pl) { return plan_tiled(d, act_fmt, feat, false, pl); }
 
 int tri_internal_num_cus();                                         // conv_igemm.hip
 static bool stem_wgrad_disabled() { return tri_env_is("TRICOLO_NO_STEM_WGRAD", '1'); }
-// geometry of conv_stem_wgrad_kernel; false when the layer does not qualify (it then runs conv_wgrad_kernel)
-static bool stem_wgrad_geometry(const TriConvDesc* d, int act_fmt, StemWgradArgs* g, int* grid) {
-    if (!act_fmt || stem_wgrad_disabled()) return false;
-    if (d->KD != 1 || d->ID != 1 || d->pad_d != 0 || d->Cin != 4 || d->stride != 2 || d->Cout != 64) return false;
-    if ((d->KH != 3 && d->KH != 5 && d->KH != 7) || d->KW > 8 || d->OW % 16 || d->IW % 2 || d->OW > 128) return false;
-    if (d->pad_w < 0 || d->pad_h < 0 || d->IW + d->pad_w > 2 * d->OW + 6) return false;
-    if ((long)d->B * d->IH * d->IW * 8 >= ((long)1 << 31) || (long)d->B * d->OH * d->OW * 128 >= ((long)1 << 31)) return false;
+// conv_stem_wgrad_kernel: persistent workgroups, one slab [64][KH * 32] each
+static int plan_stem(const TriConvDesc* d, int act_fmt, unsigned, WgradPlan* pl) {
+    StemWgradArgs* g = &pl->g.stem;
+    if (!act_fmt || stem_wgrad_disabled()) return 0;
+    if (d->KD != 1 || d->ID != 1 || d->pad_d != 0 || d->Cin != 4 || d->stride != 2 || d->Cout != 64) return 0;
+    if ((d->KH != 3 && d->KH != 5 && d->KH != 7) || d->KW > 8 || d->OW % 16 || d->IW % 2 || d->OW > 128) return 0;
+    if (d->pad_w < 0 || d->pad_h < 0 || d->IW + d->pad_w > 2 * d->OW + 6) return 0;
+    if ((long)d->B * d->IH * d->IW * 8 >= ((long)1 << 31) || (long)d->B * d->OH * d->OW * 128 >= ((long)1 << 31)) return 0;
     int TH = d->OH >= 2 ? 2 : 1;
-    if ((TH * d->OW) % 32) return false;
+    if ((TH * d->OW) % 32) return 0;
     g->B = d->B; g->IH = d->IH; g->IW = d->IW; g->OH = d->OH; g->OW = d->OW; g->KW = d->KW; g->ph = d->pad_h; g->pw = d->pad_w;
     g->TH = TH;
     g->slab_rows = (TH - 1) * 2 + d->KH;
@@ -1486,10 +1568,11 @@ static bool stem_wgrad_geometry(const TriConvDesc* d, int act_fmt, StemWgradArgs
     g->groups = TH * d->OW / 32;
     g->tiles_per_img = (d->OH + TH - 1) / TH;
     g->ntiles = d->B * g->tiles_per_img;
-    if (g->groups > STEM_WG_MAXG || g->slab_rows * (d->IW / 2) > 256 * 4) return false;
+    if (g->groups > STEM_WG_MAXG || g->slab_rows * (d->IW / 2) > 256 * 4) return 0;
     const int slots = tri_internal_num_cus() * 2;
-    *grid = g->ntiles < slots ? g->ntiles : slots;
-    return true;
+    pl->splits = g->ntiles < slots ? g->ntiles : slots;
+    pl->BI = 64; pl->BJ = pl->Kpad = d->KH * 32;
+    return 1;
 }
 
 static bool krow_wgrad_disabled() { return tri_env_is("TRICOLO_NO_KROW_WGRAD", '1'); }
@@ -1498,21 +1581,22 @@ static bool c64_wgrad_disabled() {
     if (v < 0) v = 0;
     return v == 1;
 }
-// geometry of conv_wgrad_c64_kernel; false when the layer does not qualify
-static bool c64_wgrad_geometry(const TriConvDesc* d, int act_fmt, C64WgradArgs* g, int* grid) {
-    if (!act_fmt || c64_wgrad_disabled()) return false;
-    if (d->KD != 1 || d->ID != 1 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_d != 0 || d->pad_h != 1 || d->pad_w != 1) return false;
-    if (d->Cin != 64 || d->Cout != 64 || d->OH != d->IH || d->OW != d->IW) return false;
-    if ((long)d->B * d->IH * d->IW * 128 >= ((long)1 << 31)) return false;
+// conv_wgrad_c64_kernel: persistent workgroups, one slab [64][576] each
+static int plan_c64(const TriConvDesc* d, int act_fmt, unsigned, WgradPlan* pl) {
+    C64WgradArgs* g = &pl->g.c64;
+    if (!act_fmt || c64_wgrad_disabled()) return 0;
+    if (d->KD != 1 || d->ID != 1 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_d != 0 || d->pad_h != 1 || d->pad_w != 1) return 0;
+    if (d->Cin != 64 || d->Cout != 64 || d->OH != d->IH || d->OW != d->IW) return 0;
+    if ((long)d->B * d->IH * d->IW * 128 >= ((long)1 << 31)) return 0;
     const int H = d->IH, W = d->IW;
     // round 4: widths that divide 64 go to conv_wgrad_krow_kernel<64> (config 3, 32-wide layer1: 3.975 against 4.032 ms per step); this
     // kernel keeps the widths whose 64-position steps would carry a dead tail there (56-wide layer1 of 12 x 224^2: 20.39 against 20.66 ms)
-    if (64 % W == 0 && W >= 4 && !krow_wgrad_disabled()) return false;
+    if (64 % W == 0 && W >= 4 && !krow_wgrad_disabled()) return 0;
     int TR = 0;
     for (int tr = 1; tr <= H; ++tr)                                  // most positions per tile: whole rows of one image, multiple of 32, <= 256
         if (H % tr == 0 && (tr * W) % 32 == 0 && tr * W <= 32 * C64_MAXG) TR = tr;
-    if (!TR) return false;
-    if ((size_t)TR * W * 128 + (size_t)(TR + 2) * (W + 2) * 128 > 78 * 1024) return false;      // two workgroups per CU
+    if (!TR) return 0;
+    if ((size_t)TR * W * 128 + (size_t)(TR + 2) * (W + 2) * 128 > 78 * 1024) return 0;      // two workgroups per CU
     g->B = d->B; g->H = H; g->W = W; g->TR = TR; g->groups = TR * W / 32;
     g->tiles_per_img = H / TR; g->ntiles = d->B * g->tiles_per_img;
     // 256-512 per-workgroup slabs of 147 KB.  Round 2: paid from ~6 row tiles per CU on (per-GPU batch 64 of 6 x 128^2 5.03 -> 4.87 ms,
@@ -1523,42 +1607,22 @@ static bool c64_wgrad_geometry(const TriConvDesc* d, int act_fmt, C64WgradArgs* 
     // 512 workgroups x 147 KB of slabs per layer are what it costs there
     static int min_per_cu = -1;
     if (min_per_cu < 0) min_per_cu = 6;
-    if (g->ntiles < min_per_cu * tri_internal_num_cus()) return false;
+    if (g->ntiles < min_per_cu * tri_internal_num_cus()) return 0;
     static int per_cu = -1;
     if (per_cu < 0) per_cu = 2;
-    *grid = tri_internal_num_cus() * (per_cu < 1 ? 1 : per_cu);
-    if (*grid > g->ntiles) *grid = g->ntiles;
-    return true;
+    pl->splits = tri_internal_num_cus() * (per_cu < 1 ? 1 : per_cu);
+    if (pl->splits > g->ntiles) pl->splits = g->ntiles;
+    pl->BI = 64; pl->BJ = pl->Kpad = 576;
+    return 1;
 }
 
-// geometry of conv_wgrad_krow_kernel (everything but pointers and the split plan); false when the layer does not qualify.
-// *co_t = 128 / 64 (rows per workgroup tile), *tiles = workgroups per position split, *steps = 64-position steps
-static bool krow_geometry(const TriConvDesc* d, int act_fmt, KrowArgs* g, int* co_t, int* tiles, int* steps) {
-    if (!act_fmt || krow_wgrad_disabled()) return false;
-    if (d->KD != 1 || d->ID != 1 || d->KH != 3 || d->KW != 3 || (d->stride != 1 && d->stride != 2) || d->pad_d != 0 || d->pad_h != 1 || d->pad_w != 1) return false;
-    if (d->Cin % 64 || d->Cout % 64 || d->OH * d->stride != d->IH || d->OW * d->stride != d->IW) return false;
-    const int W = d->OW, H = d->OH;
-    if (W < 4 || W > 64) return false;
-    const size_t in_bytes = (size_t)d->B * d->IH * d->IW * d->Cin * 2, dout_bytes = (size_t)d->B * H * W * d->Cout * 2;
-    if (in_bytes >= ((size_t)1 << 31) || dout_bytes >= ((size_t)1 << 31)) return false;
-    KrowArgs a{};
-    a.in_bytes = (unsigned)in_bytes; a.dout_bytes = (unsigned)dout_bytes;
-    a.NH = d->B * H; a.H = H; a.W = W; a.Cin = d->Cin; a.Cout = d->Cout; a.Kpad = 9 * d->Cin;
-    a.Hin = d->IH; a.Win = d->IW;
-    a.rps = 64 / W;
-    a.P = d->stride == 1 ? ((W + 3) & ~1) : 2 * W + 2;               // even pitch: the bank half of a pixel is the parity of its index
-    if (a.rps * a.P > (d->stride == 1 ? KROW_SLAB_PX : KROW_SLAB_PX_S2)) return false;
-    a.npiece = (a.rps * a.P + 7) / 8;
-    a.nsteps = (a.NH + a.rps - 1) / a.rps;
-    a.ci_chunks = d->Cin / 64;
-    *co_t = d->Cout % 128 == 0 ? 128 : 64;
-    a.ntiles = (d->Cout / *co_t) * 3 * a.ci_chunks;
-    a.dH = make_fastdiv(H); a.dP = make_fastdiv(a.P); a.dW = make_fastdiv(W);
-    *g = a;
-    *tiles = a.ntiles;
-    *steps = a.nsteps;
-    return true;
+// conv_vox0_wgrad_kernel (conv_vox.hip): voxel level 0 over a site mask; persistent workgroups, one slab [32][144] each
+static int plan_vox0(const TriConvDesc* d, int act_fmt, unsigned, WgradPlan* pl) {
+    if (!act_fmt || !tri_internal_vox0_geometry(*d, &pl->g.vox0) || (pl->splits = tri_internal_vox0_wgrad_grid(pl->g.vox0)) <= 0) return 0;
+    pl->BI = 32; pl->BJ = pl->Kpad = 144;
+    return 1;
 }
+
 #define KROW_TARGET_BLOCKS 512                                      // two workgroups per CU (56 / 40 KB of LDS, <= 256 registers)
 // split plan of a layer launched alone: one resident round of workgroups, at least 4 steps per split
 static void krow_plan_alone(int tiles, int steps, int* sps, int* splits) {
@@ -1569,6 +1633,37 @@ static void krow_plan_alone(int tiles, int steps, int* sps, int* splits) {
     if (s > 1024) s = 1024;
     *sps = (steps + s - 1) / s;
     *splits = (steps + *sps - 1) / *sps;
+}
+// conv_wgrad_krow_kernel: resolution-keeping 3x3 layers, 16-bit storage.  BI = 128 / 64 rows per workgroup tile, tiles = workgroups
+// per position split, steps = 64-position steps; the split plan is the one of a layer launched alone
+static int plan_krow(const TriConvDesc* d, int act_fmt, unsigned, WgradPlan* pl) {
+    if (!act_fmt || krow_wgrad_disabled()) return 0;
+    if (d->KD != 1 || d->ID != 1 || d->KH != 3 || d->KW != 3 || (d->stride != 1 && d->stride != 2) || d->pad_d != 0 || d->pad_h != 1 || d->pad_w != 1) return 0;
+    if (d->Cin % 64 || d->Cout % 64 || d->OH * d->stride != d->IH || d->OW * d->stride != d->IW) return 0;
+    const int W = d->OW, H = d->OH;
+    if (W < 4 || W > 64) return 0;
+    const size_t in_bytes = (size_t)d->B * d->IH * d->IW * d->Cin * 2, dout_bytes = (size_t)d->B * H * W * d->Cout * 2;
+    if (in_bytes >= ((size_t)1 << 31) || dout_bytes >= ((size_t)1 << 31)) return 0;
+    KrowArgs a{};
+    a.in_bytes = (unsigned)in_bytes; a.dout_bytes = (unsigned)dout_bytes;
+    a.NH = d->B * H; a.H = H; a.W = W; a.Cin = d->Cin; a.Cout = d->Cout; a.Kpad = 9 * d->Cin;
+    a.Hin = d->IH; a.Win = d->IW;
+    a.rps = 64 / W;
+    a.P = d->stride == 1 ? ((W + 3) & ~1) : 2 * W + 2;               // even pitch: the bank half of a pixel is the parity of its index
+    if (a.rps * a.P > (d->stride == 1 ? KROW_SLAB_PX : KROW_SLAB_PX_S2)) return 0;
+    a.npiece = (a.rps * a.P + 7) / 8;
+    a.nsteps = (a.NH + a.rps - 1) / a.rps;
+    a.ci_chunks = d->Cin / 64;
+    pl->BI = d->Cout % 128 == 0 ? 128 : 64;
+    pl->BJ = 3 * 64;                                                 // one kernel row of one 64-channel chunk
+    a.ntiles = (d->Cout / pl->BI) * 3 * a.ci_chunks;
+    a.dH = make_fastdiv(H); a.dP = make_fastdiv(a.P); a.dW = make_fastdiv(W);
+    krow_plan_alone(a.ntiles, a.nsteps, &a.steps_per_split, &a.nsplits);
+    pl->g.krow = a;
+    pl->tiles = pl->group_tiles = a.ntiles; pl->steps = a.nsteps; pl->splits = a.nsplits; pl->steps_per_split = a.steps_per_split; pl->Kpad = a.Kpad;
+    // grouping family: 4 = conv_wgrad_krow_kernel<128> (stride 1 and 2 share launches), 5 = <64>, 7 = its stride-2 form
+    pl->group = pl->BI == 128 ? 4 : (d->stride == 2 ? 7 : 5);
+    return 1;
 }
 static inline int krow_blocks(const KrowArgs& a) {               // (a multiple of 8: the next job's range starts on XCD 0 again)
     return a.nsplits >= 16 ? ((a.nsplits + 7) / 8) * 8 * a.ntiles : (a.nsplits * a.ntiles + 7) / 8 * 8;
@@ -1616,49 +1711,6 @@ static int launch_krow(int co_t, int act_fmt, const KrowArgs* a, int n, hipStrea
 #undef TRI_KR
 }
 
-extern "C" size_t tri_conv_wgrad_workspace(const TriConvDesc* d) {
-    size_t need = 0;
-    {
-        StemWgradArgs sg; int grid;
-        if (stem_wgrad_geometry(d, 1, &sg, &grid)) need = (size_t)grid * 64 * d->KH * 32 * sizeof(float);
-        C64WgradArgs cg;
-        if (c64_wgrad_geometry(d, 1, &cg, &grid)) need = (size_t)grid * 64 * 576 * sizeof(float);
-        TriVox0Geom vg;
-        if (tri_internal_vox0_geometry(*d, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
-            need = (size_t)tri_internal_vox0_wgrad_grid(vg) * 32 * 144 * sizeof(float);
-        KrowArgs kg; int co_t, tiles, steps;
-        if (krow_geometry(d, 1, &kg, &co_t, &tiles, &steps)) {
-            int sps, splits;
-            krow_plan_alone(tiles, steps, &sps, &splits);
-            const size_t n = (size_t)splits * d->Cout * kg.Kpad * sizeof(float);
-            if (n > need) need = n;
-        }
-    }
-    for (int mode = 0; mode < 4; ++mode) {                        // fp32 / 16-bit storage x position range / row list
-        int BI, BJ, tiles, splits, sps, Kpad, dma;
-        wgrad_plan(d, mode & 1, mode >> 1, &BI, &BJ, &tiles, &splits, &sps, &Kpad, &dma);
-        size_t n = (size_t)splits * d->Cout * Kpad * sizeof(float);
-        if (n > need) need = n;
-    }
-    return need;
-}
-
-// 0: conv_wgrad_kernel (register-staged), 2: conv_wgrad_dma_kernel (bf16 activation storage, LDS-DMA).  For profilers.
-extern "C" int tri_conv_wgrad_kernel_family(const TriConvDesc* d, int act_fmt) {
-    {
-        TriVox0Geom vg;
-        if (act_fmt && tri_internal_vox0_geometry(*d, &vg) && tri_internal_vox0_wgrad_grid(vg) > 0)
-            return 6;                                              // conv_vox0_wgrad_kernel when the call passes a site mask
-    }
-    {
-        C64WgradArgs cg; KrowArgs kg; int grid, co_t, tiles, steps;
-        if (!c64_wgrad_geometry(d, act_fmt, &cg, &grid) && krow_geometry(d, act_fmt, &kg, &co_t, &tiles, &steps)) return 7;   // conv_wgrad_krow_kernel
-    }
-    int BI, BJ, tiles, splits, sps, Kpad, dma;
-    wgrad_plan(d, act_fmt, 0, &BI, &BJ, &tiles, &splits, &sps, &Kpad, &dma);
-    return dma ? 2 : 0;
-}
-
 static inline int wgrad_dma_blocks(const WgradArgs& a) {              // (16+ splits: padded to whole groups of 8 for the XCD pinning)
     return a.nsplits >= 16 ? ((a.nsplits + 7) / 8) * 8 * a.ntiles : a.nsplits * a.ntiles;
 }
@@ -1696,15 +1748,10 @@ static int launch_wgrad_dma_jobs(const WgradArgs* a, int n, hipStream_t stream) 
     conv_wgrad_dma_kernel<BI, BJ, E, NWI, NWJ><<<dim3(blocks), NWI * NWJ * 64, smem, stream>>>(jobs);
     return tri_check_launch("tri_conv_wgrad(dma)");
 }
-template <int BI, int BJ, typename E>
-static int launch_wgrad_dma(const WgradArgs& a, int tiles, int splits, hipStream_t stream) {
-    (void)tiles; (void)splits;
-    return launch_wgrad_dma_jobs<BI, BJ, E>(&a, 1, stream);
-}
 
 #define WGRAD_MAX_STEPS 96
 template <int BI, int BJ, int NSPLIT, typename AT>
-static int launch_wgrad(const WgradArgs& a, int tiles, int splits, hipStream_t stream) {
+static int launch_wgrad(const WgradArgs& a, hipStream_t stream) {
     constexpr int STAGE = NSPLIT * (32 * BI * 2 + 32 * BJ * 2);
     size_t smem = 2 * STAGE + 512 + (size_t)a.steps_per_split * (a.row_count ? 384 : 256);
     static bool attr_set = false;
@@ -1713,74 +1760,87 @@ static int launch_wgrad(const WgradArgs& a, int tiles, int splits, hipStream_t s
                             2 * STAGE + 512 + WGRAD_MAX_STEPS * 384);
         attr_set = true;
     }
-    conv_wgrad_kernel<BI, BJ, NSPLIT, AT><<<dim3(((splits + 7) / 8) * 8 * tiles), 256, smem, stream>>>(a);
+    conv_wgrad_kernel<BI, BJ, NSPLIT, AT><<<dim3(((a.nsplits + 7) / 8) * 8 * a.ntiles), 256, smem, stream>>>(a);
     return tri_check_launch("tri_conv_wgrad");
 }
 
-// the kernel arguments of one layer (conv_wgrad_kernel / conv_wgrad_dma_kernel) from its descriptor and split plan
-static int wgrad_fill_args(const TriConvDesc* d, const void* in, const void* dout, const uint8_t* row_mask, const void* plan, float* slab,
-                           const int* row_pos, const int* row_count, int split3, int act_fmt, int Kpad, int sps, int tiles, int splits,
-                           WgradArgs* out) {
+// the kernel arguments of one layer (conv_wgrad_kernel / conv_wgrad_dma_kernel) from its descriptor, its plan's Kpad and a split plan
+static int wgrad_fill_args(const TriConvDesc* d, const WgradCall& c, int act_fmt, int Kpad, int sps, int tiles, int splits, WgradArgs* out) {
     WgradArgs a{};
-    a.in = in; a.dout = dout; a.row_mask = row_mask; a.slab = slab; a.row_pos = row_pos; a.row_count = row_count;
+    a.in = c.in; a.dout = c.dout; a.row_mask = c.row_mask; a.slab = c.slab; a.row_pos = c.row_pos; a.row_count = c.row_count;
     a.B = d->B; a.ID = d->ID; a.IH = d->IH; a.IW = d->IW; a.Cin = d->Cin;
     a.OD = d->OD; a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout;
     a.KD = d->KD; a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pd = d->pad_d; a.ph = d->pad_h; a.pw = d->pad_w;
     a.ntaps = d->KD * d->KH * d->KW;
-    if (a.ntaps > 64) { tri_set_error("wgrad: more than 64 taps unsupported"); return TRI_ERR_UNSUPPORTED; }
     a.Kpad = Kpad;
     a.M = d->B * d->OD * d->OH * d->OW;
     a.cin_shift = ilog2_exact(a.Cin);
     a.steps_per_split = sps;
     a.ntiles = tiles;
     a.nsplits = splits;
-    size_t in_bytes = (size_t)a.B * a.ID * a.IH * a.IW * a.Cin * (act_fmt ? 2 : 4);
-    if (act_fmt && split3) { tri_set_error("wgrad: 16-bit activation storage takes single operands (no 3-product split)"); return TRI_ERR_ARG; }
-    if (!plan) { tri_set_error("wgrad: a gather plan from tri_conv_plan_build is required"); return TRI_ERR_ARG; }
-    if (in_bytes >= ((size_t)1 << 31)) { tri_set_error("wgrad: input tensor >= 2 GiB (32-bit buffer offsets)"); return TRI_ERR_UNSUPPORTED; }
+    if (!c.plan) { tri_set_error("wgrad: a gather plan from tri_conv_plan_build is required"); return TRI_ERR_ARG; }
     {
         long Mpad = ((long)a.M + 31) / 32 * 32;
-        a.plan_off = (const int*)plan;
-        a.plan_mask = (const unsigned*)plan + Mpad;
-        a.in_bytes = (unsigned)in_bytes;
+        a.plan_off = (const int*)c.plan;
+        a.plan_mask = (const unsigned*)c.plan + Mpad;
+        a.in_bytes = (unsigned)((size_t)a.B * a.ID * a.IH * a.IW * a.Cin * (act_fmt ? 2 : 4));      // < 2 GiB: plan_tiled
     }
     a.dOW = make_fastdiv(a.OW); a.dOH = make_fastdiv(a.OH); a.dOD = make_fastdiv(a.OD); a.dCin = make_fastdiv(a.Cin);
     *out = a;
     return 0;
 }
-// reduce descriptor of a layer whose partial kernel wrote `splits` slabs [Cout][Kpad]
-static void wgrad_fill_pending(const TriConvDesc* d, const float* slab, int splits, int Kpad, float* dw, long s_co, long s_tap, long s_ci,
-                               int cin_real, float out_scale, TriWgradReduce* pending) {
-    const int ntaps = d->KD * d->KH * d->KW;
+// reduce descriptor of a layer whose partial kernel wrote `splits` slabs in its family's layout
+static void wgrad_fill_pending(const TriConvDesc* d, const WgradPlan& pl, const float* slab, int splits, float* dw, long s_co, long s_tap,
+                               long s_ci, int cin_real, float out_scale, TriWgradReduce* pending) {
+    const WgradFamily& f = *pl.family;
+    const int ntaps = f.kw_shift ? (d->KD * d->KH) << f.kw_shift : d->KD * d->KH * d->KW;
     const long quads = (long)d->Cout * ((ntaps * d->Cin) >> 2);
     int zlanes = 1;
     while (zlanes < 64 && zlanes * 2 <= splits && quads * zlanes < 262144) zlanes *= 2;
     const int kq = 256 / zlanes;
     pending->slab = slab; pending->dw = dw; pending->s_co = s_co; pending->s_tap = s_tap; pending->s_ci = s_ci;
-    pending->splits = splits; pending->Cout = d->Cout; pending->Kpad = Kpad; pending->ntaps = ntaps; pending->cin_stored = d->Cin;
+    pending->splits = splits; pending->Cout = d->Cout; pending->Kpad = pl.Kpad; pending->ntaps = ntaps; pending->cin_stored = d->Cin;
     pending->cin_real = cin_real; pending->zlanes = zlanes; pending->nblocks = (int)((quads + kq - 1) / kq); pending->out_scale = out_scale;
-    pending->kw_real = 0; pending->kw_shift = 0;
+    pending->kw_real = f.kw_shift ? d->KW : 0; pending->kw_shift = f.kw_shift;
     // torchvision layout with several taps and not too many splits: the row form (wgrad_reduce_row), one output channel per block
     static int rows = -1;
     if (rows < 0) rows = 1;
-    if (rows && ntaps > 1 && s_tap == 1 && s_ci == ntaps && s_co == (long)ntaps * d->Cin && cin_real == d->Cin && d->Cin % 4 == 0 &&
+    if (rows && f.row_form && ntaps > 1 && s_tap == 1 && s_ci == ntaps && s_co == (long)ntaps * d->Cin && cin_real == d->Cin && d->Cin % 4 == 0 &&
         ntaps * (d->Cin + 1) <= WGRAD_ROW_MAX && splits <= 48) {
         pending->zlanes = 0;
         pending->nblocks = d->Cout;
     }
 }
 
-// launch of conv_stem_wgrad_kernel (sg.y != NULL: the BNF instantiation) + the reduce descriptor of its per-workgroup slabs
-static int stem_wgrad_launch(const TriConvDesc* d, StemWgradArgs& sg, int grid, void* workspace, size_t workspace_bytes, float* dw, long s_co,
-                             long s_tap, long s_ci, int cin_real, int act_fmt, float out_scale, TriWgradReduce* pending, void* stream) {
-    const size_t need = (size_t)grid * 64 * d->KH * 32 * sizeof(float);
-    if (workspace_bytes < need) { tri_set_error("wgrad(stem): workspace too small"); return TRI_ERR_ARG; }
-    sg.slab = (float*)workspace;
+// ---- launch adapters of the rows
+static int run_c64(const TriConvDesc*, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t stream) {
+    C64WgradArgs cg = pl.g.c64;
+    cg.in = c.in; cg.dout = c.dout; cg.slab = c.slab;
+    cg.h_abl = tri_probe_ablation();
+    const size_t smem = (size_t)cg.TR * cg.W * 128 + (size_t)(cg.TR + 2) * (cg.W + 2) * 128;
+    static bool attr = false;
+    if (!attr) {
+        hipFuncSetAttribute((const void*)conv_wgrad_c64_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        hipFuncSetAttribute((const void*)conv_wgrad_c64_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        attr = true;
+    }
+    if (act_fmt == TRI_FMT_F16) conv_wgrad_c64_kernel<f16_t><<<pl.splits, 256, smem, stream>>>(cg);
+    else conv_wgrad_c64_kernel<bf16_t><<<pl.splits, 256, smem, stream>>>(cg);
+    return tri_check_launch("tri_conv_wgrad(c64)");
+}
+static int run_vox0(const TriConvDesc* d, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t stream) {
+    return tri_internal_vox0_wgrad_launch(pl.g.vox0, pl.splits, d->B, c.in, c.dout, c.row_mask, c.slab, act_fmt, stream);
+}
+// (c.y != NULL: the BNF instantiation, which forms dOut from the BatchNorm-backward inputs and does not read c.dout)
+static int run_stem(const TriConvDesc* d, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t st) {
+    StemWgradArgs sg = pl.g.stem;
+    sg.in = c.in; sg.dout = c.dout; sg.slab = c.slab;
+    sg.y = c.y; sg.arg = c.arg; sg.dpool = c.dpool; sg.c1 = c.c1; sg.c2 = c.c2; sg.c3 = c.c3; sg.rs = c.rs; sg.rb = c.rb;
     sg.h_abl = tri_probe_ablation();
     { static int pipe = -1; if (pipe < 0) pipe = 1; sg.unpiped = !pipe; }
     const bool bnf = sg.y != nullptr;
+    const int grid = pl.splits;
     const size_t smem = (size_t)sg.TH * sg.OW * 128 + (size_t)sg.slab_rows * sg.row_bytes + (bnf ? 5 * 64 * sizeof(float) : 0);
-    hipStream_t st = (hipStream_t)stream;
 #define TRI_SWG1(KH_, T_, F_)                                                                                                  \
     do {                                                                                                                       \
         static bool attr = false;                                                                                              \
@@ -1798,153 +1858,35 @@ static int stem_wgrad_launch(const TriConvDesc* d, StemWgradArgs& sg, int grid, 
     switch (d->KH) { TRI_SWG(7) TRI_SWG(5) TRI_SWG(3) default: break; }
 #undef TRI_SWG
 #undef TRI_SWG1
-    int rc = tri_check_launch("tri_conv_wgrad(stem)");
-    if (rc) return rc;
-    const int ntaps_p = d->KH * 8;
-    const long quads = (long)64 * ntaps_p;
-    int zlanes = 1;
-    while (zlanes < 64 && zlanes * 2 <= grid && quads * zlanes < 262144) zlanes *= 2;
-    const int kq = 256 / zlanes;
-    pending->slab = (const float*)workspace; pending->dw = dw; pending->s_co = s_co; pending->s_tap = s_tap; pending->s_ci = s_ci;
-    pending->splits = grid; pending->Cout = 64; pending->Kpad = d->KH * 32; pending->ntaps = ntaps_p; pending->cin_stored = 4;
-    pending->cin_real = cin_real; pending->zlanes = zlanes; pending->nblocks = (int)((quads + kq - 1) / kq);
-    pending->out_scale = out_scale; pending->kw_real = d->KW; pending->kw_shift = 3;
-    return 0;
+    return tri_check_launch("tri_conv_wgrad(stem)");
 }
-// Weight gradient of the stem conv straight from the BatchNorm-backward inputs (conv -> BN -> ReLU -> MaxPool2d(3, 2, 1), mv_cnn.py:44):
-// the gradient w.r.t. the conv output that tri_maxpool_bn_bwd_apply would store (and this kernel re-read) is formed while the dOut tile
-// is staged.  The stem has no data gradient, so that tensor (100 MB at the bench shape) is never materialised.  y [N,OH,OW,64] conv
-// output, arg / dpool [N,OH/2,OW/2,64] winning-tap map and pooled gradient, c1..c3 from tri_bn_bwd_finalize, relu_scale / relu_shift
-// the forward's BN coefficients.  TRI_ERR_UNSUPPORTED when the layer does not take conv_stem_wgrad_kernel (caller: apply + wgrad).
-extern "C" int tri_conv_stem_wgrad_bn(const TriConvDesc* d, const void* in, const void* y, const uint8_t* arg, const void* dpool, const float* c1,
-                                      const float* c2, const float* c3, const float* relu_scale, const float* relu_shift, void* workspace,
-                                      size_t workspace_bytes, float* dw, long s_co, long s_tap, long s_ci, int cin_real, int act_fmt,
-                                      float out_scale, TriWgradReduce* pending, void* stream) {
-    if (!pending) { tri_set_error("wgrad: pending descriptor is NULL"); return TRI_ERR_ARG; }
-    StemWgradArgs sg; int grid;
-    if (!stem_wgrad_geometry(d, act_fmt, &sg, &grid) || d->OH % 2 || d->OW % 2 || sg.TH != 2 || (sg.slab_rows * sg.row_bytes) % 16) {
-        tri_set_error("tri_conv_stem_wgrad_bn: not a stem-kernel layer with an even output grid"); return TRI_ERR_UNSUPPORTED;
-    }
-    sg.in = in; sg.dout = nullptr;
-    sg.y = y; sg.arg = arg; sg.dpool = dpool; sg.c1 = c1; sg.c2 = c2; sg.c3 = c3; sg.rs = relu_scale; sg.rb = relu_shift;
-    return stem_wgrad_launch(d, sg, grid, workspace, workspace_bytes, dw, s_co, s_tap, s_ci, cin_real, act_fmt, out_scale, pending, stream);
+static int run_krow(const TriConvDesc*, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t stream) {
+    KrowArgs kg = pl.g.krow;
+    kg.in = c.in; kg.dout = c.dout; kg.slab = c.slab;
+    return launch_krow(pl.BI, act_fmt, &kg, 1, stream);
 }
-
-// dw (addressed by element strides s_co / s_tap / s_ci, i.e. directly in the reference's parameter layout)
-//   = sum over positions of dout x im2col(in).  row_mask (optional, per output position, buffer padded to a
-// multiple of 32 bytes) marks live positions; split3 != 0 selects the 3-product bf16 split mode.
-extern "C" int tri_conv_wgrad_partial(const TriConvDesc* d, const void* in, const void* dout, const uint8_t* row_mask, const void* plan,
-                                      void* workspace, size_t workspace_bytes, float* dw, long s_co, long s_tap, long s_ci, int cin_real,
-                                      int split3, int act_fmt, float out_scale, const int* row_pos, const int* row_count,
-                                      TriWgradReduce* pending, void* stream) {
-    if (!pending) { tri_set_error("wgrad: pending descriptor is NULL"); return TRI_ERR_ARG; }
-    if ((row_pos == nullptr) != (row_count == nullptr)) { tri_set_error("wgrad: row_pos and row_count go together"); return TRI_ERR_ARG; }
-    pending->kw_real = 0;
-    {
-        C64WgradArgs cg; int grid;
-        if (!row_mask && !row_count && !split3 && c64_wgrad_geometry(d, act_fmt, &cg, &grid)) {
-            const size_t need = (size_t)grid * 64 * 576 * sizeof(float);
-            if (workspace_bytes < need) { tri_set_error("wgrad(c64): workspace too small"); return TRI_ERR_ARG; }
-            cg.in = in; cg.dout = dout; cg.slab = (float*)workspace;
-            cg.h_abl = tri_probe_ablation();
-            const size_t smem = (size_t)cg.TR * cg.W * 128 + (size_t)(cg.TR + 2) * (cg.W + 2) * 128;
-            static bool attr = false;
-            if (!attr) {
-                hipFuncSetAttribute((const void*)conv_wgrad_c64_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                hipFuncSetAttribute((const void*)conv_wgrad_c64_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                attr = true;
-            }
-            if (act_fmt == TRI_FMT_F16) conv_wgrad_c64_kernel<f16_t><<<grid, 256, smem, (hipStream_t)stream>>>(cg);
-            else conv_wgrad_c64_kernel<bf16_t><<<grid, 256, smem, (hipStream_t)stream>>>(cg);
-            int rc = tri_check_launch("tri_conv_wgrad(c64)");
-            if (rc) return rc;
-            const long quads = (long)64 * 144;
-            int zlanes = 1;
-            while (zlanes < 64 && zlanes * 2 <= grid && quads * zlanes < 262144) zlanes *= 2;
-            const int kq = 256 / zlanes;
-            pending->slab = (const float*)workspace; pending->dw = dw; pending->s_co = s_co; pending->s_tap = s_tap; pending->s_ci = s_ci;
-            pending->splits = grid; pending->Cout = 64; pending->Kpad = 576; pending->ntaps = 9; pending->cin_stored = 64;
-            pending->cin_real = cin_real; pending->zlanes = zlanes; pending->nblocks = (int)((quads + kq - 1) / kq);
-            pending->out_scale = out_scale; pending->kw_shift = 0;
-            return 0;
-        }
-    }
-    {   // voxel level 0 over a site mask: conv_vox0_wgrad_kernel (conv_vox.hip)
-        TriVox0Geom vg; int grid;
-        if (row_mask && !row_count && !split3 && act_fmt &&
-            tri_internal_vox0_geometry(*d, &vg) && (grid = tri_internal_vox0_wgrad_grid(vg)) > 0) {
-            const size_t need = (size_t)grid * 32 * 144 * sizeof(float);
-            if (workspace_bytes < need) { tri_set_error("wgrad(vox0): workspace too small"); return TRI_ERR_ARG; }
-            int rc = tri_internal_vox0_wgrad_launch(vg, grid, d->B, in, dout, row_mask, (float*)workspace, act_fmt, (hipStream_t)stream);
-            if (rc) return rc;
-            const long quads = (long)32 * 36;
-            int zlanes = 1;
-            while (zlanes < 64 && zlanes * 2 <= grid && quads * zlanes < 262144) zlanes *= 2;
-            const int kq = 256 / zlanes;
-            pending->slab = (const float*)workspace; pending->dw = dw; pending->s_co = s_co; pending->s_tap = s_tap; pending->s_ci = s_ci;
-            pending->splits = grid; pending->Cout = 32; pending->Kpad = 144; pending->ntaps = 36; pending->cin_stored = 4;
-            pending->cin_real = cin_real; pending->zlanes = zlanes; pending->nblocks = (int)((quads + kq - 1) / kq);
-            pending->out_scale = out_scale; pending->kw_real = 3; pending->kw_shift = 2;
-            return 0;
-        }
-    }
-    {
-        StemWgradArgs sg; int grid;
-        if (!row_mask && !row_count && !split3 && stem_wgrad_geometry(d, act_fmt, &sg, &grid)) {
-            sg.in = in; sg.dout = dout;
-            sg.y = nullptr;
-            return stem_wgrad_launch(d, sg, grid, workspace, workspace_bytes, dw, s_co, s_tap, s_ci, cin_real, act_fmt, out_scale, pending, stream);
-        }
-    }
-    if (d->Cin % 4 != 0 || d->Cout % 4 != 0) { tri_set_error("wgrad: channels must be multiples of 4"); return TRI_ERR_ARG; }
-    {   // resolution-keeping 3x3 layers, 16-bit storage: conv_wgrad_krow_kernel
-        KrowArgs kg; int co_t, tiles, steps;
-        if (!row_mask && !row_count && !split3 && krow_geometry(d, act_fmt, &kg, &co_t, &tiles, &steps)) {
-            int sps, splits;
-            krow_plan_alone(tiles, steps, &sps, &splits);
-            if (workspace_bytes < (size_t)splits * d->Cout * kg.Kpad * sizeof(float)) { tri_set_error("wgrad(krow): workspace too small"); return TRI_ERR_ARG; }
-            kg.in = in; kg.dout = dout; kg.slab = (float*)workspace; kg.steps_per_split = sps; kg.nsplits = splits;
-            int rc = launch_krow(co_t, act_fmt, &kg, 1, (hipStream_t)stream);
-            if (rc) return rc;
-            wgrad_fill_pending(d, (const float*)workspace, splits, kg.Kpad, dw, s_co, s_tap, s_ci, cin_real, out_scale, pending);
-            return 0;
-        }
-    }
-    int BI, BJ, tiles, splits, sps, Kpad, dma;
-    wgrad_plan(d, act_fmt, row_count != nullptr, &BI, &BJ, &tiles, &splits, &sps, &Kpad, &dma);
-    if (workspace_bytes < (size_t)splits * d->Cout * Kpad * sizeof(float)) { tri_set_error("wgrad: workspace too small"); return TRI_ERR_ARG; }
+static int run_dma(const TriConvDesc* d, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t s) {
     WgradArgs a{};
-    {
-        int rc = wgrad_fill_args(d, in, dout, row_mask, plan, (float*)workspace, row_pos, row_count, split3, act_fmt, Kpad, sps, tiles, splits, &a);
-        if (rc) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-#define TRI_WG(BI_, BJ_)                                                                                   \
-    (act_fmt == TRI_FMT_F16 ? launch_wgrad<BI_, BJ_, 1, f16_t>(a, tiles, splits, s)                      \
-     : act_fmt == TRI_FMT_BF16 ? launch_wgrad<BI_, BJ_, 1, bf16_t>(a, tiles, splits, s)                  \
-              : (split3 ? launch_wgrad<BI_, BJ_, 2, float>(a, tiles, splits, s) : launch_wgrad<BI_, BJ_, 1, float>(a, tiles, splits, s)))
-    if (dma) {
-        if ((size_t)a.M * a.Cout * 2 >= ((size_t)1 << 31)) { tri_set_error("wgrad: dOut tensor >= 2 GiB (32-bit buffer offsets)"); return TRI_ERR_UNSUPPORTED; }
-        if (act_fmt == TRI_FMT_F16) rc = BI == 128 ? launch_wgrad_dma<128, 128, f16_t>(a, tiles, splits, s) : launch_wgrad_dma<64, 128, f16_t>(a, tiles, splits, s);
-        else rc = BI == 128 ? launch_wgrad_dma<128, 128, bf16_t>(a, tiles, splits, s) : launch_wgrad_dma<64, 128, bf16_t>(a, tiles, splits, s);
-    } else if (BI == 128) rc = TRI_WG(128, 128);
-    else if (BJ == 256) rc = TRI_WG(64, 256);
-    else rc = TRI_WG(64, 128);
-#undef TRI_WG
+    const int rc = wgrad_fill_args(d, c, act_fmt, pl.Kpad, pl.steps_per_split, pl.tiles, pl.splits, &a);
     if (rc) return rc;
-    wgrad_fill_pending(d, (const float*)workspace, splits, Kpad, dw, s_co, s_tap, s_ci, cin_real, out_scale, pending);
-    return 0;
+    if (act_fmt == TRI_FMT_F16) return pl.BI == 128 ? launch_wgrad_dma_jobs<128, 128, f16_t>(&a, 1, s) : launch_wgrad_dma_jobs<64, 128, f16_t>(&a, 1, s);
+    return pl.BI == 128 ? launch_wgrad_dma_jobs<128, 128, bf16_t>(&a, 1, s) : launch_wgrad_dma_jobs<64, 128, bf16_t>(&a, 1, s);
+}
+static int run_staged(const TriConvDesc* d, const WgradPlan& pl, const WgradCall& c, int act_fmt, hipStream_t s) {
+    WgradArgs a{};
+    const int rc = wgrad_fill_args(d, c, act_fmt, pl.Kpad, pl.steps_per_split, pl.tiles, pl.splits, &a);
+    if (rc) return rc;
+#define TRI_WG(BI_, BJ_)                                                                 \
+    (act_fmt == TRI_FMT_F16 ? launch_wgrad<BI_, BJ_, 1, f16_t>(a, s)                     \
+     : act_fmt == TRI_FMT_BF16 ? launch_wgrad<BI_, BJ_, 1, bf16_t>(a, s)                 \
+              : (c.split3 ? launch_wgrad<BI_, BJ_, 2, float>(a, s) : launch_wgrad<BI_, BJ_, 1, float>(a, s)))
+    if (pl.BI == 128) return TRI_WG(128, 128);
+    return pl.BJ == 256 ? TRI_WG(64, 256) : TRI_WG(64, 128);
+#undef TRI_WG
 }
 
-// TRICOLO_WGRAD_WIDE=1: grouped jobs with Cout % 256 == 0 take 256 x 128 tiles (512-thread workgroups, one per CU).  Measured at the
-// bench shape: the launches themselves 0.286 -> 0.266 ms per step, the STEP 3.08 -> 3.12 ms (a 104 KB workgroup per CU leaves the
-// other towers' kernels no room beside it) - so it stays an experiment switch (profiles/r3/NOTES_wgrad.md).
-static bool wgrad_wide_tiles() {
-    static int v = -1;
-    if (v < 0) v = 0;
-    return v == 1;
-}
+// ---- several layers in one launch (tri_conv_wgrad_partial_group): pl[i] is job i's plan; every job gets the splits that make all
+// workgroups of the launch about equally long and never more than it would get alone (so its plan's slab_bytes still bound its slab)
 static int wgrad_group_target(int family) {                     // resident workgroups a grouped launch is planned for
     // 128x128 tiles (64 KB of stages + the plan ring: two workgroups per CU): all 512 slots; 64x128 tiles: 448 as for single launches
     // (measured on the bench shape, profiles/r3/NOTES_wgrad.md).  TRICOLO_WGRAD_GROUP_BLOCKS="a,b" overrides (a: 128-row, b: 64-row tiles)
@@ -1958,122 +1900,221 @@ static int wgrad_group_target(int family) {                     // resident work
     }
     return v[family >= 1 && family <= 7 ? family - 1 : 1];
 }
-// ---- several layers in one launch
-// family of a layer for grouping: 0 = not groupable (tri_conv_wgrad_partial), 1 = conv_wgrad_dma_kernel<128,128>, 2 = <64,128>, 3 = <256,128>
-// (TRICOLO_WGRAD_WIDE), 4 = conv_wgrad_krow_kernel<128> (stride 1 and 2 share launches), 5 = conv_wgrad_krow_kernel<64>, 7 = its stride-2 form;
-// tiles = output tiles (workgroups per split), steps = 64-position steps of the contraction
-extern "C" int tri_conv_wgrad_group_info(const TriConvDesc* d, int act_fmt, int* family, int* tiles, int* steps) {
-    *family = 0; *tiles = 0; *steps = 0;
-    if (!act_fmt || d->Cin % 4 != 0 || d->Cout % 4 != 0) return 0;
-    {
-        C64WgradArgs cg; StemWgradArgs sg; int grid;
-        if (c64_wgrad_geometry(d, act_fmt, &cg, &grid) || stem_wgrad_geometry(d, act_fmt, &sg, &grid)) return 0;
-        KrowArgs kg; int co_t;
-        if (krow_geometry(d, act_fmt, &kg, &co_t, tiles, steps)) { *family = co_t == 128 ? 4 : (d->stride == 2 ? 7 : 5); return 0; }
-    }
-    int BI, BJ, t, splits, sps, Kpad, dma;
-    wgrad_plan(d, act_fmt, 0, &BI, &BJ, &t, &splits, &sps, &Kpad, &dma);
-    if (!dma) return 0;
-    *family = BI == 128 ? 1 : 2;
-    if (BI == 128 && d->Cout % 256 == 0 && wgrad_wide_tiles()) {      // 256 x 128 tiles, 512-thread workgroups
-        *family = 3;
-        t = (d->Cout / 256) * ((Kpad + 127) / 128);
-    }
-    *tiles = t;
-    *steps = (int)(((long)d->B * d->OD * d->OH * d->OW + 63) / 64);
+static int wgrad_group_job(const TriWgradJob& j, const WgradPlan& pl, int splits, const char* what, TriWgradReduce* pending) {
+    if (j.workspace_bytes < (size_t)splits * j.d->Cout * pl.Kpad * sizeof(float)) { tri_set_error(what); return TRI_ERR_ARG; }
+    wgrad_fill_pending(j.d, pl, (const float*)j.workspace, splits, j.dw, j.s_co, j.s_tap, j.s_ci, j.cin_real, j.out_scale, pending);
     return 0;
 }
-// n <= TRI_WGRAD_JOBS_MAX layers of ONE family (tri_conv_wgrad_group_info), each over its dense position range or over a compact row list
-// (row_pos / row_count; no row MASK), 16-bit activation storage.  Every job gets the splits that make all workgroups of the launch about
-// equally long and never more than it would get alone (so tri_conv_wgrad_workspace still bounds its slab); pending[i] receives job i's
-// reduce descriptor.  Row-list jobs are PLANNED for the dense position count (the list length lives on the device): a list that is
-// 15 % full leaves its splits correspondingly short - the kernel re-derives the steps per split from *row_count, so the result does not
-// depend on the plan, only the balance of the launch does (the contract is "correct for any occupancy, sized for a full list").
-extern "C" int tri_conv_wgrad_partial_group(const TriWgradJob* jobs, int n, int act_fmt, TriWgradReduce* pending, void* stream) {
-    if (n < 1 || n > WGRAD_JOBS_MAX || !jobs || !pending) { tri_set_error("wgrad group: 1..TRI_WGRAD_JOBS_MAX jobs"); return TRI_ERR_ARG; }
-    static_assert(WGRAD_JOBS_MAX == TRI_WGRAD_JOBS_MAX, "header and kernel disagree");
-    {
-        int fam, t0, st0;
-        tri_conv_wgrad_group_info(jobs[0].d, act_fmt, &fam, &t0, &st0);
-        if (fam >= 4 && fam <= 7) {
-            // kernel-row jobs: every job is cut into splits of about the launch's mean workgroup length (total tile-steps / resident
-            // slots), never more splits than it would get alone; the launch may hold more workgroups than slots - they are dealt longest
-            // first and the short ones fill in behind (one resident round would leave the few-step layers' slots idle for most of it)
-            KrowArgs ka[WGRAD_JOBS_MAX];
-            int co_t0 = 0, tl[WGRAD_JOBS_MAX], st[WGRAD_JOBS_MAX];
-            long total = 0;
-            for (int i = 0; i < n; ++i) {
-                int co_t;
-                if (jobs[i].row_pos || jobs[i].row_count || !krow_geometry(jobs[i].d, act_fmt, &ka[i], &co_t, &tl[i], &st[i]) || (i && co_t != co_t0)) {
-                    tri_set_error("wgrad group: jobs must share one groupable kernel family"); return TRI_ERR_ARG;
-                }
-                co_t0 = co_t;
-                total += (long)tl[i] * st[i];
-            }
-            int common = (int)((total + wgrad_group_target(fam) - 1) / wgrad_group_target(fam));
-            if (common < 8) common = 8;
-            for (int i = 0; i < n; ++i) {
-                int sps_alone, splits_alone;
-                krow_plan_alone(tl[i], st[i], &sps_alone, &splits_alone);
-                int sps = n == 1 ? sps_alone : (common > sps_alone ? common : sps_alone);
-                if (sps > st[i]) sps = st[i];
-                const int splits = (st[i] + sps - 1) / sps;
-                sps = (st[i] + splits - 1) / splits;                 // evened out
-                const TriConvDesc* d = jobs[i].d;
-                if (jobs[i].workspace_bytes < (size_t)splits * d->Cout * ka[i].Kpad * sizeof(float)) { tri_set_error("wgrad group(krow): workspace too small"); return TRI_ERR_ARG; }
-                ka[i].in = jobs[i].in; ka[i].dout = jobs[i].dout; ka[i].slab = (float*)jobs[i].workspace;
-                ka[i].steps_per_split = sps; ka[i].nsplits = splits;
-                wgrad_fill_pending(d, (const float*)jobs[i].workspace, splits, ka[i].Kpad, jobs[i].dw, jobs[i].s_co, jobs[i].s_tap, jobs[i].s_ci,
-                                   jobs[i].cin_real, jobs[i].out_scale, &pending[i]);
-            }
-            return launch_krow(co_t0, act_fmt, ka, n, (hipStream_t)stream);
-        }
-    }
-    WgradArgs a[WGRAD_JOBS_MAX];
-    int fam0 = 0, ind_sps[WGRAD_JOBS_MAX], tiles[WGRAD_JOBS_MAX], steps[WGRAD_JOBS_MAX], Kpads[WGRAD_JOBS_MAX];
+// kernel-row jobs: every job is cut into splits of about the launch's mean workgroup length (total tile-steps / resident slots), never
+// more splits than it would get alone; the launch may hold more workgroups than slots - they are dealt longest first and the short
+// ones fill in behind (one resident round would leave the few-step layers' slots idle for most of it)
+static int group_krow(const TriWgradJob* jobs, const WgradPlan* pl, int n, int act_fmt, TriWgradReduce* pending, hipStream_t stream) {
+    KrowArgs ka[WGRAD_JOBS_MAX];
     long total = 0;
+    for (int i = 0; i < n; ++i) total += (long)pl[i].tiles * pl[i].steps;
+    const int target = wgrad_group_target(pl[0].group);
+    int common = (int)((total + target - 1) / target);
+    if (common < 8) common = 8;
     for (int i = 0; i < n; ++i) {
-        int fam;
-        tri_conv_wgrad_group_info(jobs[i].d, act_fmt, &fam, &tiles[i], &steps[i]);
-        if (!fam || (i && fam != fam0)) { tri_set_error("wgrad group: jobs must share one groupable kernel family"); return TRI_ERR_ARG; }
-        fam0 = fam;
-        int BI, BJ, t, splits, dma;
-        wgrad_plan(jobs[i].d, act_fmt, 0, &BI, &BJ, &t, &splits, &ind_sps[i], &Kpads[i], &dma);
-        total += (long)tiles[i] * steps[i];
+        const int st = pl[i].steps, sps_alone = pl[i].steps_per_split;
+        int sps = n == 1 ? sps_alone : (common > sps_alone ? common : sps_alone);
+        if (sps > st) sps = st;
+        const int splits = (st + sps - 1) / sps;
+        sps = (st + splits - 1) / splits;                            // evened out
+        const int rc = wgrad_group_job(jobs[i], pl[i], splits, "wgrad group(krow): workspace too small", &pending[i]);
+        if (rc) return rc;
+        ka[i] = pl[i].g.krow;
+        ka[i].in = jobs[i].in; ka[i].dout = jobs[i].dout; ka[i].slab = (float*)jobs[i].workspace;
+        ka[i].steps_per_split = sps; ka[i].nsplits = splits;
     }
+    return launch_krow(pl[0].BI, act_fmt, ka, n, stream);
+}
+// LDS-DMA jobs, dense position ranges or compact row lists.  Row-list jobs are PLANNED for the dense position count (the list length lives
+// on the device): a list that is 15 % full leaves its splits correspondingly short - the kernel re-derives the steps per split from
+// *row_count, so the result does not depend on the plan, only the balance of the launch does (the contract is "correct for any
+// occupancy, sized for a full list").
+static int group_dma(const TriWgradJob* jobs, const WgradPlan* pl, int n, int act_fmt, TriWgradReduce* pending, hipStream_t s) {
+    WgradArgs a[WGRAD_JOBS_MAX];
+    const int fam = pl[0].group;
+    long total = 0;
+    for (int i = 0; i < n; ++i) total += (long)pl[i].group_tiles * pl[i].steps;
     // the smallest common split length whose workgroups (tiles x splits over the jobs) all fit the launch's resident slots at once;
     // a job's own split length is then evened out (ceil(steps / splits)) and never shorter than the one it would get alone
-    const int target = wgrad_group_target(fam0);
+    const int target = wgrad_group_target(fam);
     int common = (int)((total + target - 1) / target);
     if (common < 1) common = 1;
     for (;; ++common) {
         long wgs = 0;
         for (int i = 0; i < n; ++i) {
-            const int sps = common > ind_sps[i] ? common : ind_sps[i];
-            wgs += (long)tiles[i] * ((steps[i] + sps - 1) / sps);
+            const int sps = common > pl[i].steps_per_split ? common : pl[i].steps_per_split;
+            wgs += (long)pl[i].group_tiles * ((pl[i].steps + sps - 1) / sps);
         }
         if (wgs <= target || common >= 4096) break;
     }
     for (int i = 0; i < n; ++i) {
-        int sps = (n == 1 && fam0 != 3) ? ind_sps[i] : (common > ind_sps[i] ? common : ind_sps[i]);
-        if (sps > steps[i]) sps = steps[i];
-        const int splits = (steps[i] + sps - 1) / sps;
-        if (n > 1 || fam0 == 3) sps = (steps[i] + splits - 1) / splits;
-        const TriConvDesc* d = jobs[i].d;
-        if (jobs[i].workspace_bytes < (size_t)splits * d->Cout * Kpads[i] * sizeof(float)) { tri_set_error("wgrad group: workspace too small"); return TRI_ERR_ARG; }
-        if ((size_t)d->B * d->OD * d->OH * d->OW * d->Cout * 2 >= ((size_t)1 << 31)) { tri_set_error("wgrad: dOut tensor >= 2 GiB (32-bit buffer offsets)"); return TRI_ERR_UNSUPPORTED; }
-        if ((jobs[i].row_pos == nullptr) != (jobs[i].row_count == nullptr)) { tri_set_error("wgrad group: row_pos and row_count go together"); return TRI_ERR_ARG; }
-        int rc = wgrad_fill_args(d, jobs[i].in, jobs[i].dout, nullptr, jobs[i].plan, (float*)jobs[i].workspace, jobs[i].row_pos, jobs[i].row_count,
-                                 0, act_fmt, Kpads[i], sps, tiles[i], splits, &a[i]);
+        const int st = pl[i].steps, sps_alone = pl[i].steps_per_split;
+        int sps = (n == 1 && fam != 3) ? sps_alone : (common > sps_alone ? common : sps_alone);
+        if (sps > st) sps = st;
+        const int splits = (st + sps - 1) / sps;
+        if (n > 1 || fam == 3) sps = (st + splits - 1) / splits;
+        int rc = wgrad_group_job(jobs[i], pl[i], splits, "wgrad group: workspace too small", &pending[i]);
+        if (rc) return rc;
+        const WgradCall c = {jobs[i].in, jobs[i].dout, nullptr, jobs[i].plan, jobs[i].row_pos, jobs[i].row_count, (float*)jobs[i].workspace};
+        rc = wgrad_fill_args(jobs[i].d, c, act_fmt, pl[i].Kpad, sps, pl[i].group_tiles, splits, &a[i]);
         if (rc) return rc;
         a[i].plan_ring = sps > 2 * WGRAD_RING_STEPS ? 1 : 0;
-        wgrad_fill_pending(d, (const float*)jobs[i].workspace, splits, Kpads[i], jobs[i].dw, jobs[i].s_co, jobs[i].s_tap, jobs[i].s_ci,
-                           jobs[i].cin_real, jobs[i].out_scale, &pending[i]);
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (fam0 == 3) return act_fmt == TRI_FMT_F16 ? launch_wgrad_dma_jobs<256, 128, f16_t, 4, 2>(a, n, s) : launch_wgrad_dma_jobs<256, 128, bf16_t, 4, 2>(a, n, s);
-    if (act_fmt == TRI_FMT_F16) return fam0 == 1 ? launch_wgrad_dma_jobs<128, 128, f16_t>(a, n, s) : launch_wgrad_dma_jobs<64, 128, f16_t>(a, n, s);
-    return fam0 == 1 ? launch_wgrad_dma_jobs<128, 128, bf16_t>(a, n, s) : launch_wgrad_dma_jobs<64, 128, bf16_t>(a, n, s);
+    if (fam == 3) return act_fmt == TRI_FMT_F16 ? launch_wgrad_dma_jobs<256, 128, f16_t, 4, 2>(a, n, s) : launch_wgrad_dma_jobs<256, 128, bf16_t, 4, 2>(a, n, s);
+    if (act_fmt == TRI_FMT_F16) return fam == 1 ? launch_wgrad_dma_jobs<128, 128, f16_t>(a, n, s) : launch_wgrad_dma_jobs<64, 128, f16_t>(a, n, s);
+    return fam == 1 ? launch_wgrad_dma_jobs<128, 128, bf16_t>(a, n, s) : launch_wgrad_dma_jobs<64, 128, bf16_t>(a, n, s);
+}
+
+static const WgradFamily wgrad_families[] = {
+    // code, kernel, plan | skips | needs, ch4 | kw_shift, row_form | launch, launch_group
+    {TRI_WGRAD_C64, "conv_wgrad_c64_kernel", plan_c64, WF_MASK | WF_ROWS | WF_SPLIT3 | WF_BNF, 0, false, 0, false, run_c64, nullptr},
+    {TRI_WGRAD_VOX0, "conv_vox0_wgrad_kernel", plan_vox0, WF_ROWS | WF_SPLIT3 | WF_BNF, WF_MASK, false, 2, false, run_vox0, nullptr},
+    {TRI_WGRAD_STEM, "conv_stem_wgrad_kernel", plan_stem, WF_MASK | WF_ROWS | WF_SPLIT3, 0, false, 3, false, run_stem, nullptr},
+    {TRI_WGRAD_KROW, "conv_wgrad_krow_kernel", plan_krow, WF_MASK | WF_ROWS | WF_SPLIT3 | WF_BNF, 0, true, 0, true, run_krow, group_krow},
+    {TRI_WGRAD_DMA, "conv_wgrad_dma_kernel", plan_dma, WF_BNF, 0, true, 0, true, run_dma, group_dma},
+    {TRI_WGRAD_STAGED, "conv_wgrad_kernel", plan_staged, WF_BNF, 0, true, 0, true, run_staged, nullptr},
+};
+
+// asks one row; a row that takes the layer (or takes it and refuses the call) leaves its plan in *pl
+static int wgrad_ask(const WgradFamily& f, const TriConvDesc* d, int act_fmt, unsigned feat, WgradPlan* pl) {
+    *pl = WgradPlan{};
+    const int r = f.plan(d, act_fmt, feat, pl);
+    if (!r) return 0;
+    pl->family = &f;
+    pl->rc = r < 0 ? r : 0;
+    pl->slab_bytes = (size_t)pl->splits * d->Cout * pl->Kpad * sizeof(float);
+    return r;
+}
+static WgradPlan wgrad_make_plan(const TriConvDesc* d, int act_fmt, unsigned feat) {
+    WgradPlan pl{};
+    for (const WgradFamily& f : wgrad_families) {
+        if ((feat & f.skips) || (f.needs & ~feat)) continue;
+        if (f.ch4 && (d->Cin % 4 != 0 || d->Cout % 4 != 0)) { pl = WgradPlan{}; pl.refusal = "wgrad: channels must be multiples of 4"; pl.rc = TRI_ERR_ARG; return pl; }
+        if (wgrad_ask(f, d, act_fmt, feat, &pl)) return pl;
+    }
+    pl = WgradPlan{};
+    pl.refusal = "wgrad: no kernel family takes this call"; pl.rc = TRI_ERR_UNSUPPORTED;
+    return pl;
+}
+
+// the fused stem call (WF_BNF) takes the stem row's layers with an even output grid in tiles of two rows
+static bool wgrad_bnf_ok(const TriConvDesc* d, const WgradPlan& pl) {
+    const StemWgradArgs& sg = pl.g.stem;
+    return !pl.rc && pl.family->code == TRI_WGRAD_STEM && !(d->OH % 2 || d->OW % 2 || sg.TH != 2 || (sg.slab_rows * sg.row_bytes) % 16);
+}
+
+// the workspace check, the family's launch and the reduce descriptor of its slabs
+static int wgrad_run(const TriConvDesc* d, const WgradPlan& pl, WgradCall& c, void* workspace, size_t workspace_bytes, float* dw, long s_co,
+                     long s_tap, long s_ci, int cin_real, int act_fmt, float out_scale, TriWgradReduce* pending, void* stream) {
+    if (pl.rc) { tri_set_error(pl.refusal); return pl.rc; }
+    if (workspace_bytes < pl.slab_bytes) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "wgrad(%s): workspace too small", pl.family->kernel);
+        tri_set_error(msg); return TRI_ERR_ARG;
+    }
+    c.slab = (float*)workspace;
+    const int rc = pl.family->launch(d, pl, c, act_fmt, (hipStream_t)stream);
+    if (rc) return rc;
+    wgrad_fill_pending(d, pl, c.slab, pl.splits, dw, s_co, s_tap, s_ci, cin_real, out_scale, pending);
+    return 0;
+}
+
+// the largest slab any call on this layer can need: every row that takes the layer, fp32 / 16-bit storage x position range / row list
+extern "C" size_t tri_conv_wgrad_workspace(const TriConvDesc* d) {
+    size_t need = 0;
+    for (int mode = 0; mode < 4; ++mode)
+        for (const WgradFamily& f : wgrad_families) {
+            WgradPlan pl;
+            if (wgrad_ask(f, d, mode & 1, mode & 2 ? WF_ROWS : 0, &pl) && pl.slab_bytes > need) need = pl.slab_bytes;
+        }
+    return need;
+}
+
+// The layer's class, for callers that choose what to pass: 6 brick layer (a call that passes the site mask runs conv_vox0_wgrad_kernel),
+// 7 kernel-row layer, 2 DMA-capable, 0 otherwise - not the kernel of a particular call (tri_conv_wgrad_route).  A layer whose dense call
+// runs conv_wgrad_c64_kernel or conv_stem_wgrad_kernel is classed by the im2col kernel that takes its other calls.
+extern "C" int tri_conv_wgrad_kernel_family(const TriConvDesc* d, int act_fmt) {
+    WgradPlan pl = wgrad_make_plan(d, act_fmt, WF_MASK);
+    if (pl.family && pl.family->code == TRI_WGRAD_VOX0) return TRI_WGRAD_VOX0;
+    const WgradPlan dense = wgrad_make_plan(d, act_fmt, 0);
+    if (dense.family && dense.family->code == TRI_WGRAD_KROW) pl = dense;
+    return pl.family ? (int)pl.family->code : 0;
+}
+
+extern "C" int tri_conv_wgrad_route(const TriConvDesc* d, int act_fmt, int features) {
+    const unsigned feat = (unsigned)features;
+    if ((feat & WF_BNF) && feat != WF_BNF) { tri_set_error("wgrad: the fused stem call takes no other feature"); return TRI_ERR_ARG; }
+    const WgradPlan pl = wgrad_make_plan(d, act_fmt, feat);
+    if ((feat & WF_BNF) && !wgrad_bnf_ok(d, pl)) { tri_set_error("wgrad: not a stem-kernel layer with an even output grid"); return TRI_ERR_UNSUPPORTED; }
+    if (pl.rc) { tri_set_error(pl.refusal); return pl.rc; }
+    // the launch the call may share: none with a row mask, and with a row list only the one its layer's dense jobs are queued for
+    int group = (feat & ~WF_ROWS) ? 0 : pl.group;
+    if (group && (feat & WF_ROWS) && wgrad_make_plan(d, act_fmt, 0).family != pl.family) group = 0;
+    return (int)pl.family->code | group << TRI_WGRAD_ROUTE_GROUP_SHIFT | pl.BI << TRI_WGRAD_ROUTE_ROWS_SHIFT | pl.BJ << TRI_WGRAD_ROUTE_COLS_SHIFT;
+}
+
+// Weight gradient of the stem conv straight from the BatchNorm-backward inputs (conv -> BN -> ReLU -> MaxPool2d(3, 2, 1), mv_cnn.py:44):
+// the gradient w.r.t. the conv output that tri_maxpool_bn_bwd_apply would store (and this kernel re-read) is formed while the dOut tile
+// is staged.  The stem has no data gradient, so that tensor (100 MB at the bench shape) is never materialised.  y [N,OH,OW,64] conv
+// output, arg / dpool [N,OH/2,OW/2,64] winning-tap map and pooled gradient, c1..c3 from tri_bn_bwd_finalize, relu_scale / relu_shift
+// the forward's BN coefficients.  TRI_ERR_UNSUPPORTED when the layer does not take conv_stem_wgrad_kernel (caller: apply + wgrad).
+extern "C" int tri_conv_stem_wgrad_bn(const TriConvDesc* d, const void* in, const void* y, const uint8_t* arg, const void* dpool, const float* c1,
+                                      const float* c2, const float* c3, const float* relu_scale, const float* relu_shift, void* workspace,
+                                      size_t workspace_bytes, float* dw, long s_co, long s_tap, long s_ci, int cin_real, int act_fmt,
+                                      float out_scale, TriWgradReduce* pending, void* stream) {
+    if (!pending) { tri_set_error("wgrad: pending descriptor is NULL"); return TRI_ERR_ARG; }
+    const WgradPlan pl = wgrad_make_plan(d, act_fmt, WF_BNF);
+    if (!wgrad_bnf_ok(d, pl)) {
+        tri_set_error("tri_conv_stem_wgrad_bn: not a stem-kernel layer with an even output grid"); return TRI_ERR_UNSUPPORTED;
+    }
+    WgradCall c = {in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, y, arg, dpool, c1, c2, c3, relu_scale, relu_shift};
+    return wgrad_run(d, pl, c, workspace, workspace_bytes, dw, s_co, s_tap, s_ci, cin_real, act_fmt, out_scale, pending, stream);
+}
+
+// dw (addressed by element strides s_co / s_tap / s_ci, i.e. directly in the reference's parameter layout)
+//   = sum over positions of dout x im2col(in).  row_mask (optional, per output position, buffer padded to a
+// multiple of 32 bytes) marks live positions; split3 != 0 selects the 3-product bf16 split mode.
+extern "C" int tri_conv_wgrad_partial(const TriConvDesc* d, const void* in, const void* dout, const uint8_t* row_mask, const void* plan,
+                                      void* workspace, size_t workspace_bytes, float* dw, long s_co, long s_tap, long s_ci, int cin_real,
+                                      int split3, int act_fmt, float out_scale, const int* row_pos, const int* row_count,
+                                      TriWgradReduce* pending, void* stream) {
+    if (!pending) { tri_set_error("wgrad: pending descriptor is NULL"); return TRI_ERR_ARG; }
+    if ((row_pos == nullptr) != (row_count == nullptr)) { tri_set_error("wgrad: row_pos and row_count go together"); return TRI_ERR_ARG; }
+    const WgradPlan pl = wgrad_make_plan(d, act_fmt, (row_mask ? WF_MASK : 0) | (row_count ? WF_ROWS : 0) | (split3 ? WF_SPLIT3 : 0));
+    WgradCall c = {in, dout, row_mask, plan, row_pos, row_count, nullptr, split3};
+    return wgrad_run(d, pl, c, workspace, workspace_bytes, dw, s_co, s_tap, s_ci, cin_real, act_fmt, out_scale, pending, stream);
+}
+
+// family of a layer for grouping: 0 = not groupable (tri_conv_wgrad_partial), else the group its family's planner names (plan_tiled,
+// plan_krow); tiles = output tiles (workgroups per split), steps = 64-position steps of the contraction
+extern "C" int tri_conv_wgrad_group_info(const TriConvDesc* d, int act_fmt, int* family, int* tiles, int* steps) {
+    *family = 0; *tiles = 0; *steps = 0;
+    const WgradPlan pl = wgrad_make_plan(d, act_fmt, 0);
+    if (pl.family && pl.group) { *family = pl.group; *tiles = pl.group_tiles; *steps = pl.steps; }
+    return 0;
+}
+// n <= TRI_WGRAD_JOBS_MAX layers of ONE family (tri_conv_wgrad_group_info) and tile height, each over its dense position range or - where
+// the family takes one - over a compact row list (row_pos / row_count; no row MASK), 16-bit activation storage.  One plan per job, the
+// dense call's; the family's launch_group cuts the jobs and fills pending[i], job i's reduce descriptor.
+extern "C" int tri_conv_wgrad_partial_group(const TriWgradJob* jobs, int n, int act_fmt, TriWgradReduce* pending, void* stream) {
+    if (n < 1 || n > WGRAD_JOBS_MAX || !jobs || !pending) { tri_set_error("wgrad group: 1..TRI_WGRAD_JOBS_MAX jobs"); return TRI_ERR_ARG; }
+    static_assert(WGRAD_JOBS_MAX == TRI_WGRAD_JOBS_MAX, "header and kernel disagree");
+    WgradPlan pl[WGRAD_JOBS_MAX];
+    for (int i = 0; i < n; ++i) {
+        pl[i] = wgrad_make_plan(jobs[i].d, act_fmt, 0);
+        const bool rows = jobs[i].row_pos || jobs[i].row_count;
+        if (!pl[i].family || !pl[i].group || (rows && (pl[i].family->skips & WF_ROWS)) || pl[i].family != pl[0].family || pl[i].BI != pl[0].BI ||
+            (pl[i].group == 3) != (pl[0].group == 3)) {
+            tri_set_error("wgrad group: jobs must share one groupable kernel family"); return TRI_ERR_ARG;
+        }
+        if (pl[i].rc) { tri_set_error(pl[i].refusal); return pl[i].rc; }
+        if ((jobs[i].row_pos == nullptr) != (jobs[i].row_count == nullptr)) { tri_set_error("wgrad group: row_pos and row_count go together"); return TRI_ERR_ARG; }
+    }
+    return pl[0].family->launch_group(jobs, pl, n, act_fmt, pending, (hipStream_t)stream);
 }
 
 extern "C" int tri_wgrad_reduce_grouped(const TriWgradReduce* pending, int n, void* stream) {

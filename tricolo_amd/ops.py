@@ -153,6 +153,26 @@ CONV_FAMILIES = {
 FAMILY_CODE_MASK, FAMILY_TILE_SHIFT, FAMILY_SPLITK_SHIFT, FAMILY_SPU_SHIFT = 255, 8, 16, 24
 
 
+# Kernel families of the weight gradient by code (TriWgradFamily; the C side's table is wgrad_families[] in csrc/conv_wgrad.hip): what
+# rocprofv3 calls the kernel.  WGRAD_* are the feature bits and the word of tri_conv_wgrad_route (TRI_WGRAD_* in include/tricolo_hip.h).
+WGRAD_FAMILIES = {
+    0: "conv_wgrad_kernel<{bi}, {bj}, {nsplit}, {t}>",
+    2: "conv_wgrad_dma_kernel<{bi}, {bj}, {t}>",
+    4: "conv_stem_wgrad_kernel<{kh}, {t}>",
+    6: "conv_vox0_wgrad_kernel<{t}>",
+    7: "conv_wgrad_krow_kernel<{bi}, {t}>",
+    9: "conv_wgrad_c64_kernel<{t}>",
+}
+WGRAD_MASK, WGRAD_ROWS, WGRAD_SPLIT3, WGRAD_BNF = 1, 2, 4, 8
+WGRAD_ROUTE_GROUP_SHIFT, WGRAD_ROUTE_ROWS_SHIFT, WGRAD_ROUTE_COLS_SHIFT = 8, 12, 21
+
+
+def _wgrad_symbol(g, route, dtype, split=False):
+    """Name of the kernel a weight-gradient call with route word `route` (ConvGeom.wgrad_route) runs, for the KernelTimer."""
+    return WGRAD_FAMILIES[route & FAMILY_CODE_MASK].format(bi=(route >> WGRAD_ROUTE_ROWS_SHIFT) & 511, bj=(route >> WGRAD_ROUTE_COLS_SHIFT) & 1023,
+                                                           nsplit=2 if split else 1, t=_TNAME[dtype], kh=g.kernel[1])
+
+
 def _igemm_symbol(g, transposed, split, t):
     """Name of the kernel the C dispatch picks for this layer (what rocprofv3 reports), for the KernelTimer."""
     code = g.kernel_family[(transposed, 1 if split else (2 if t.dtype != torch.float32 else 0))]
@@ -231,10 +251,9 @@ class ConvGeom:
         self.kernel_family = {(tr, m): lib().tri_conv_kernel_family(_C.C.byref(self.desc), 1 if tr else 0, m)
                               for tr in (False, True) for m in (0, 1, 2)}
         self.wgrad_ws = lib().tri_conv_wgrad_workspace(_C.C.byref(self.desc))
-        fam = lib().tri_conv_wgrad_kernel_family(_C.C.byref(self.desc), 1)
-        self.wgrad_dma = fam == 2
-        self.wgrad_krow = fam == 7                                # conv_wgrad_krow_kernel (resolution-keeping 3x3 layers, 16-bit storage, no row mask / list)
-        self.wgrad_brick = fam == 6                               # conv_vox0_wgrad_kernel: needs the dense site mask (row_mask), not a row list
+        routes = [lib().tri_conv_wgrad_route(_C.C.byref(self.desc), 1, feat) for feat in (0, WGRAD_MASK)]     # (negative: refused)
+        self.wgrad_krow = routes[0] >= 0 and routes[0] & FAMILY_CODE_MASK == 7    # conv_wgrad_krow_kernel (resolution-keeping 3x3 layers, 16-bit storage, no row mask / list)
+        self.wgrad_brick = routes[1] >= 0 and routes[1] & FAMILY_CODE_MASK == 6   # conv_vox0_wgrad_kernel: needs the dense site mask (row_mask), not a row list
         self._plans = {}
         self.fwd_ws = lib().tri_conv_workspace(_C.C.byref(self.desc), 0)
         self.dgrad_ws = lib().tri_conv_workspace(_C.C.byref(self.desc), 1) if cin == cin_stored and cin % 32 == 0 else 0
@@ -309,6 +328,17 @@ class ConvGeom:
                   "tri_conv_wgrad_group_info")
             c[fmt] = (fam.value, tiles.value, steps.value)
         return c[fmt]
+
+    def wgrad_route(self, fmt: int, features: int) -> int:
+        """The word tri_conv_wgrad_route answers for a weight-gradient call with these WGRAD_* features in storage format fmt, cached;
+        a call the library refuses raises as the call itself would."""
+        c = self.__dict__.setdefault("_wgrad_route", {})
+        if (fmt, features) not in c:
+            word = lib().tri_conv_wgrad_route(_C.C.byref(self.desc), fmt, features)
+            if word < 0:
+                check(word, "tri_conv_wgrad_route")
+            c[(fmt, features)] = word
+        return c[(fmt, features)]
 
     def plan(self, device):
         """Gather plan (built once per geometry and device, reused by every step's wgrad)."""
@@ -473,10 +503,11 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 
 _WGRAD_GROUPED = os.environ.get("TRICOLO_WGRAD_GROUPED", "1") != "0"     # A/B switch: one reduce launch per layer instead
 _WGRAD_JOBS = os.environ.get("TRICOLO_WGRAD_JOBS", "1") != "0"           # A/B switch: one partial launch per layer instead
-# output tiles (workgroups per split) one grouped partial launch takes, per kernel family (1: 128-row, 2: 64-row, 3: 256-row tiles); the
-# library's split planner uses the same figures
-# (4, 5: conv_wgrad_krow_kernel<128> / <64>; a krow launch may hold more workgroups than resident slots, the library deals them longest first)
-_WGRAD_JOB_TILES = dict(zip(range(1, 8), [512, 448, 256, 512, 512, 512, 512]))   # (6, 7: stride-2 krow; the tuning aid for these figures was dropped in round 6)
+# output tiles (workgroups per split) this queue lets one grouped partial launch collect, per grouping family (1: 128-row, 2: 64-row,
+# 3: 256-row DMA tiles; 4, 5, 7: conv_wgrad_krow_kernel<128> / <64> / <64> stride 2).  The queue's budget, not the resident-slot target the
+# library plans a launch's splits for (wgrad_group_target: family 5 is 768 there); a krow launch may hold more workgroups than resident
+# slots, the library deals them longest first
+_WGRAD_JOB_TILES = {1: 512, 2: 448, 3: 256, 4: 512, 5: 512, 7: 512}
 
 
 _WGRAD_REDUCE_OVERLAP = os.environ.get("TRICOLO_WGRAD_REDUCE_OVERLAP", "1") != "0"   # A/B switch (round 6): WgradBatch.flush(side=...)
@@ -658,18 +689,10 @@ def conv_wgrad(x, dout, g: ConvGeom, like: torch.Tensor, precision: str, row_mas
     ws = batch.slab(g.wgrad_ws) if batch is not None else _workspace(g.wgrad_ws, x.device)
     plan = g.plan(x.device)
     s_co, s_tap, s_ci = g.strides
-    bi = 128 if (g.cout % 128 == 0 and g.kpad >= 128) else 64
     h16 = x.dtype != torch.float32
-    bj = 128 if bi == 128 else (256 if (g.kpad <= 256 and not (h16 and g.wgrad_dma)) else 128)
     s3 = 1 if (split3(precision) and not h16) else 0          # fp32 tensors (heads, GRU) take the 3-product split in the f16 mode too
-    if h16 and g.wgrad_brick and row_mask is not None:
-        sym = f"conv_vox0_wgrad_kernel<{_TNAME[x.dtype]}>"
-    elif h16 and g.wgrad_krow and row_mask is None and rows is None:
-        sym = f"conv_wgrad_krow_kernel<{128 if g.cout % 128 == 0 else 64}, {_TNAME[x.dtype]}>"
-    elif h16 and g.wgrad_dma:
-        sym = f"conv_wgrad_dma_kernel<{bi}, {bj}, {_TNAME[x.dtype]}>"
-    else:
-        sym = f"conv_wgrad_kernel<{bi}, {bj}, {2 if s3 else 1}, {_TNAME[x.dtype]}>"
+    feat = (WGRAD_MASK if row_mask is not None else 0) | (WGRAD_ROWS if rows is not None else 0) | (WGRAD_SPLIT3 if s3 else 0)
+    sym = _wgrad_symbol(g, g.wgrad_route(_abf(x), feat), x.dtype, s3)
     if batch is not None and batch.group_jobs and h16 and row_mask is None:
         fam, tiles, _ = g.wgrad_group(_abf(x))
         if fam:
@@ -1016,7 +1039,7 @@ def maxpool_bn_bwd_wgrad(x0, y, arg, dpool, co: "BNCoeffs", gamma, g: "ConvGeom"
     ws = batch.slab(g.wgrad_ws) if batch is not None else _workspace(g.wgrad_ws, y.device)
     s_co, s_tap, s_ci = g.strides
     desc = _C.TriWgradReduce()
-    rc = _timed(f"conv_stem_wgrad_kernel<{g.kernel[1]}, {_TNAME[y.dtype]}>", g.flops,
+    rc = _timed(WGRAD_FAMILIES[4].format(kh=g.kernel[1], t=_TNAME[y.dtype]), g.flops,
                 lambda: lib().tri_conv_stem_wgrad_bn(_C.C.byref(g.desc), ptr(_act(x0)), ptr(_act(y)), ptr(arg), ptr(_act(dpool)), ptr(buf[2]),
                                                      ptr(buf[3]), ptr(buf[4]), ptr(co.scale), ptr(co.shift), ptr(ws), ws.numel(), ptr(dw), s_co,
                                                      s_tap, s_ci, g.cin, _abf(y), float(out_scale), _C.C.byref(desc), stream()))
