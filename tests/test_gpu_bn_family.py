@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import bn_reference as R
+from tests.guard_bands import same_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -266,6 +267,44 @@ def test_stem_bn_relu_maxpool_forward_and_backward(rep, store):
     for with_pooled in (False, True):
         dy, dgamma, dbeta = ops.maxpool_bn_bwd(y, arg, dpool, co, inp.gamma, out_scale=OUT_SCALE, pooled=pooled if with_pooled else None)
         R.check_bwd(rp, f"{case} maxpool_bn_bwd pooled={with_pooled}", b, dy, dgamma, dbeta)
+
+
+@pytest.mark.parametrize("store", [F16, F32], ids=["f16", "fp32"])
+def test_stem_on_an_odd_map_through_maxpool_bn_bwd_wgrad(rep, store):
+    """ops.maxpool_bn_bwd_wgrad on 2 images whose 7x7 / 2 stem conv gives 15 x 15 x 64 (tap map and pooled tensor 8 x 8: the last pooled
+    row and column are partial windows) - the smallest shape of the odd-size form: dw, dgamma and dbeta bit for bit those of
+    ops.maxpool2d_bwd, ops.bn_bwd(relu=True, count_host=g.M), ops.conv_wgrad, and the two stages against float64: the routed gradient
+    within maxpool2d_bwd's bound, dgamma / dbeta / dy within bn_bwd's for the routed gradient as stored."""
+    N, S, C = 2, 15, 64
+    rp = _rep(rep, store)
+    case = f"stem {N}x{S}x{S}x{C} {IDS[store]}"
+    inp = R.make_inputs(N * S * S, C, store, seed=15, device=DEV, grad_scale=64.0 if store != F32 else 1.0)
+    co, st = finalize(rp, case, inp)
+    y = inp.y.reshape(N, 1, S, S, C)
+    pooled, arg = ops.maxpool2d_fwd(y, bn=co)
+    assert tuple(pooled.shape) == (N, 1, 8, 8, C)
+    gen = torch.Generator().manual_seed(16)
+    dpool = torch.randn(pooled.numel() // C, C, generator=gen) * (64.0 if store != F32 else 1.0)
+    dpool[:, 2:4] = torch.randn(pooled.numel() // C, 2, generator=gen)                   # (variance 0: see make_inputs)
+    dpool = dpool.to(DEV).to(store).reshape(pooled.shape)
+    x0 = torch.randn(N, 1, 2 * S, 2 * S, 4, generator=gen)
+    x0[..., 3] = 0.0                                                                     # (3 image channels stored as 4)
+    x0, like = x0.to(DEV).to(store), torch.empty(C, 3, 1, 7, 7, device=DEV)
+    geom = ops.ConvGeom(N, (1, 2 * S, 2 * S), 3, 4, C, (1, 7, 7), 2, (0, 3, 3), (3 * 49, 1, 49))
+    assert geom.out_grid == (1, S, S) and geom.M == N * S * S
+    dw, dgamma, dbeta = ops.maxpool_bn_bwd_wgrad(x0, y, arg, dpool, co, inp.gamma, geom, like, PREC[store], out_scale=OUT_SCALE, pooled=pooled)
+    dz = ops.maxpool2d_bwd(arg, dpool, tuple(y.shape))
+    routed = dz.clone()
+    dy, dgamma2, dbeta2 = ops.bn_bwd(y, dz, co, inp.gamma, count_host=geom.M, relu=True, out_scale=OUT_SCALE)
+    dw2 = ops.conv_wgrad(x0, dy, geom, like, PREC[store], out_scale=OUT_SCALE)
+    assert same_bytes(dw, dw2) and same_bytes(dgamma, dgamma2) and same_bytes(dbeta, dbeta2)
+    assert bool(torch.isfinite(dw).all()) and float(dw.abs().max()) > 0
+    rb = R.stem_pool(y, st, store=store, dpool=dpool, tap=arg)
+    mass = R.stem_pool(y, st, store=store, dpool=dpool.abs(), tap=arg).g_unmasked.reshape(-1, C)
+    R.check(rp, "elementwise", case, "maxpool2d_bwd", routed.reshape(-1, C), rb.g_unmasked.reshape(-1, C),
+            R.eps_of(store) * rb.g_unmasked.abs().reshape(-1, C) + R.tiny_of(store) + 8 * R.U32 * mass)
+    b = R.bn_bwd(y.reshape(-1, C), routed.reshape(-1, C), st, inp.gamma, mode="relu", out_scale=OUT_SCALE, store=store)
+    R.check_bwd(rp, f"{case} maxpool_bn_bwd_wgrad", b, dy.reshape(-1, C), dgamma, dbeta)
 
 
 # ------------------------------------------------------------------------------------------------ running statistics

@@ -14,6 +14,7 @@ view max are fused.  The whole tower (forward and backward) is one autograd node
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -440,38 +441,22 @@ class MVCNNEncoder(TriModule):
         dout = self._backward_blocks(self._blocks()[:self.N_LOWER_BLOCKS], saved["blocks"], dout, gr, prec, ugs, batch)
         x0, y, co, g0, parg = saved["stem"]
         ops.stamp("image.bwd.layer1.end")
-        stem_mode = "2"                                                # (2: apply pass inside the weight-gradient kernel; the 0 / 1 A/B forms stay reachable for odd map sizes only)
-        if y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0 and stem_mode == "2":
-            # ... and the BatchNorm-backward apply pass inside the weight-gradient kernel's staging: the stem's dy is never stored
-            # Round 6 (stem_side, _STEM_BESIDE_WGRAD): the stem's backward - three HBM-bound launches, ~85 us - has nothing behind it but the
-            # tower's weight-gradient launches, which are MFMA-bound and need nothing from it: those are issued first (WgradBatch.prelaunch)
-            # and the stem chain runs on the side stream beside them, hanging on the event recorded here
-            cm = None
-            if stem_side is not None and _STEM_BESIDE_WGRAD and batch is not None:
-                ev = torch.cuda.Event()
-                ev.record()
-                if batch.prelaunch():
-                    cm = torch.cuda.stream(stem_side.fork(dout, event=ev))
-            import contextlib
-            with (cm if cm is not None else contextlib.nullcontext()):
-                gr[self.net_1[0].weight], gr[self.net_1[1].weight], gr[self.net_1[1].bias] = ops.maxpool_bn_bwd_wgrad(
-                    x0, y, parg, dout, co, self.net_1[1].weight, g0, self.net_1[0].weight, prec, out_scale=ugs, batch=batch,
-                    pooled=saved["blocks"][0][0])                  # (the max-pool output = the first block's saved input)
-            if cm is not None and not torch.cuda.is_current_stream_capturing():
-                for t_ in (gr[self.net_1[0].weight], gr[self.net_1[1].weight], gr[self.net_1[1].bias]):
-                    t_.record_stream(torch.cuda.current_stream())   # (allocated on the side stream, read by the optimizer on this one)
-            if own and batch is not None:
-                batch.flush()
-            return [gr[p] for p in self._lower_params()]
-        if y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0 and stem_mode != "0":
-            # BatchNorm backward straight from the pooled gradient and the winning-tap map: no max-pool backward pass
-            dy, gr[self.net_1[1].weight], gr[self.net_1[1].bias] = ops.maxpool_bn_bwd(y, parg, dout, co, self.net_1[1].weight, out_scale=ugs,
-                                                                                      pooled=saved["blocks"][0][0])
-        else:
-            dzs = ops.maxpool2d_bwd(parg, dout, tuple(y.shape))
-            dy, gr[self.net_1[1].weight], gr[self.net_1[1].bias] = ops.bn_bwd(y, dzs, co, self.net_1[1].weight, count_host=g0.M, relu=True,
-                                                                              out_scale=ugs)
-        gr[self.net_1[0].weight] = ops.conv_wgrad(x0, dy, g0, self.net_1[0].weight, prec, out_scale=ugs, batch=batch)
+        # Round 6 (stem_side, _STEM_BESIDE_WGRAD): the stem's backward - three HBM-bound launches, ~85 us, its dy never stored - has nothing behind
+        # it but the tower's weight-gradient launches, which are MFMA-bound and need nothing from it: on even map sizes those are issued first
+        # (WgradBatch.prelaunch) and the stem chain runs on the side stream beside them, hanging on the event recorded here
+        side = None
+        if y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0 and stem_side is not None and _STEM_BESIDE_WGRAD and batch is not None:
+            ev = torch.cuda.Event()
+            ev.record()
+            if batch.prelaunch():
+                side = stem_side.fork(dout, event=ev)
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            stem = ops.maxpool_bn_bwd_wgrad(x0, y, parg, dout, co, self.net_1[1].weight, g0, self.net_1[0].weight, prec, out_scale=ugs, batch=batch,
+                                            pooled=saved["blocks"][0][0])   # (the max-pool output = the first block's saved input)
+        if side is not None and not torch.cuda.is_current_stream_capturing():
+            for t_ in stem:
+                t_.record_stream(torch.cuda.current_stream())     # (allocated on the side stream, read by the optimizer on this one)
+        gr[self.net_1[0].weight], gr[self.net_1[1].weight], gr[self.net_1[1].bias] = stem
         if own and batch is not None:
             batch.flush()
         return [gr[p] for p in self._lower_params()]

@@ -825,6 +825,23 @@ def _bn_bwd_finalize(partial, nblk, C, count_dev, count_host, gamma, co: "BNCoef
 _BN_SMALL = True                                                    # one-launch BatchNorm backward of tiny tensors (A/B switch dropped in round 6)
 
 
+def _bn_bwd_finish(y, g, partial, co: BNCoeffs, gamma, count_dev, count_host, out_scale, dy, row_mask=None, keep_inactive=False, rows=None,
+                   rs=None, rb=None, relu_out=None, g_masked=None):
+    """The last two stages of every BatchNorm backward that has its sums ("BatchNorm backward by caller"):
+    tri_bn_bwd_finalize over partial [nblk, 2, C], then ONE apply pass into dy (may be g) -> (dy, dgamma, dbeta).  The apply is dense, or
+    walks the dense grid by row_mask (keep_inactive: rows with 0 stay unwritten instead of zeroed), or walks the row list rows =
+    (row_pos, count) and touches no other row.  rs / rb (ReLU scale / shift), relu_out, g_masked: the mask operands of bn_bwd."""
+    C = y.shape[-1]
+    buf = _bn_bwd_finalize(partial, partial.shape[0], C, count_dev, count_host, gamma, co, out_scale)
+    if rows is not None:
+        check(lib().tri_bn_bwd_apply_rows(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(dy), C, ptr(rows[0]), ptr(rows[1]),
+                                          rows[0].numel(), _abf(y), stream()), "tri_bn_bwd_apply_rows")
+    else:
+        check(lib().tri_bn_bwd_apply(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(row_mask), ptr(dy), y.numel() // C, C, ptr(rs), ptr(rb),
+                                     ptr(relu_out), ptr(g_masked), 1 if keep_inactive else 0, _abf(y), stream()), "tri_bn_bwd_apply")
+    return dy, buf[0], buf[1]
+
+
 def bn_bwd(y, g, co: BNCoeffs, gamma, count_dev=None, count_host=0, row_mask=None, inplace=True, relu=False, relu_out=None,
            g_masked=None, out_scale: float = 1.0, keep_inactive: bool = False, partial=None):
     # row_mask: rows with 0 are never read by either pass (their y / g may be unwritten) and come out as zeros in dy
@@ -832,33 +849,28 @@ def bn_bwd(y, g, co: BNCoeffs, gamma, count_dev=None, count_host=0, row_mask=Non
     w.r.t. relu(bn(y)): the ReLU mask is then recomputed from y inside the two passes (no separate relu_bwd pass), or -
     with relu_out - w.r.t. relu(bn(y) + residual) whose saved output is relu_out; g_masked (may alias g) then receives
     g * (relu_out > 0), the gradient of the pre-activation sum that the residual branch needs too.
-    out_scale multiplies dgamma / dbeta only (f16 mode: g and dy carry F16_GRAD_SCALE, parameter gradients do not)."""
+    out_scale multiplies dgamma / dbeta only (f16 mode: g and dy carry F16_GRAD_SCALE, parameter gradients do not).
+    partial: sums [nblk, 2, C] that the pass which produced g left behind (conv_dgrad(bn_sums=...)), in place of this function's own."""
     rs, rb = (co.scale, co.shift) if relu else (None, None)
     C = y.shape[-1]
     M = y.numel() // C
     assert y.dtype == g.dtype
+    dy = g if inplace else torch.empty_like(g)
     if partial is None and _BN_SMALL and M <= 512 and C % 8 == 0 and C >= 64 and _sync_world() == 1:
         # tiny tensors (deepest voxel level): sums, coefficients and the apply pass in ONE launch (tri_bn_bwd_small; slower than the
         # three passes from ~1 k rows on - its loads are 16 bytes per cache line)
-        dy = g if inplace else torch.empty_like(g)
         buf = torch.empty((2, C), dtype=torch.float32, device=y.device)
         check(lib().tri_bn_bwd_small(ptr(_act(y)), ptr(_act(g)), M, C, ptr(count_dev), int(count_host), ptr(gamma), ptr(co.mean), ptr(co.invstd),
                                      ptr(rs), ptr(rb), ptr(relu_out), ptr(g_masked), ptr(row_mask), 1 if keep_inactive else 0, ptr(dy), ptr(buf[0]),
                                      ptr(buf[1]), float(out_scale), _abf(y), stream()), "tri_bn_bwd_small")
         return dy, buf[0], buf[1]
-    if partial is not None:                          # the sums came out of the data gradient that produced g (conv_dgrad(bn_sums=...))
-        assert row_mask is None and partial.shape[1:] == (2, C)
-        nblk = partial.shape[0]
-    else:
-        nblk = lib().tri_bn_bwd_num_blocks(M)
-        partial = torch.empty((nblk, 2, C), dtype=torch.float32, device=y.device)
+    if partial is None:
+        partial = torch.empty((lib().tri_bn_bwd_num_blocks(M), 2, C), dtype=torch.float32, device=y.device)
         check(lib().tri_bn_bwd_reduce(ptr(_act(y)), ptr(_act(g)), M, C, ptr(partial), ptr(rs), ptr(rb), ptr(relu_out), ptr(row_mask), _abf(y), stream()),
               "tri_bn_bwd_reduce")
-    buf = _bn_bwd_finalize(partial, nblk, C, count_dev, count_host, gamma, co, out_scale)
-    dy = g if inplace else torch.empty_like(g)
-    check(lib().tri_bn_bwd_apply(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(row_mask), ptr(dy), M, C, ptr(rs), ptr(rb),
-                                 ptr(relu_out), ptr(g_masked), 1 if keep_inactive else 0, _abf(y), stream()), "tri_bn_bwd_apply")
-    return dy, buf[0], buf[1]
+    assert partial.shape[1:] == (2, C)
+    return _bn_bwd_finish(y, g, partial, co, gamma, count_dev, count_host, out_scale, dy, row_mask=row_mask, keep_inactive=keep_inactive,
+                          rs=rs, rb=rb, relu_out=relu_out, g_masked=g_masked)
 
 
 def bn_bwd_pair(ya, coa: BNCoeffs, gamma_a, yb, cob: BNCoeffs, gamma_b, g, relu_out, count_host, g_masked=None, out_scale: float = 1.0):
@@ -893,24 +905,35 @@ def bn_relu_pool3d_fwd(y, co: BNCoeffs, mask, B, D, C, want_mask: bool = True):
     return pooled, mask_out
 
 
-def pool3d_bwd_route(y, co: BNCoeffs, mask, pooled, dpooled, B, D, C):
-    g = torch.empty_like(y)
-    assert dpooled.dtype == y.dtype and pooled.dtype == y.dtype
-    check(lib().tri_pool3d_bwd_route(ptr(_act(y)), ptr(co.scale), ptr(co.shift), ptr(mask), ptr(pooled), ptr(_act(dpooled)), B, D, C,
-                                     ptr(g), _abf(y), stream()), "tri_pool3d_bwd_route")
-    return g
-
-
 _VOX_ROWS = True                                                    # row-list passes on the fine voxel levels (A/B switch dropped in round 6)
 _ROUTE_RED = True                                                     # BatchNorm-backward sums inside the row-list routing walk (A/B switch dropped in round 6)
+_POOL3D_ROUTES = {(False, False): "tri_pool3d_bwd_route", (True, False): "tri_pool3d_bwd_route_rows",       # by (row list, sums)
+                  (False, True): "tri_pool3d_bwd_route_reduce", (True, True): "tri_pool3d_bwd_route_rows_reduce"}
+
+
+def _pool3d_bwd_route(y, co: BNCoeffs, mask, pooled, dpooled, B, D, C, rows_out=None, sums=False):
+    """The routing launch of one voxel level -> (g, partial).  rows_out (the pooled level's (row_pos, count)): over the ACTIVE pooled sites
+    only.  sums: the walk also leaves the BatchNorm-backward sums, partial [nblk, 2, C] (C / 4 must divide 256); otherwise partial is None."""
+    assert dpooled.dtype == y.dtype and pooled.dtype == y.dtype
+    g, partial = torch.empty_like(y), None
+    args = (ptr(_act(y)), ptr(co.scale), ptr(co.shift), ptr(mask), ptr(pooled), ptr(_act(dpooled)), B, D, C, ptr(g))
+    args += (ptr(rows_out[0]), ptr(rows_out[1])) if rows_out is not None else ()
+    if sums:
+        nblk = (lib().tri_pool3d_bwd_route_reduce_num_blocks if rows_out is None else lib().tri_pool3d_bwd_route_rows_num_blocks)(B, D, C)
+        partial = torch.empty((nblk, 2, C), dtype=torch.float32, device=y.device)
+        args += (ptr(partial),)
+    name = _POOL3D_ROUTES[(rows_out is not None, sums)]
+    check(getattr(lib(), name)(*args, _abf(y), stream()), name)
+    return g, partial
+
+
+def pool3d_bwd_route(y, co: BNCoeffs, mask, pooled, dpooled, B, D, C):
+    return _pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C)[0]
 
 
 def pool3d_bwd_route_rows(y, co: BNCoeffs, mask, pooled, dpooled, B, D, C, rows_out):
     """pool3d_bwd_route over the ACTIVE pooled sites only (rows_out = the next level's (row_pos, count))."""
-    g = torch.empty_like(y)
-    check(lib().tri_pool3d_bwd_route_rows(ptr(_act(y)), ptr(co.scale), ptr(co.shift), ptr(mask), ptr(pooled), ptr(_act(dpooled)), B, D, C,
-                                          ptr(g), ptr(rows_out[0]), ptr(rows_out[1]), _abf(y), stream()), "tri_pool3d_bwd_route_rows")
-    return g
+    return _pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C, rows_out)[0]
 
 
 def bn_bwd_rows(y, g, co: BNCoeffs, gamma, rows, out_scale: float = 1.0):
@@ -926,53 +949,29 @@ def bn_bwd_rows(y, g, co: BNCoeffs, gamma, rows, out_scale: float = 1.0):
 
 def pool3d_bn_bwd(y, co: BNCoeffs, mask, pooled, dpooled, B, D, C, gamma, count_dev, out_scale: float = 1.0, fused: bool = True,
                   keep_inactive: bool = False, rows=None, rows_out=None):
-    """Backward of BatchNorm1d -> ReLU -> SparseMaxPool3d of one voxel level: (dy, dgamma, dbeta).  fused: the routing pass also
-    produces the BatchNorm-backward sums (tri_pool3d_bwd_route_reduce), so the level costs route + finalize + apply instead of
-    route + reduce + finalize + apply; channel counts whose quads do not divide 256 take the unfused passes.  keep_inactive: dy rows
-    of inactive sites are left unwritten instead of zeroed (level 0: its dy only feeds the weight gradient over the same mask - at
-    13 % occupancy the zeros were 87 % of the pass's writes)."""
-    # rows / rows_out (round 4): (row_pos, count) of THIS level / of the pooled level.  The finest levels are 13-16 % occupied: the
-    # routing pass then walks the active pooled sites, and - where dy may stay unwritten at inactive sites (keep_inactive) - the whole
-    # BatchNorm backward walks this level's list
-    big = y.numel() // C > 16384
-    if _VOX_ROWS and _ROUTE_RED and fused and big and C % 4 == 0 and 256 % (C // 4) == 0 and rows_out is not None:
-        # (round 5) the routing walk over the active pooled sites also leaves the BatchNorm-backward sums: route + finalize + apply
-        # (fused=False / TRICOLO_POOL_REDUCE=0 select the separate route and reduce passes here too)
-        assert dpooled.dtype == y.dtype and pooled.dtype == y.dtype
-        g = torch.empty_like(y)
-        nblk = lib().tri_pool3d_bwd_route_rows_num_blocks(B, D, C)
-        partial = torch.empty((nblk, 2, C), dtype=torch.float32, device=y.device)
-        check(lib().tri_pool3d_bwd_route_rows_reduce(ptr(_act(y)), ptr(co.scale), ptr(co.shift), ptr(mask), ptr(pooled), ptr(_act(dpooled)),
-                                                     B, D, C, ptr(g), ptr(rows_out[0]), ptr(rows_out[1]), ptr(partial), _abf(y), stream()),
-              "tri_pool3d_bwd_route_rows_reduce")
-        buf = _bn_bwd_finalize(partial, nblk, C, count_dev, 0, gamma, co, out_scale)
-        if rows is not None and keep_inactive:
-            check(lib().tri_bn_bwd_apply_rows(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(g), C, ptr(rows[0]), ptr(rows[1]),
-                                              rows[0].numel(), _abf(y), stream()), "tri_bn_bwd_apply_rows")
-        else:
-            check(lib().tri_bn_bwd_apply(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(mask), ptr(g), y.numel() // C, C,
-                                         None, None, None, None, 1 if keep_inactive else 0, _abf(y), stream()), "tri_bn_bwd_apply")
-        return g, buf[0], buf[1]
-    if _VOX_ROWS and big and _sync_world() == 1 and C % 4 == 0 and (rows_out is not None or (rows is not None and keep_inactive)):
-        gz = (pool3d_bwd_route_rows(y, co, mask, pooled, dpooled, B, D, C, rows_out) if rows_out is not None
-              else pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C))
-        if rows is not None and keep_inactive:
-            return bn_bwd_rows(y, gz, co, gamma, rows, out_scale=out_scale)
-        return bn_bwd(y, gz, co, gamma, count_dev=count_dev, row_mask=mask, out_scale=out_scale, keep_inactive=keep_inactive)
-    if C % 4 or (C // 4) > 256 or 256 % (C // 4) or not fused:
-        gz = pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C)
-        return bn_bwd(y, gz, co, gamma, count_dev=count_dev, row_mask=mask, out_scale=out_scale, keep_inactive=keep_inactive)
-    assert dpooled.dtype == y.dtype and pooled.dtype == y.dtype
-    g = torch.empty_like(y)
-    nblk = lib().tri_pool3d_bwd_route_reduce_num_blocks(B, D, C)
-    partial = torch.empty((nblk, 2, C), dtype=torch.float32, device=y.device)
-    check(lib().tri_pool3d_bwd_route_reduce(ptr(_act(y)), ptr(co.scale), ptr(co.shift), ptr(mask), ptr(pooled), ptr(_act(dpooled)), B, D, C,
-                                            ptr(g), ptr(partial), _abf(y), stream()), "tri_pool3d_bwd_route_reduce")
-    M = y.numel() // C
-    buf = _bn_bwd_finalize(partial, nblk, C, count_dev, 0, gamma, co, out_scale)
-    check(lib().tri_bn_bwd_apply(ptr(y), ptr(g), ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(mask), ptr(g), M, C, None, None, None, None,
-                                 1 if keep_inactive else 0, _abf(y), stream()), "tri_bn_bwd_apply")
-    return g, buf[0], buf[1]
+    """Backward of BatchNorm1d -> ReLU -> SparseMaxPool3d of one voxel level: (dy, dgamma, dbeta).  fused: the routing pass also leaves the
+    BatchNorm-backward sums where a kernel for it exists (fused=False / TRICOLO_POOL_REDUCE=0: separate route and reduce passes).
+    keep_inactive: dy rows of inactive sites stay unwritten instead of zeroed (level 0: its dy only feeds the weight gradient over the same
+    mask).  rows / rows_out: (row_pos, count) of THIS level / of the pooled level.  DESIGN.md section 5, "BatchNorm backward by caller"."""
+    c4 = C % 4 == 0
+    sums = fused and c4 and 256 % (C // 4) == 0            # the *_reduce routing kernels: C / 4 divides 256
+    lists = _VOX_ROWS and c4 and y.numel() // C > 16384    # the fine levels (13-16 % occupied) walk row lists, not the dense grid
+    own = rows is not None and keep_inactive               # ... this level's own list for the whole BatchNorm backward: dy may stay unwritten
+    # step one: the routing launch -> g and, from the two *_reduce forms, the sums
+    if lists and sums and _ROUTE_RED and rows_out is not None:
+        g, partial = _pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C, rows_out, sums=True)
+    elif lists and (rows_out is not None or own) and _sync_world() == 1:
+        g, partial = _pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C, rows_out)
+    else:                                                  # coarse levels, and sync-BN without sums: the dense grid by the site mask
+        own = False
+        g, partial = _pool3d_bwd_route(y, co, mask, pooled, dpooled, B, D, C, sums=sums)
+    # step two: the BatchNorm backward over g, in place
+    if partial is not None:
+        return _bn_bwd_finish(y, g, partial, co, gamma, count_dev, 0, out_scale, g, row_mask=None if own else mask, keep_inactive=keep_inactive,
+                              rows=rows if own else None)
+    if own:
+        return bn_bwd_rows(y, g, co, gamma, rows, out_scale=out_scale)
+    return bn_bwd(y, g, co, gamma, count_dev=count_dev, row_mask=mask, out_scale=out_scale, keep_inactive=keep_inactive)
 
 
 def maxpool2d_fwd(x, want_arg=True, bn: BNCoeffs = None):
@@ -1008,34 +1007,34 @@ def _maxpool_bn_bwd_sums(y, arg, dpool, co: "BNCoeffs", gamma, pooled):
     return partial, nblk
 
 
-def maxpool_bn_bwd(y, arg, dpool, co: "BNCoeffs", gamma, out_scale: float = 1.0, pooled=None):
-    """Backward of relu(bn(y)) -> MaxPool2d(3, 2, 1) in the two BatchNorm passes (no max-pool backward pass, no 4x-sized gradient
-    tensor): (dy, dgamma, dbeta).  y [N,1,H,W,C], arg / dpool [N,1,H/2,W/2,C]; H, W even.  pooled: the forward's max-pool output."""
-    N, _, H, W, C = y.shape
-    assert dpool.dtype == y.dtype and H % 2 == 0 and W % 2 == 0
+def _maxpool_bn_bwd_coeffs(y, arg, dpool, co: "BNCoeffs", gamma, out_scale, pooled):
+    """Sums and coefficients of the stem's BatchNorm backward -> buf [5, C] = (dgamma, dbeta, c1, c2, c3)."""
     partial, nblk = _maxpool_bn_bwd_sums(y, arg, dpool, co, gamma, pooled)
-    buf = _bn_bwd_finalize(partial, nblk, C, None, N * H * W, gamma, co, out_scale)
+    return _bn_bwd_finalize(partial, nblk, y.shape[-1], None, y.numel() // y.shape[-1], gamma, co, out_scale)      # (count = N * H * W)
+
+
+def _maxpool_bn_bwd_apply(y, arg, dpool, co: "BNCoeffs", buf):
+    """The stem's apply pass: dy from the pooled gradient, the winning-tap map and the coefficients buf[2:5]."""
+    N, _, H, W, C = y.shape
     dy = torch.empty_like(y)
     check(lib().tri_maxpool_bn_bwd_apply(ptr(y), ptr(arg), ptr(dpool), N, H, W, C, ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(co.scale),
                                          ptr(co.shift), ptr(dy), _abf(y), stream()), "tri_maxpool_bn_bwd_apply")
-    return dy, buf[0], buf[1]
+    return dy
 
 
-def maxpool_bn_bwd_wgrad(x0, y, arg, dpool, co: "BNCoeffs", gamma, g: "ConvGeom", like, precision: str, out_scale: float = 1.0, batch=None,
-                         pooled=None):
-    """Stem backward in three launches: (dw, dgamma, dbeta) of conv -> BN -> ReLU -> MaxPool2d(3, 2, 1) (mv_cnn.py:44).  As maxpool_bn_bwd,
-    but the apply pass is folded into the weight-gradient kernel's operand staging (tri_conv_stem_wgrad_bn): the stem has no data
-    gradient, so the gradient w.r.t. the conv output - 100 MB written and re-read at the bench shape - is never stored.  Falls back to
-    maxpool_bn_bwd + conv_wgrad where the layer does not run the stem kernel."""
-    N, _, H, W, C = y.shape
-    h16 = y.dtype != torch.float32
-    if not (h16 and C == 64 and H % 2 == 0 and W % 2 == 0 and dpool.dtype == y.dtype and _sync_world() == 1):
-        dy, dgamma, dbeta = maxpool_bn_bwd(y, arg, dpool, co, gamma, out_scale=out_scale, pooled=pooled)
-        return conv_wgrad(x0, dy, g, like, precision, out_scale=out_scale, batch=batch), dgamma, dbeta
-    partial, nblk = _maxpool_bn_bwd_sums(y, arg, dpool, co, gamma, pooled)
-    buf = _bn_bwd_finalize(partial, nblk, C, None, N * H * W, gamma, co, out_scale)
+def maxpool_bn_bwd(y, arg, dpool, co: "BNCoeffs", gamma, out_scale: float = 1.0, pooled=None):
+    """Backward of relu(bn(y)) -> MaxPool2d(3, 2, 1) in the two BatchNorm passes (no max-pool backward pass, no 4x-sized gradient
+    tensor): (dy, dgamma, dbeta).  y [N,1,H,W,C], arg / dpool [N,1,H/2,W/2,C]; H, W even.  pooled: the forward's max-pool output."""
+    assert dpool.dtype == y.dtype and y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0
+    buf = _maxpool_bn_bwd_coeffs(y, arg, dpool, co, gamma, out_scale, pooled)
+    return _maxpool_bn_bwd_apply(y, arg, dpool, co, buf), buf[0], buf[1]
+
+
+def _stem_wgrad_bn(x0, y, arg, dpool, co: "BNCoeffs", buf, g: "ConvGeom", like, out_scale, batch):
+    """tri_conv_stem_wgrad_bn: the stem's weight gradient with the apply pass of _maxpool_bn_bwd_apply folded into its operand staging
+    -> dw, or None where the library has no stem kernel for the geometry (nothing was launched; the batch gets its slab back)."""
     dw = torch.empty_like(like)
-    mark = (batch.ci, batch.off) if batch is not None else None   # the arena cursor: an unsupported geometry hands its slab back
+    mark = (batch.ci, batch.off) if batch is not None else None   # the arena cursor
     ws = batch.slab(g.wgrad_ws) if batch is not None else _workspace(g.wgrad_ws, y.device)
     s_co, s_tap, s_ci = g.strides
     desc = _C.TriWgradReduce()
@@ -1043,20 +1042,35 @@ def maxpool_bn_bwd_wgrad(x0, y, arg, dpool, co: "BNCoeffs", gamma, g: "ConvGeom"
                 lambda: lib().tri_conv_stem_wgrad_bn(_C.C.byref(g.desc), ptr(_act(x0)), ptr(_act(y)), ptr(arg), ptr(_act(dpool)), ptr(buf[2]),
                                                      ptr(buf[3]), ptr(buf[4]), ptr(co.scale), ptr(co.shift), ptr(ws), ws.numel(), ptr(dw), s_co,
                                                      s_tap, s_ci, g.cin, _abf(y), float(out_scale), _C.C.byref(desc), stream()))
-    if rc == _C.TRI_ERR_UNSUPPORTED:                               # not a stem-kernel geometry: the two-pass form
+    if rc == _C.TRI_ERR_UNSUPPORTED:
         if batch is not None:
-            batch.ci, batch.off = mark                             # (nothing was launched into that slab: conv_wgrad below carves its own)
-        dy = torch.empty_like(y)
-        check(lib().tri_maxpool_bn_bwd_apply(ptr(y), ptr(arg), ptr(dpool), N, H, W, C, ptr(buf[2]), ptr(buf[3]), ptr(buf[4]), ptr(co.scale),
-                                             ptr(co.shift), ptr(dy), _abf(y), stream()), "tri_maxpool_bn_bwd_apply")
-        return conv_wgrad(x0, dy, g, like, precision, out_scale=out_scale, batch=batch), buf[0], buf[1]
+            batch.ci, batch.off = mark
+        return None
     check(rc, "tri_conv_stem_wgrad_bn")
     if batch is not None:
         batch.descs.append(desc)
         batch.dws[dw.data_ptr()] = dw
     else:
         check(lib().tri_wgrad_reduce_grouped(_C.C.byref(desc), 1, stream()), "tri_wgrad_reduce_grouped")
-    return dw, buf[0], buf[1]
+    return dw
+
+
+def maxpool_bn_bwd_wgrad(x0, y, arg, dpool, co: "BNCoeffs", gamma, g: "ConvGeom", like, precision: str, out_scale: float = 1.0, batch=None,
+                         pooled=None):
+    """Stem backward: (dw, dgamma, dbeta) of conv -> BN -> ReLU -> MaxPool2d(3, 2, 1) (mv_cnn.py:44).  The stem has no data gradient: where
+    the stem kernel runs the layer, the gradient w.r.t. the conv output - 100 MB written and re-read at the bench shape - is never stored
+    (three launches).  Elsewhere the apply pass is a launch of its own in front of conv_wgrad, and a map with an odd side takes
+    maxpool2d_bwd and bn_bwd ("BatchNorm backward by caller")."""
+    N, _, H, W, C = y.shape
+    if H % 2 == 0 and W % 2 == 0:
+        assert dpool.dtype == y.dtype
+        buf = _maxpool_bn_bwd_coeffs(y, arg, dpool, co, gamma, out_scale, pooled)
+        dw = _stem_wgrad_bn(x0, y, arg, dpool, co, buf, g, like, out_scale, batch) if y.dtype != torch.float32 and C == 64 and _sync_world() == 1 else None
+        if dw is None:
+            dw = conv_wgrad(x0, _maxpool_bn_bwd_apply(y, arg, dpool, co, buf), g, like, precision, out_scale=out_scale, batch=batch)
+        return dw, buf[0], buf[1]
+    dy, dgamma, dbeta = bn_bwd(y, maxpool2d_bwd(arg, dpool, tuple(y.shape)), co, gamma, count_host=g.M, relu=True, out_scale=out_scale)
+    return conv_wgrad(x0, dy, g, like, precision, out_scale=out_scale, batch=batch), dgamma, dbeta
 
 
 def maxpool2d_bwd(arg, dout, in_shape):
