@@ -520,6 +520,26 @@ int tri_raster_render(const float* verts, const int* faces, const long* vert_off
                       const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
                       double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
 
+/* tri_raster_render with map_Kd textures.  The batch's five texture fields (csrc/mesh_batch.h): face_uv fp32 [sumF][3][2], one (u, v)
+ * per face corner, a NaN in face_uv[f][0][0] marks a face without texture coordinates; mat_tex int32 [sumM], a batch-global texture
+ * index per material, -1 = none, anything else clamped to T - 1 (T == 0: nothing is textured); texels u8 [sumTexels][4] RGBA (alpha
+ * ignored); tex_off int64 [T + 1] texel offsets; tex_size int32 [T][2] = (height, width); row 0 is the top of the image, v = 0 its
+ * bottom.  Visibility is tri_raster_render's, bit for bit; the colour of a textured face is clamp((Kd c) shade, 0, 1) with c the
+ * texture at the perspective-correct (u, v) of the pixel centre: repeat wrap, bilinear over the texel centres, NO mip-maps, every
+ * operation in fp32 rounded on its own (spelled out at the head of csrc/raster.hip).  An untextured face - by its material, by the NaN
+ * marker, or where (u, v) is not finite - is coloured exactly as by tri_raster_render.  Same workspace, same limits. */
+int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                          const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
+                          double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
+
+/* One colour per face for the voxeliser: colours fp32 [sumF][3] = Kd for an untextured face, else Kd times the mean of four bilinear
+ * samples of its texture, at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of the face's UVs (used
+ * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped. */
+int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                          const long* tex_off, const int* tex_size, int T, int N, long sumF, float* colours, void* stream);
+
 /* ---- Coloured solid voxel grids from meshes (no counterpart in the reference, which reads downloaded NRRD grids) --------------- */
 /* The packed batch of tri_raster_render plus frame fp32 [N][4] = (origin x, y, z, cell size) per mesh.  grid u8 [N][4][V][V][V],
  * indexed [channel][x][y][z] (mesh x, y, z -> grid i, j, k); labels (optional) u8 [N][V][V][V]: 0 exterior, 1 surface, 2 interior.

@@ -1,0 +1,83 @@
+"""Timing of the textured renderer on the GPU (DESIGN.md "Textures"): ops.render_views_textured against ops.render_views on the scene
+of tools/raster_bench.py - a batch of 8 procedural meshes (a sphere on a table of boxes, about 20 k and about 200 k faces) in 12
+views at 224 x 224 - and ops.mesh_face_colours on the same batch.  Two of the three materials carry a 256 x 256 random-noise texture
+(the parser's largest size; noise is the worst case for the texel loads), the third has none, and every face has random UVs in
+[-2, 3]: textured and untextured pixels meet in the same waves.  HIP events, warmed; the two renderers alternate window by window in
+one process, and every window is reported, so the spread is on the page.  One JSON line per size.
+
+    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--trace-only RINGS]
+    (--trace-only: three warmed calls of each for rocprofv3 --kernel-trace --stats, which gives the resolve kernels' own times)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tests import raster_reference as rr                      # noqa: E402
+from tricolo_amd import ops                                  # noqa: E402
+from tricolo_amd.data import render as R                     # noqa: E402
+from tricolo_amd.meshes import MeshBatch                     # noqa: E402
+
+VIEWS, SIZE, TEXTURE = 12, 224, 256
+
+
+def batch(rings, n, dev):
+    pv, pf, pm, pk = rr.procedural_mesh(rings)
+    g = np.random.default_rng(1)
+    uv = torch.from_numpy(g.uniform(-2.0, 3.0, (pf.shape[0], 3, 2)).astype(np.float32))
+    texs = [np.concatenate([g.integers(0, 256, (TEXTURE, TEXTURE, 3), dtype=np.uint8), np.full((TEXTURE, TEXTURE, 1), 255, np.uint8)], 2) for _ in range(2)]
+    mt = torch.tensor([-1, 0, 1], dtype=torch.int32)
+    packed = MeshBatch.pack([pv] * n, [pf] * n, [pm] * n, [pk] * n, dev, face_uv_list=[uv] * n, mat_tex_list=[mt] * n, textures_list=[texs] * n)
+    return pf.shape[0], packed, (R.pack_cameras(R.box_centers(packed.boxes), VIEWS, dev), SIZE, SIZE)
+
+
+def window(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rings", type=int, nargs="+", default=[100, 317])
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--trace-only", type=int, default=None, metavar="RINGS")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs an MI355X"
+    dev = torch.device("cuda:0")
+    for rings in ([a.trace_only] if a.trace_only else a.rings):
+        faces, packed, tail = batch(rings, a.batch, dev)
+        calls = {"render_views": lambda: ops.render_views(*packed.tensors, *tail),
+                 "render_views_textured": lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail),
+                 "mesh_face_colours": lambda: ops.mesh_face_colours(packed)}
+        for fn in calls.values():
+            for _ in range(3):
+                out = fn()
+        torch.cuda.synchronize()
+        if a.trace_only:
+            print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "finite": bool(torch.isfinite(out).all())}))
+            return
+        plain, tex = ops.render_views(*packed.tensors, *tail), ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail)
+        ms = {k: [] for k in calls}
+        for _ in range(a.windows):
+            for k, fn in calls.items():
+                ms[k].append(round(window(fn, a.iters), 4))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "views": VIEWS, "size": SIZE, "texture": TEXTURE, "iters": a.iters, "ms_per_call": ms,
+                          "median_ms_per_call": med, "textured_over_plain": round(med["render_views_textured"] / med["render_views"], 4),
+                          "pixels_changed_by_textures": float((plain != tex).any(dim=2).float().mean())}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -154,6 +154,8 @@ SIGNATURES = {
     "tri_mesh_sample_points": (I, [P, P, P, P, P, P, P, I, I, C.c_ulonglong, P, P, P]),
     "tri_raster_workspace": (Z, [L, I, I, I, I]),
     "tri_raster_render": (I, [P, P, P, P, P, P, P, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
+    "tri_raster_render_tex": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
+    "tri_mesh_face_colours": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, L, P, P]),
     "tri_voxelize_workspace": (Z, [L, I, I]),
     "tri_voxelize_meshes": (I, [P, P, P, P, P, P, P, P, I, L, I, I, P, P, P, P]),
     "tri_resize_bicubic_aa_workspace": (Z, [I, I, I, I]),

@@ -7,6 +7,14 @@
 // never reads beyond the mesh.  A mesh without vertices has nothing to clamp to - every kernel checks V > 0 first - and a mesh without
 // materials is grey 0.4.  The sampler has no use for materials and leaves the three material fields null.
 //
+// Textures (optional; the five fields are null and T is 0 in a batch packed without them).  face_uv fp32 [sumF][3][2] holds one (u, v)
+// per face corner in the order of `faces`; a face whose face_uv[f][0][0] is NaN has no texture coordinates (the host writes NaN into
+// all six values).  mat_tex int32 [sumM] names a material's texture by a BATCH-GLOBAL index, -1 = none; any other value is read as
+// unsigned and clamped to T - 1, and with T == 0 every material is untextured.  Texture t is the tex_size[t] = (height, width) texels
+// from tex_off[t] (int64 [T + 1]) of texels u8 [sumTexels][4] = R, G, B, alpha (ignored, written as 255): one aligned dword each.  Row
+// 0 is the top row of the image and v = 0 its bottom (the OBJ convention).  mb_tex_sample below is THE sampling rule - repeat wrap,
+// bilinear, no mip-maps - of the textured resolve pass of raster.hip and of its face colours.
+//
 // Contraction is switched off HERE, not only in the including files: `#pragma clang fp contract(off)` covers the code that follows it,
 // so a helper defined in a header ahead of the including file's own pragma would be compiled with contraction on - a * b + c became
 // v_fmac_f32 in such a helper while the same expression in a kernel body stayed a multiply and an add.  With an fma the cross product
@@ -27,6 +35,12 @@ struct MeshBatch {
     const float* __restrict__ mat_kd;
     const long* __restrict__ mat_off;
     int N;
+    const float* __restrict__ face_uv;              // the texture fields: null / 0 when an initialiser stops at N
+    const int* __restrict__ mat_tex;
+    const unsigned* __restrict__ texels;            // one RGBA texel per dword, R in the low byte
+    const long* __restrict__ tex_off;
+    const int* __restrict__ tex_size;
+    int T;
 };
 
 // the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
@@ -64,6 +78,53 @@ __device__ __forceinline__ void mb_cross(const float* a, const float* b, const f
 // float64 the result is exact: a correctly rounded 53-bit result rounded again to 24 bits equals the directly rounded one (53 >= 2 * 24 + 2).
 __device__ __forceinline__ float mb_div(float a, float b) { return (float)((double)a / (double)b); }
 __device__ __forceinline__ float mb_sqrt(float x) { return (float)sqrt((double)x); }
+
+// The texture of global face gf of mesh n, -1 for none: no textures in the batch, a mesh without materials, a material with mat_tex
+// -1, or a face whose first texture coordinate is the NaN marker.  A bad index reads the batch's last texture.
+__device__ __forceinline__ int mb_face_tex(const MeshBatch& m, int n, long gf) {
+    const long m0 = m.mat_off[n], M = m.mat_off[n + 1] - m0;
+    if (m.T <= 0 || M <= 0) return -1;
+    const int t = m.mat_tex[m0 + min((long)(unsigned)m.face_mat[gf], M - 1)];
+    const float u0 = m.face_uv[(size_t)gf * 6];
+    if (t == -1 || u0 != u0) return -1;
+    return (int)min((long)(unsigned)t, (long)m.T - 1);
+}
+
+// i modulo n (n >= 1), correct for negative i
+__device__ __forceinline__ int mb_mod(int i, int n) {
+    const int r = i % n;
+    return r < 0 ? r + n : r;
+}
+
+// c[0..2] = texture t (0 <= t < T) at (u, v), every operation rounded on its own; false, with c untouched, for a non-finite u or v:
+//   u <- u - floorf(u), v likewise (repeat);  x = u W - 0.5,  y = (1 - v) H - 0.5;  x0 = floorf(x), fx = x - x0, y likewise;
+//   the four neighbours at columns x0, x0 + 1 modulo W and rows y0, y0 + 1 modulo H;  a channel is t = byte / 255 correctly rounded;
+//   a = t00 + (t10 - t00) fx (row y0),  b = t01 + (t11 - t01) fx (row y0 + 1),  c = a + (b - a) fy.
+// The host validates the tables (1 <= H, W <= 2^24, tex_off the running sum of H W); whatever they hold, no texel index leaves
+// [0, tex_off[T] - 1], and a texture without a texel reads as false.
+__device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u, float v, float* c) {
+    const int Ht = m.tex_size[2 * t], Wt = m.tex_size[2 * t + 1];
+    const long base = m.tex_off[t], last = m.tex_off[m.T] - 1;
+    if (!(fabsf(u) < INFINITY) || !(fabsf(v) < INFINITY) || Ht < 1 || Wt < 1 || last < 0) return false;
+    u = u - floorf(u);
+    v = v - floorf(v);
+    const float x = u * (float)Wt - 0.5f, y = (1.0f - v) * (float)Ht - 0.5f;
+    const float xf = floorf(x), yf = floorf(y);
+    const float fx = x - xf, fy = y - yf;
+    const int xa = mb_mod((int)fminf(xf, 2147483520.f), Wt), ya = mb_mod((int)fminf(yf, 2147483520.f), Ht);     // xf, yf >= -1
+    const int xb = xa + 1 == Wt ? 0 : xa + 1, yb = ya + 1 == Ht ? 0 : ya + 1;
+    const long ra = base + (long)ya * Wt, rb = base + (long)yb * Wt;
+    const unsigned p00 = m.texels[min(max(ra + xa, 0L), last)], p10 = m.texels[min(max(ra + xb, 0L), last)];    // four independent loads
+    const unsigned p01 = m.texels[min(max(rb + xa, 0L), last)], p11 = m.texels[min(max(rb + xb, 0L), last)];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float t00 = mb_div((float)((p00 >> (8 * k)) & 255u), 255.f), t10 = mb_div((float)((p10 >> (8 * k)) & 255u), 255.f);
+        const float t01 = mb_div((float)((p01 >> (8 * k)) & 255u), 255.f), t11 = mb_div((float)((p11 >> (8 * k)) & 255u), 255.f);
+        const float a = t00 + (t10 - t00) * fx, b = t01 + (t11 - t01) * fx;
+        c[k] = a + (b - a) * fy;
+    }
+    return true;
+}
 
 // Queue append.  EVERY lane of the wave must call this; one atomic add on *counter per wave, the slots in lane order.  Returns the
 // slot of a lane with pred set (the caller checks it against the queue's capacity); the value means nothing in the other lanes.

@@ -21,11 +21,23 @@
 //     correctly rounded, e = eye - a, the normal is turned toward the eye by the sign of (cx ex + cy ey) + cz ez; with the light
 //     l = (0, 1, 0): ndl = max(+-cy / len, 0) (0 when len == 0), s = 0.1 + fl32(3 / pi) ndl, colour = clamp(Kd s, 0, 1),
 //     u8 = floor(255 colour + 0.5); background 255.
+//   textured shading (tri_raster_render_tex only; the batch's texture fields are laid out in mesh_batch.h): visibility is untouched.
+//     The pixel's winning face is set up again (the snapped corners, d_i, 2A, the swap of corners 1 and 2 - their UVs swap with
+//     them), its three edge functions are formed at this pixel's centre in int64 and l_k = fl32(E_k) / fl32(2A) as for the depth; then
+//     w_k = l_k d_k,  d = (w0 + w1) + w2,  b_k = w_k / d (perspective-correct weights),  u = (b0 u0 + b1 u1) + b2 u2,  v likewise;
+//     (u, v) is sampled by mb_tex_sample (mesh_batch.h: repeat wrap, bilinear over texel centres, no mip-maps) to c, and
+//     colour = clamp((Kd c) s, 0, 1).  A face without a texture - by its material, by the NaN marker in its face_uv, or at a pixel
+//     where u or v is not finite - takes the path above, Kd s, bit for bit.  Kd x texel is the MTL rule.
+//   face colours (tri_mesh_face_colours, for the voxeliser; no camera, the UVs are used affinely): Kd times the mean of the four
+//     samples at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) - u = (b0 u0 + b1 u1) + b2 u2 with the
+//     fp32 constants RS_B13, RS_B23, RS_B16 - summed in that order and multiplied by 0.25f; Kd for a face without a texture or with
+//     a sample that is not finite.
 //
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
 #include <math.h>
+#include <stdio.h>
 
 #include "mesh_batch.h"
 #include "../../include/tricolo_hip.h"
@@ -39,12 +51,16 @@
 #define RS_SNAP_MAX 1048576.f                   // 2^20 in 1/256 pixel
 #define RS_MAX_PIXELS (1L << 31)
 #define RS_KDIFF 0.95492965f                    // fl32(3 / pi): intensity 3, Lambert's 1 / pi
+#define RS_B13 0.33333334f                      // fl32(1 / 3), fl32(2 / 3), fl32(1 / 6): the sample positions of the face colours
+#define RS_B23 0.6666667f
+#define RS_B16 0.16666667f
 
 struct RsFace {
     long A2, e[3];                              // doubled area (> 0); the edge functions at the centre of pixel (x0, y0)
     int sx[3], sy[3], bias[3];                  // their steps per pixel in x and y; 0 on a top / left edge, -1 otherwise
     float d[3];
     int x0, x1, y0, y1;                         // the box of pixel centres, clipped to the image
+    int swap;                                   // 1 when vertices 1 and 2 changed places
 };
 
 __device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
@@ -76,6 +92,7 @@ __device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __rest
     if (!ok) return false;
     long A2 = (long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long)(X[2] - X[0]) * (Y[1] - Y[0]);
     if (A2 == 0) return false;
+    o.swap = A2 < 0;
     if (A2 < 0) {
         int t = X[1]; X[1] = X[2]; X[2] = t;
         t = Y[1]; Y[1] = Y[2]; Y[2] = t;
@@ -166,12 +183,48 @@ __global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(MeshBatch m, c
     }
 }
 
-// one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int HW, long npix,
-                                                                    const u64* __restrict__ keys, uint8_t* __restrict__ image,
-                                                                    int* __restrict__ visibility) {
+// The flat Lambert shade s of the face (a, b, c) seen from `eye` (the camera's first three values).
+__device__ __forceinline__ float rs_shade(const float* a, const float* b, const float* c, const float* eye) {
+    float x[3];
+    mb_cross(a, b, c, x);
+    const float len = mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
+    const float side = (x[0] * ex + x[1] * ey) + x[2] * ez;
+    float ndl = 0.f;
+    if (len > 0.f) {
+        const float ny = mb_div(x[1], len);
+        ndl = fmaxf(side < 0.f ? -ny : ny, 0.f);
+    }
+    return 0.1f + RS_KDIFF * ndl;
+}
+
+// The texture colour c[0..2] of face gf (texture t) at the centre of pixel (px, py): false where the face is untextured there.
+__device__ __forceinline__ bool rs_texel(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
+                                         float fy, float znear, int t, int px, int py, float* c) {
+    RsFace f;
+    if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) return false;        // the winner of a pixel was set up before: never taken
+    const float* uv = m.face_uv + (size_t)gf * 6;
+    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
+    const float u0 = uv[0], v0 = uv[1], u1 = uv[2 * i1], v1 = uv[2 * i1 + 1], u2 = uv[2 * i2], v2 = uv[2 * i2 + 1];
+    const long dx = px - f.x0, dy = py - f.y0;
+    const float fa = (float)(double)f.A2;
+    const float l0 = mb_div((float)(double)(f.e[0] + dx * f.sx[0] + dy * f.sy[0]), fa);
+    const float l1 = mb_div((float)(double)(f.e[1] + dx * f.sx[1] + dy * f.sy[1]), fa);
+    const float l2 = mb_div((float)(double)(f.e[2] + dx * f.sx[2] + dy * f.sy[2]), fa);
+    const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
+    const float d = (w0 + w1) + w2;
+    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
+    return mb_tex_sample(m, t, (b0 * u0 + b1 * u1) + b2 * u2, (b0 * v0 + b1 * v1) + b2 * v2, c);
+}
+
+// one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn.  TEX: the textured resolve pass - the
+// lanes of a wave whose face has a texture run rs_texel together, the others wait for them and keep their Kd.
+template <bool TEX>
+__device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx, float fy,
+                                           float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image, int* __restrict__ visibility) {
     const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
     if (i >= npix) return;
+    const int HW = H * W;
     const long nv = i / HW;
     const int pix = (int)(i - nv * HW), n = (int)(nv / views);
     const u64 key = keys[i];
@@ -185,25 +238,60 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m,
     }
     if (visibility) visibility[i] = (int)lf;
     const int* fi = m.faces + (size_t)(f0 + lf) * 3;
-    const float *a = mb_vertex(m, v0, V, fi[0]), *b = mb_vertex(m, v0, V, fi[1]), *c = mb_vertex(m, v0, V, fi[2]);
-    const float* eye = cam + (size_t)nv * 12;
-    float x[3], kd[3];
-    mb_cross(a, b, c, x);
-    const float len = mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
-    const float side = (x[0] * ex + x[1] * ey) + x[2] * ez;
-    float ndl = 0.f;
-    if (len > 0.f) {
-        const float ny = mb_div(x[1], len);
-        ndl = fmaxf(side < 0.f ? -ny : ny, 0.f);
-    }
-    const float shade = 0.1f + RS_KDIFF * ndl;
+    const float shade = rs_shade(mb_vertex(m, v0, V, fi[0]), mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
+    float kd[3];
     mb_face_kd(m, n, f0 + lf, kd);
+    if (TEX) {
+        const int t = mb_face_tex(m, n, f0 + lf);
+        float c[3];
+        if (t >= 0 && rs_texel(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c)) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) kd[k] = kd[k] * c[k];
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
         out[(size_t)k * HW] = (uint8_t)(int)floorf(255.f * col + 0.5f);
     }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, long npix,
+                                                                    const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                                    int* __restrict__ visibility) {
+    rs_resolve<false>(m, cam, views, H, W, npix, 0.f, 0.f, 0.f, keys, image, visibility);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_tex_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
+                                                                        long npix, float fx, float fy, float znear, const u64* __restrict__ keys,
+                                                                        uint8_t* __restrict__ image, int* __restrict__ visibility) {
+    rs_resolve<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+}
+
+// one lane per face of the whole batch: out fp32 [sumF][3], the colour the voxeliser takes for the face
+__global__ __launch_bounds__(RS_THREADS) void mesh_face_colours_kernel(MeshBatch m, long sumF, float* __restrict__ out) {
+    const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (gf >= sumF) return;
+    const int n = mb_mesh_of(m, gf);
+    float kd[3];
+    mb_face_kd(m, n, gf, kd);
+    const int t = mb_face_tex(m, n, gf);
+    if (t >= 0) {
+        const float* uv = m.face_uv + (size_t)gf * 6;
+        const float bary[4][3] = {{RS_B13, RS_B13, RS_B13}, {RS_B23, RS_B16, RS_B16}, {RS_B16, RS_B23, RS_B16}, {RS_B16, RS_B16, RS_B23}};
+        float c[4][3];
+        bool ok = true;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            ok = mb_tex_sample(m, t, (bary[s][0] * uv[0] + bary[s][1] * uv[2]) + bary[s][2] * uv[4],
+                               (bary[s][0] * uv[1] + bary[s][1] * uv[3]) + bary[s][2] * uv[5], c[s]) && ok;
+        if (ok) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) kd[k] = kd[k] * ((((c[0][k] + c[1][k]) + c[2][k]) + c[3][k]) * 0.25f);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[(size_t)gf * 3 + k] = kd[k];
 }
 
 static bool rs_sizes_ok(long sumF, int N, int views, int H, int W) {
@@ -216,15 +304,19 @@ extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W
     return npix * 8 + 16 + (size_t)sumF * views * 8;                    // keys | queue count (padded to 16 bytes) | queue
 }
 
-extern "C" int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                 const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
-                                 double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    if (!rs_sizes_ok(sumF, N, views, H, W)) { tri_set_error("tri_raster_render: negative size"); return TRI_ERR_ARG; }
-    if (!(yfov > 0.0 && yfov < M_PI) || !(znear > 0.0)) { tri_set_error("tri_raster_render: yfov must lie in (0, pi) and znear above 0"); return TRI_ERR_ARG; }
-    if (sumF >= (1L << 31)) { tri_set_error("tri_raster_render: 2^31 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
-    if (views > 65535) { tri_set_error("tri_raster_render: more than 65535 views"); return TRI_ERR_UNSUPPORTED; }
+static int rs_render(const MeshBatch& m, bool tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+                     void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
+    const int N = m.N;
+    char msg[160];
+    if (!rs_sizes_ok(sumF, N, views, H, W)) { snprintf(msg, sizeof msg, "%s: negative size", who); tri_set_error(msg); return TRI_ERR_ARG; }
+    if (!(yfov > 0.0 && yfov < M_PI) || !(znear > 0.0)) {
+        snprintf(msg, sizeof msg, "%s: yfov must lie in (0, pi) and znear above 0", who); tri_set_error(msg); return TRI_ERR_ARG;
+    }
+    if (sumF >= (1L << 31)) { snprintf(msg, sizeof msg, "%s: 2^31 or more faces in a batch", who); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
+    if (views > 65535) { snprintf(msg, sizeof msg, "%s: more than 65535 views", who); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
     if ((double)N * views * H * W >= (double)RS_MAX_PIXELS) {
-        tri_set_error("tri_raster_render: 2^31 or more pixels (a visibility buffer of 16 GiB or more) in one launch");
+        snprintf(msg, sizeof msg, "%s: 2^31 or more pixels (a visibility buffer of 16 GiB or more) in one launch", who);
+        tri_set_error(msg);
         return TRI_ERR_UNSUPPORTED;
     }
     const long npix = (long)N * views * H * W;
@@ -236,14 +328,49 @@ extern "C" int tri_raster_render(const float* verts, const int* faces, const lon
     const u64 qcap = (u64)sumF * views;
     const double fyd = 1.0 / tan(yfov / 2.0);
     const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
     raster_clear_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(keys, npix, qcount);
     if (sumF > 0) {
         raster_faces_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
             m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
         raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
     }
-    raster_resolve_kernel<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H * W, npix, keys, image,
-                                                                                                   visibility);
-    return tri_check_launch("tri_raster_render");
+    const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
+    if (tex) raster_resolve_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    else raster_resolve_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
+    return tri_check_launch(who);
+}
+
+extern "C" int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                 const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
+                                 double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
+    return rs_render(m, false, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
+}
+
+extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                     const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
+                                     int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    if (T < 0) { tri_set_error("tri_raster_render_tex: negative size"); return TRI_ERR_ARG; }
+    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
+        tri_set_error("tri_raster_render_tex: T > 0 needs all five texture fields");
+        return TRI_ERR_ARG;
+    }
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    return rs_render(m, true, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_tex");
+}
+
+extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                     const long* tex_off, const int* tex_size, int T, int N, long sumF, float* colours, void* stream) {
+    if (N < 0 || sumF < 0 || T < 0) { tri_set_error("tri_mesh_face_colours: negative size"); return TRI_ERR_ARG; }
+    if (sumF >= (1L << 31)) { tri_set_error("tri_mesh_face_colours: 2^31 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
+    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
+        tri_set_error("tri_mesh_face_colours: T > 0 needs all five texture fields");
+        return TRI_ERR_ARG;
+    }
+    if (sumF == 0 || N == 0) return TRI_OK;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    mesh_face_colours_kernel<<<(unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, (hipStream_t)stream>>>(m, sumF, colours);
+    return tri_check_launch("tri_mesh_face_colours");
 }

@@ -1,7 +1,9 @@
 """Per-face diffuse colours of a Wavefront OBJ: the `usemtl` groups of the file and the `Kd` of the `mtllib` files next to it,
-as far as the renderer of data/render.py uses them (map_Kd textures and every other MTL statement are ignored)."""
+as far as the renderer of data/render.py uses them.  load_obj_materials ignores map_Kd textures (and every other MTL statement);
+load_obj_textured also reads the `vt` texture coordinates and decodes the map_Kd images for ops.render_views_textured."""
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -61,3 +63,98 @@ def load_obj_materials(path):
     if face_material.shape[0] != faces.shape[0]:
         raise ValueError(f"{path}: {face_material.shape[0]} material entries for {faces.shape[0]} faces")
     return verts, faces, face_material, torch.from_numpy(np.asarray(kd, dtype=np.float32).reshape(-1, 3)), names
+
+
+def load_mtl_textures(path):
+    """-> {name: map_Kd file name or None} in file order.  The file name is the LAST token of the map_Kd line (options such as
+    `-s 1 1 1` are skipped), with backslashes turned into slashes."""
+    out = {}
+    name = None
+    with open(path, "rb") as f:
+        for ln in f.read().replace(b"\r", b"").split(b"\n"):
+            tok = ln.split()
+            if len(tok) >= 2 and tok[0] == b"newmtl":
+                name = b" ".join(tok[1:]).decode(errors="replace")
+                out.setdefault(name, None)
+            elif len(tok) >= 2 and tok[0] == b"map_Kd" and name is not None:
+                out[name] = tok[-1].decode(errors="replace").replace("\\", "/")
+    return out
+
+
+def load_texture(path, max_texture_size=256):
+    """An image file -> uint8 [H, W, 4] RGBA (alpha 255), row 0 the top row: decoded with PIL, converted to RGB (from greyscale,
+    palette or RGBA), and reduced by the smallest integer box factor (PIL's Image.reduce) that brings both sides to at most
+    max_texture_size - the renderer has no mip-maps, this bounds its minification.  Raises what PIL raises."""
+    from PIL import Image
+    with Image.open(path) as img:
+        img = img.convert("RGB")
+        factor = int(math.ceil(max(img.size) / float(max_texture_size)))
+        if factor > 1:
+            img = img.reduce(factor)
+        rgb = np.asarray(img, dtype=np.uint8)
+    return np.concatenate([rgb, np.full(rgb.shape[:2] + (1,), 255, np.uint8)], axis=2)
+
+
+def load_obj_textured(path, max_texture_size=256):
+    """load_obj_materials plus textures -> (verts, faces, face_material, Kd, names, face_uv, mat_tex, textures, warnings):
+    face_uv float32 [F, 3, 2], the `vt u v [w]` of every face corner in the order of `faces` (tokens i/j and i/j/k; 1-based, negative
+    = counted back from the vt lines read so far; polygons fan like their vertices) - all six values NaN for a face with a corner
+    that has no vt (tokens i and i//k, or an index outside the file's vt lines); mat_tex int32 [M], per material an index into
+    textures or -1; textures, a list of uint8 [H, W, 4] arrays (load_texture) of the map_Kd files, looked up relative to the MTL file
+    that names them, one entry per distinct file; warnings, a list of strings, one per map_Kd that could not be loaded (a missing
+    or unreadable file, no PIL) - such a material stays untextured, nothing is raised."""
+    verts, faces, face_material, kd, names = load_obj_materials(path)
+    with open(path, "rb") as f:
+        lines = [ln.strip() for ln in f.read().replace(b"\r", b"").split(b"\n")]
+    here = os.path.dirname(os.path.abspath(path))
+    mat_tex = np.full((len(names),), -1, np.int32)
+    textures, loaded, warnings, seen = [], {}, [], set()
+    for ln in lines:
+        if ln[:7] not in (b"mtllib ", b"mtllib\t"):
+            continue
+        for lib in ln.split()[1:]:
+            lib_path = os.path.join(here, lib.decode(errors="replace"))
+            if not os.path.isfile(lib_path):
+                continue
+            for name, file_name in load_mtl_textures(lib_path).items():
+                if name in seen or name not in names:
+                    continue
+                seen.add(name)                                                           # the first definition counts, as for Kd
+                if file_name is None:
+                    continue
+                tex_path = os.path.normpath(os.path.join(os.path.dirname(lib_path), file_name))
+                if tex_path not in loaded:
+                    try:
+                        textures.append(load_texture(tex_path, max_texture_size))
+                        loaded[tex_path] = len(textures) - 1
+                    except Exception as e:                                               # never raises: the material stays untextured
+                        loaded[tex_path] = -1
+                        warnings.append(f"{tex_path}: {type(e).__name__}: {e}")
+                mat_tex[names.index(name)] = loaded[tex_path]
+    vt, uv = [], []
+    nan = (math.nan, math.nan)
+    for ln in lines:
+        head = ln[:3]
+        if head in (b"vt ", b"vt\t"):
+            tok = ln.split()
+            try:
+                vt.append((float(tok[1]), float(tok[2])))
+            except (IndexError, ValueError):
+                vt.append(nan)
+        elif head[:2] in (b"f ", b"f\t"):
+            corner = []
+            for tok in ln.split()[1:]:
+                part = tok.split(b"/")
+                try:
+                    j = int(part[1]) if len(part) >= 2 and part[1] else 0
+                except ValueError:
+                    j = 0
+                j = j - 1 if j > 0 else len(vt) + j if j < 0 else -1
+                corner.append(vt[j] if 0 <= j < len(vt) else nan)
+            for k in range(1, len(corner) - 1):
+                tri = (corner[0], corner[k], corner[k + 1])
+                uv.append(tri if all(c[0] == c[0] and c[1] == c[1] for c in tri) else (nan, nan, nan))
+    face_uv = torch.from_numpy(np.asarray(uv, dtype=np.float64).astype(np.float32).reshape(-1, 3, 2))
+    if face_uv.shape[0] != faces.shape[0]:
+        raise ValueError(f"{path}: {face_uv.shape[0]} texture coordinate rows for {faces.shape[0]} faces")
+    return verts, faces, face_material, kd, names, face_uv, torch.from_numpy(mat_tex), textures, warnings

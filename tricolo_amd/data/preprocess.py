@@ -2,7 +2,7 @@
 splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
-        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto]
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
@@ -10,7 +10,14 @@ shapenet.json; for Text2ShapeC13 the existing map file is read instead - and `<e
 with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V]) and images (uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
 `<dirname(dataset_path)>/ShapeNetCore.v2/<category>/<model_id>/models/model_normalized.obj` by ops.render_views (csrc/raster.hip), a
 batch of meshes per call.  data/render.py says what that renderer restates of the reference's pyrender scene, what it deliberately
-does differently (Lambert shading, flat normals, no culling, no textures) and that no pixel has been compared with pyrender's.
+does differently (Lambert shading, flat normals, no culling, textures only on request) and that no pixel has been compared with
+pyrender's.
+
+--textures on (the default is off: a textured material renders with its bare Kd) reads the `vt` coordinates and the map_Kd images
+of the models (data/materials.py load_obj_textured; textures above 256 texels on a side are reduced) and renders through
+ops.render_views_textured: Kd x texel, repeat wrap, bilinear, no mip-maps.  Voxels made from the meshes (--voxels mesh | auto) then
+take one colour per face, ops.mesh_face_colours: Kd times the mean of four texture samples of the face.  The summary names the
+models with at least one loaded texture and the map_Kd files that could not be loaded (such a material keeps its Kd).
 
 --voxels says where the grids come from.  nrrd (the default): Text2Shape's nrrd_256_filter_div_{V}_solid/<id>/<id>.nrrd downloads
 (data/nrrd.py), which exist for chairs and tables only.  mesh: ops.voxelize_meshes (csrc/voxelize.hip) voxelises the meshes already
@@ -39,12 +46,13 @@ import torch
 from .. import config as tcfg
 from ..meshes import MeshBatch
 from . import render, voxelize
-from .materials import load_obj_materials
+from .materials import load_obj_materials, load_obj_textured
 from .nrrd import read_nrrd
 
 VOXEL_SIZES = (32, 64, 128)
 SPLITS = ("train", "val", "test")
 VOXEL_SOURCES = ("nrrd", "mesh", "auto")
+TEXTURE_MODES = ("off", "on")
 
 
 def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
@@ -96,20 +104,38 @@ def nrrd_path(data_root, mid, v):
     return os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd")
 
 
-def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd"):
+def pack_batch(meshes, device, textures=False):
+    """MeshBatch.pack of load_obj_materials' (or, with textures, load_obj_textured's) tuples; with textures the voxeliser's batch too."""
+    if not textures:
+        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device)
+        return packed, packed
+    from .. import ops
+    packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_uv_list=[m[5] for m in meshes],
+                            mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes])
+    return packed, packed.with_face_colours(ops.mesh_face_colours(packed))
+
+
+def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd",
+                textures=False, texture_stats=None):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
-    come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist)."""
+    come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist).
+    textures: read and render map_Kd textures, and colour mesh voxels from them; texture_stats, a dict, then gains the number of
+    "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded)."""
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
+    load = load_obj_textured if textures else load_obj_materials
     for i in range(0, len(todo), batch_meshes):
         batch = todo[i:i + batch_meshes]
-        meshes = [load_obj_materials(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
-        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device)
-        images = render.render_batch(packed, num_views, render.IMAGE_SIZE).cpu().numpy()
+        meshes = [load(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
+        if textures and texture_stats is not None:
+            texture_stats["textured_models"] = texture_stats.get("textured_models", 0) + sum(1 for m in meshes if len(m[7]))
+            texture_stats["texture_failures"] = texture_stats.get("texture_failures", 0) + sum(len(m[8]) for m in meshes)
+        packed, solid = pack_batch(meshes, device, textures)
+        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures).cpu().numpy()
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
         if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
-            packed = MeshBatch.pack(*zip(*(meshes[k][:4] for k in from_mesh)), device=device)
-        made = {f"voxel{v}": voxelize.voxelize_batch(packed, v, fill="carve").cpu().numpy() for v in VOXEL_SIZES} if from_mesh else {}
+            solid = pack_batch([meshes[k] for k in from_mesh], device, textures)[1]
+        made = {f"voxel{v}": voxelize.voxelize_batch(solid, v, fill="carve").cpu().numpy() for v in VOXEL_SIZES} if from_mesh else {}
         for k, ((cat, mid), views) in enumerate(zip(batch, images)):
             if k in from_mesh:
                 grids = {name: g[from_mesh.index(k)] for name, g in made.items()}
@@ -126,7 +152,7 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
 
 
 def main(argv=None, log=print):
-    """-> {split: {"models", "written", "skipped"}}."""
+    """-> {split: {"models", "written", "skipped"}}, with --textures on also "textured_models" and "texture_failures"."""
     ap = argparse.ArgumentParser(prog="python -m tricolo_amd.data.preprocess", description=__doc__.split("\n\n")[0])
     ap.add_argument("overrides", nargs="*", help="config overrides, e.g. data=text2shape_chair_table data.dataset_root_path=...")
     ap.add_argument("--batch-meshes", type=int, default=8, help="meshes rendered per call")
@@ -134,6 +160,8 @@ def main(argv=None, log=print):
     ap.add_argument("--device", default="cuda", help="cuda (csrc/raster.hip, csrc/voxelize.hip) or cpu (the untuned torch restatements)")
     ap.add_argument("--voxels", choices=VOXEL_SOURCES, default="nrrd", help="the grids: the nrrd_256_filter_div_{V}_solid downloads, voxelised "
                     "from the meshes, or auto (the downloads where all three sizes exist for a model)")
+    ap.add_argument("--textures", choices=TEXTURE_MODES, default="off", help="on: render map_Kd textures (ops.render_views_textured) and colour "
+                    "mesh voxels from them; off: a textured material renders with its bare Kd")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.batch_meshes < 1:
         ap.error("--batch-meshes must be positive")
@@ -149,10 +177,13 @@ def main(argv=None, log=print):
                                                    os.path.join(data.dataset_path, "shapenet.json"), map_path, data.ignored_models)
         else:
             keys = read_model_ids(map_path)
+        tex = {"textured_models": 0, "texture_failures": 0} if args.textures == "on" else {}
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
-                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels)
-        stats[split] = {"models": len(keys), "written": written, "skipped": skipped}
+                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, args.textures == "on", tex)
+        stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")
+        if tex:
+            log(f"  {tex['textured_models']} of the written models have a texture, {tex['texture_failures']} map_Kd files could not be loaded")
     return stats
 
 

@@ -12,13 +12,16 @@ Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliber
   * Lambert diffuse plus ambient, Kd (0.1 + 3/pi max(n . l, 0)), instead of pyrender's metallic-roughness BRDF;
   * flat face normals (no vertex normals, no smoothing), turned toward the eye;
   * no back-face culling: both sides of a face are drawn (ShapeNet's winding is unreliable);
-  * map_Kd textures are ignored: a textured material renders with its Kd;
+  * map_Kd textures are opt-in (ops.render_views_textured, textures=True below; the default renders a textured material with its
+    bare Kd): colour = Kd x texel, the MTL rule and - from their documentation - what trimesh's SimpleMaterial becomes in pyrender
+    (baseColorFactor x baseColorTexture); repeat wrap, bilinear over texel centres at the perspective-correct (u, v) of the pixel
+    centre, NO mip-maps (the parser bounds minification by reducing textures to 256 texels on a side), no gamma;
   * no near-plane clipping: a face with a vertex nearer than znear is dropped whole.  model_normalized.obj lies within 0.5 of its
     centre and the camera stands 0.85 away, so no face of such a mesh comes near the plane; no anti-aliasing either.
 
 On GPU tensors ops.render_views launches the HIP kernels; on CPU tensors the same call runs render_views_cpu below, a torch
 restatement of the kernel's arithmetic (spelled out at the head of csrc/raster.hip) that gives the same bits.  It exists for
-checking and for machines without a GPU and is not tuned.
+checking and for machines without a GPU and is not tuned.  ops.render_views_textured and ops.mesh_face_colours have theirs here too.
 """
 from __future__ import annotations
 
@@ -34,6 +37,9 @@ DISTANCE, ELEVATION = 0.85, math.pi / 5
 SNAP_MAX = float(2 ** 20)
 KDIFF = float(np.float32(3.0 / math.pi))
 CANDIDATES_PER_PASS = 1 << 21                       # (face, pixel) pairs the fallback expands at a time
+B13, B23, B16 = (float(np.float32(c)) for c in ("0.33333334", "0.6666667", "0.16666667"))      # csrc/raster.hip RS_B13, RS_B23, RS_B16
+FACE_SAMPLES = ((B13, B13, B13), (B23, B16, B16), (B16, B23, B16), (B16, B16, B23))
+TEXEL_VALUE = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0))           # byte / 255, correctly rounded
 
 
 # ------------------------------------------------------------------------------------------------ cameras
@@ -104,17 +110,19 @@ def snap_vertices(verts, cam, H, W, yfov, znear):
     return front & inside, X, Y, 1.0 / z
 
 
-def project_faces(verts, faces, cam, H, W, yfov, znear):
+def project_faces(verts, faces, cam, H, W, yfov, znear, with_order=False):
     """Setup of csrc/raster.hip for one mesh and one view.  verts fp32 [V, 3], faces int64 [F, 3] (already clamped to the mesh),
     cam fp32 [12] -> (keep bool [F], X int64 [F, 3], Y int64 [F, 3], d fp32 [F, 3], A2 int64 [F]) with vertices 1 and 2 swapped
-    where the doubled area was negative; keep is False for dropped faces (behind znear, off the snap range, zero area)."""
+    where the doubled area was negative; keep is False for dropped faces (behind znear, off the snap range, zero area).
+    with_order: also order int64 [F, 3], the corner each of the three positions came from ((0, 2, 1) for a swapped face)."""
     okv, Xv, Yv, dv = snap_vertices(verts, cam, H, W, yfov, znear)
     X, Y, d = Xv[faces], Yv[faces], dv[faces]
     A2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (X[:, 2] - X[:, 0]) * (Y[:, 1] - Y[:, 0])
     keep = okv[faces].all(dim=1) & (A2 != 0)
     flip = A2 < 0
     order = torch.where(flip[:, None], torch.tensor([0, 2, 1]), torch.tensor([0, 1, 2]))
-    return keep, X.gather(1, order), Y.gather(1, order), d.gather(1, order), A2.abs()
+    out = (keep, X.gather(1, order), Y.gather(1, order), d.gather(1, order), A2.abs())
+    return out + (order,) if with_order else out
 
 
 def _visibility_one(verts, faces, cam, H, W, yfov, znear):
@@ -165,8 +173,68 @@ def _visibility_one(verts, faces, cam, H, W, yfov, znear):
     return keys
 
 
-def _shade_one(verts, faces, face_mat, kd, cam, vis):
-    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background)."""
+def face_textures(face_mat, mat_tex, face_uv, T):
+    """int64 [F]: the (clamped, batch-global) texture of every face of one mesh, -1 for none (csrc/mesh_batch.h mb_face_tex);
+    mat_tex: the mesh's rows of the batch's table."""
+    if T <= 0 or mat_tex.shape[0] == 0:
+        return torch.full((face_mat.shape[0],), -1, dtype=torch.int64)
+    t = mat_tex[clamp_index(face_mat, mat_tex.shape[0])].to(torch.int64)
+    none = (t == -1) | torch.isnan(face_uv[:, 0, 0])
+    return torch.where(none, torch.full_like(t, -1), clamp_index(t, T))
+
+
+def sample_textures(t, u, v, texels, tex_off, tex_size):
+    """csrc/mesh_batch.h mb_tex_sample: textures t int64 [P] (0 <= t < T) at u, v fp32 [P] -> (ok bool [P], c fp32 [P, 3]); rows of c
+    with ok False (a non-finite u or v) mean nothing."""
+    ok = torch.isfinite(u) & torch.isfinite(v)
+    u, v = torch.where(ok, u, torch.zeros_like(u)), torch.where(ok, v, torch.zeros_like(v))
+    Ht, Wt = tex_size[t, 0].to(torch.int64), tex_size[t, 1].to(torch.int64)
+    u, v = u - torch.floor(u), v - torch.floor(v)
+    x, y = u * Wt.to(torch.float32) - 0.5, (1.0 - v) * Ht.to(torch.float32) - 0.5
+    xf, yf = torch.floor(x), torch.floor(y)
+    fx, fy = (x - xf)[:, None], (y - yf)[:, None]
+    xa, ya = torch.remainder(xf.to(torch.int64), Wt), torch.remainder(yf.to(torch.int64), Ht)
+    xb, yb = torch.where(xa + 1 == Wt, torch.zeros_like(xa), xa + 1), torch.where(ya + 1 == Ht, torch.zeros_like(ya), ya + 1)
+    base, last = tex_off[t], int(tex_off[-1]) - 1
+
+    def texel(row, col):
+        return TEXEL_VALUE[texels[(base + row * Wt + col).clamp(0, last), :3].to(torch.int64)]
+
+    t00, t10, t01, t11 = texel(ya, xa), texel(ya, xb), texel(yb, xa), texel(yb, xb)
+    a, b = t00 + (t10 - t00) * fx, t01 + (t11 - t01) * fx
+    return ok, a + (b - a) * fy
+
+
+def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size):
+    """(has bool [HW], c fp32 [HW, 3]) of one mesh and one view: where the winning face of vis int64 [HW] is textured, and the
+    texture colour at the perspective-correct (u, v) of the pixel centre."""
+    has = torch.zeros((vis.numel(),), dtype=torch.bool)
+    c = torch.ones((vis.numel(), 3), dtype=torch.float32)
+    pix = torch.nonzero((vis >= 0) & (face_t[vis.clamp(min=0)] >= 0)).reshape(-1)
+    if pix.numel() == 0:
+        return has, c
+    _, X, Y, d, A2, order = project_faces(verts, faces, cam, H, W, yfov, znear, with_order=True)
+    f = vis[pix]
+    Px, Py = 256 * (pix % W) + 128, 256 * torch.div(pix, W, rounding_mode="floor") + 128
+    fa = A2[f].to(torch.float32)
+    w = []
+    for k in range(3):
+        a, b = (k + 1) % 3, (k + 2) % 3
+        e = (X[f, b] - X[f, a]) * (Py - Y[f, a]) - (Y[f, b] - Y[f, a]) * (Px - X[f, a])
+        w.append((e.to(torch.float32) / fa) * d[f, k])
+    dd = (w[0] + w[1]) + w[2]
+    bw = [wk / dd for wk in w]
+    uv = face_uv[f].gather(1, order[f][:, :, None].expand(-1, 3, 2))
+    u = (bw[0] * uv[:, 0, 0] + bw[1] * uv[:, 1, 0]) + bw[2] * uv[:, 2, 0]
+    v = (bw[0] * uv[:, 0, 1] + bw[1] * uv[:, 1, 1]) + bw[2] * uv[:, 2, 1]
+    ok, col = sample_textures(face_t[f], u, v, texels, tex_off, tex_size)
+    has[pix[ok]] = True
+    c[pix[ok]] = col[ok]
+    return has, c
+
+
+def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
+    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background); tex: _texels_one's pair."""
     out = torch.full((3, vis.numel()), 255, dtype=torch.uint8)
     pix = torch.nonzero(vis >= 0).reshape(-1)
     if pix.numel() == 0:
@@ -181,14 +249,18 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis):
     ny = cy / torch.where(ok, length, torch.ones_like(length))
     ndl = torch.where(ok, torch.where(side < 0, -ny, ny).clamp(min=0.0), torch.zeros_like(ny))
     shade = 0.1 + _f32(KDIFF) * ndl
-    rgb = torch.floor(255.0 * (face_kd(face_mat[f], kd) * shade[:, None]).clamp(0.0, 1.0) + 0.5).to(torch.uint8)
+    colour = face_kd(face_mat[f], kd)
+    if tex is not None:
+        colour = torch.where(tex[0][pix][:, None], colour * tex[1][pix], colour)
+    rgb = torch.floor(255.0 * (colour * shade[:, None]).clamp(0.0, 1.0) + 0.5).to(torch.uint8)
     out[:, pix] = rgb.t()
     return out
 
 
 def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
-                     return_visibility=False):
-    """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch."""
+                     return_visibility=False, textures=None):
+    """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch.  textures: the five
+    texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured."""
     voff, foff, moff = vert_off.tolist(), face_off.tolist(), mat_off.tolist()
     N, views = len(voff) - 1, cam.shape[1]
     image = torch.full((N, views, 3, H, W), 255, dtype=torch.uint8)
@@ -204,21 +276,55 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
             keys = _visibility_one(v, f, cam[n, k], H, W, yfov, znear)
             face = torch.where(keys != 0, 0xFFFFFFFF - (keys & 0xFFFFFFFF), torch.full_like(keys, -1))
             vis[n, k] = face.to(torch.int32).view(H, W)
-            image[n, k] = _shade_one(v, f, fm, kd, cam[n, k], face).view(3, H, W)
+            tex = None
+            if textures is not None:
+                face_uv, mat_tex, texels, tex_off, tex_size = textures
+                uv = face_uv[foff[n]:foff[n + 1]]
+                face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
+                tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size)
+            image[n, k] = _shade_one(v, f, fm, kd, cam[n, k], face, tex).view(3, H, W)
     return (image, vis) if return_visibility else image
 
 
+def mesh_face_colours_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size):
+    """ops.mesh_face_colours on CPU tensors -> fp32 [sumF, 3]: Kd, for a textured face times the mean of the four samples of
+    FACE_SAMPLES (summed in their order, times 0.25); the UVs are used affinely."""
+    foff, moff = face_off.tolist(), mat_off.tolist()
+    out = torch.empty((faces.shape[0], 3), dtype=torch.float32)
+    for n in range(len(foff) - 1):
+        fm, uv = face_mat[foff[n]:foff[n + 1]], face_uv[foff[n]:foff[n + 1]]
+        colour = face_kd(fm, mat_kd[moff[n]:moff[n + 1]])
+        face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
+        sel = torch.nonzero(face_t >= 0).reshape(-1)
+        if sel.numel():
+            t, q = face_t[sel], uv[sel]
+            ok, total = torch.ones_like(sel, dtype=torch.bool), None
+            for b0, b1, b2 in FACE_SAMPLES:
+                good, c = sample_textures(t, (b0 * q[:, 0, 0] + b1 * q[:, 1, 0]) + b2 * q[:, 2, 0],
+                                          (b0 * q[:, 0, 1] + b1 * q[:, 1, 1]) + b2 * q[:, 2, 1], texels, tex_off, tex_size)
+                ok, total = ok & good, c if total is None else total + c
+            colour[sel[ok]] = colour[sel[ok]] * (total[ok] * 0.25)
+        out[foff[n]:foff[n + 1]] = colour
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the convenient calls
-def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False):
+def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False):
     """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
     [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
-    ops.render_views."""
+    ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures)."""
     from .. import ops
     cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
     H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
+    if textures:
+        return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility)
     return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility)
 
 
-def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False):
-    """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None)."""
-    return render_batch(MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device), num_views, image_size, return_visibility)
+def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False,
+                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None):
+    """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None); textures=True
+    needs the three texture lists of MeshBatch.pack."""
+    batch = MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device, face_uv_list=face_uv_list, mat_tex_list=mat_tex_list,
+                           textures_list=textures_list)
+    return render_batch(batch, num_views, image_size, return_visibility, textures)

@@ -1,5 +1,5 @@
 """The packed batch of triangle meshes that the sampler, the renderer and the voxeliser share (csrc/mesh_batch.h lays it out): reading
-OBJ files, validating and packing lists of meshes on the host, the float64 bounding boxes the cameras and voxel frames come from, and
+OBJ files, validating and packing lists of meshes (with their materials and, on request, their textures) on the host, the float64 bounding boxes the cameras and voxel frames come from, and
 the three conventions of the kernels that the torch restatements in evaluation/mesh.py, data/render.py and data/voxelize.py have in
 common - the unsigned clamp of a bad index, the diffuse colour of a face, the fp32 cross product."""
 from __future__ import annotations
@@ -97,6 +97,57 @@ def pack_materials(face_mat_list, kd_list, device=None):
             torch.cat([kd.to(device) for kd in kd_list]).contiguous(), torch.tensor(moff, dtype=torch.int64, device=device))
 
 
+TEXTURE_MAX_SIDE = 2 ** 24                                                         # texel positions are formed in fp32
+
+
+def check_textures(face_uv, mat_tex, texels, tex_off, tex_size, num_faces, num_materials):
+    """The five texture fields of csrc/mesh_batch.h, validated on the host (ValueError): shapes and dtypes, mat_tex in [-1, T), every
+    texture 1 <= H, W <= 2^24, tex_off the running sum of H * W ending at the number of texels."""
+    for name, x, dtype, tail in (("face_uv", face_uv, torch.float32, (3, 2)), ("mat_tex", mat_tex, torch.int32, ()),
+                                 ("texels", texels, torch.uint8, (4,)), ("tex_off", tex_off, torch.int64, ()), ("tex_size", tex_size, torch.int32, (2,))):
+        if not torch.is_tensor(x) or x.dtype != dtype or x.dim() != 1 + len(tail) or tuple(x.shape[1:]) != tail:
+            raise ValueError(f"{name} must be a {dtype} tensor of shape {['*', *tail]}")
+    T = tex_size.shape[0]
+    if face_uv.shape[0] != num_faces or mat_tex.shape[0] != num_materials or tex_off.shape[0] != T + 1:
+        raise ValueError(f"textures: {face_uv.shape[0]} face_uv rows for {num_faces} faces, {mat_tex.shape[0]} mat_tex entries for "
+                         f"{num_materials} materials, {tex_off.shape[0]} offsets for {T} textures")
+    if mat_tex.numel() and (int(mat_tex.min()) < -1 or int(mat_tex.max()) >= T):
+        raise ValueError(f"mat_tex spans {int(mat_tex.min())} .. {int(mat_tex.max())} but the batch has {T} textures (-1 = none)")
+    size = tex_size.to("cpu", torch.int64)
+    if T and (int(size.min()) < 1 or int(size.max()) > TEXTURE_MAX_SIDE):
+        raise ValueError(f"every texture needs 1 <= H, W <= 2^24, got sizes from {int(size.min())} to {int(size.max())}")
+    want = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(size[:, 0] * size[:, 1], 0)])
+    if not torch.equal(tex_off.cpu(), want) or int(want[-1]) != texels.shape[0]:
+        raise ValueError("tex_off must be the running sum of H * W over tex_size and end at the number of texels")
+
+
+def pack_textures(face_uv_list, mat_tex_list, textures_list, device=None):
+    """Per mesh: face_uv fp32 [F, 3, 2] (a NaN row = no texture coordinates), mat_tex int [M] indexing that mesh's own list of
+    textures (-1 = none), textures a list of uint8 [H, W, 4] RGBA arrays or tensors (row 0 = top)
+    -> (face_uv, mat_tex with batch-global indices, texels u8 [sumTexels, 4], tex_off int64 [T + 1], tex_size int32 [T, 2])."""
+    device = device or "cpu"
+    mat_tex, texels, sizes, base = [], [], [], 0
+    for n, (mt, texs) in enumerate(zip(mat_tex_list, textures_list)):
+        mt = torch.as_tensor(mt).to(torch.int64).reshape(-1)
+        if mt.numel() and (int(mt.min()) < -1 or int(mt.max()) >= len(texs)):
+            raise ValueError(f"mesh {n}: texture indices span {int(mt.min())} .. {int(mt.max())} but the mesh has {len(texs)} textures (-1 = none)")
+        mat_tex.append(torch.where(mt < 0, mt, mt + base).to(torch.int32))
+        for k, tex in enumerate(texs):
+            tex = torch.as_tensor(tex)
+            if tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] != 4 or tex.shape[0] < 1 or tex.shape[1] < 1:
+                raise ValueError(f"mesh {n}: texture {k} must be a uint8 array of shape [H >= 1, W >= 1, 4]")
+            sizes.append((tex.shape[0], tex.shape[1]))
+            texels.append(tex.reshape(-1, 4))
+        base += len(texs)
+    off = [0]
+    for h, w in sizes:
+        off.append(off[-1] + h * w)
+    return (torch.cat([torch.as_tensor(uv).to(device) for uv in face_uv_list]).contiguous() if face_uv_list else torch.zeros((0, 3, 2), device=device),
+            torch.cat(mat_tex).to(device).contiguous() if mat_tex else torch.zeros((0,), dtype=torch.int32, device=device),
+            torch.cat(texels).to(device).contiguous() if texels else torch.zeros((0, 4), dtype=torch.uint8, device=device),
+            torch.tensor(off, dtype=torch.int64, device=device), torch.tensor(sizes, dtype=torch.int32, device=device).reshape(-1, 2))
+
+
 def host_boxes(verts_list):
     """float64 [N, 3, 2]: per-axis (min, max) over all vertices of every mesh (tensors or arrays), zeros for a mesh without vertices.
     Minimum and maximum are exact, so whatever is derived from a box has the bits it would have from the vertices themselves."""
@@ -110,7 +161,8 @@ def host_boxes(verts_list):
 
 @dataclass
 class MeshBatch:
-    """A packed batch on one device; the three material tensors are None for a batch packed without materials."""
+    """A packed batch on one device; the three material tensors are None for a batch packed without materials, the five texture
+    tensors for a batch packed without textures."""
     verts: torch.Tensor
     faces: torch.Tensor
     vert_off: torch.Tensor
@@ -120,21 +172,58 @@ class MeshBatch:
     mat_off: torch.Tensor | None
     max_faces: int                                  # the largest face count of a mesh (sizes ops.mesh_face_cdf's grid)
     boxes: np.ndarray                               # host_boxes of the input lists
+    face_uv: torch.Tensor | None = None
+    mat_tex: torch.Tensor | None = None
+    texels: torch.Tensor | None = None
+    tex_off: torch.Tensor | None = None
+    tex_size: torch.Tensor | None = None
 
     @classmethod
-    def pack(cls, verts_list, faces_list, face_mat_list=None, kd_list=None, device=None):
-        """pack_meshes, then pack_materials where face_mat_list and kd_list are given; device=None: where verts_list[0] lives."""
+    def pack(cls, verts_list, faces_list, face_mat_list=None, kd_list=None, device=None, *, face_uv_list=None, mat_tex_list=None,
+             textures_list=None):
+        """pack_meshes, then pack_materials where face_mat_list and kd_list are given; device=None: where verts_list[0] lives.  With
+        face_uv_list, mat_tex_list and textures_list (all three, beside the materials) pack_textures adds the texture fields,
+        validated by check_textures."""
         verts, faces, voff, foff, max_faces = pack_meshes(verts_list, faces_list, device)
         mats = (None, None, None)
         if face_mat_list is not None:
             if len(face_mat_list) != len(faces_list) or any(fm.shape[0] != f.shape[0] for fm, f in zip(face_mat_list, faces_list)):
                 raise ValueError("every mesh needs one material index per face")
             mats = pack_materials(face_mat_list, kd_list, verts.device)
-        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list))
+        tex = (None,) * 5
+        given = [x is not None for x in (face_uv_list, mat_tex_list, textures_list)]
+        if any(given):
+            if not all(given) or face_mat_list is None:
+                raise ValueError("textures need face_uv_list, mat_tex_list and textures_list, and the materials they belong to")
+            if not len(face_uv_list) == len(mat_tex_list) == len(textures_list) == len(faces_list):
+                raise ValueError("every mesh needs its face_uv, mat_tex and list of textures")
+            for n, (uv, f, mt, kd) in enumerate(zip(face_uv_list, faces_list, mat_tex_list, kd_list)):
+                if not torch.is_tensor(uv) or uv.dtype != torch.float32 or tuple(uv.shape) != (f.shape[0], 3, 2):
+                    raise ValueError(f"mesh {n}: face_uv must be a float32 tensor of shape [{f.shape[0]}, 3, 2]")
+                if len(mt) != kd.shape[0]:
+                    raise ValueError(f"mesh {n}: {len(mt)} mat_tex entries for {kd.shape[0]} materials")
+            tex = pack_textures(face_uv_list, mat_tex_list, textures_list, verts.device)
+            check_textures(*tex, faces.shape[0], mats[1].shape[0])
+        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list), *tex)
 
     @property
     def tensors(self):                              # the first seven arguments of ops.render_views and ops.voxelize_meshes, in their order
         return self.verts, self.faces, self.vert_off, self.face_off, self.face_mat, self.mat_kd, self.mat_off
+
+    @property
+    def texture_tensors(self):                      # the next five arguments of ops.render_views_textured and ops.mesh_face_colours
+        return self.face_uv, self.mat_tex, self.texels, self.tex_off, self.tex_size
+
+    def with_face_colours(self, colours):
+        """The batch with one material per face, `colours` fp32 [sumF, 3] (ops.mesh_face_colours) as their Kd, and no textures: what
+        the voxeliser takes to colour its voxels from textures.  face_mat counts up within every mesh and mat_off = face_off."""
+        sumF = self.faces.shape[0]
+        if not torch.is_tensor(colours) or colours.dtype != torch.float32 or tuple(colours.shape) != (sumF, 3) or colours.device != self.verts.device:
+            raise ValueError(f"colours must be a float32 tensor of shape [{sumF}, 3] on the batch's device")
+        counts = self.face_off[1:] - self.face_off[:-1]
+        local = torch.arange(sumF, dtype=torch.int64, device=self.verts.device) - torch.repeat_interleave(self.face_off[:-1], counts)
+        return MeshBatch(self.verts, self.faces, self.vert_off, self.face_off, local.to(torch.int32), colours.contiguous(), self.face_off.clone(),
+                         self.max_faces, self.boxes)
 
 
 # ------------------------------------------------------------------------------------------------ shared by the torch restatements

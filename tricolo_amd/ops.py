@@ -1721,6 +1721,80 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     return (image, vis) if return_visibility else image
 
 
+def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size):
+    """Checks the five texture tensors of csrc/mesh_batch.h (meshes.MeshBatch.texture_tensors; their contents are validated where
+    they are packed) -> T."""
+    if any(x is None for x in (face_uv, mat_tex, texels, tex_off, tex_size)):
+        raise ValueError(f"{stage}: the batch was packed without textures (MeshBatch.pack(..., face_uv_list=, mat_tex_list=, textures_list=))")
+    if len({x.device for x in (faces, face_uv, mat_tex, texels, tex_off, tex_size)}) != 1:
+        raise ValueError(f"{stage}: all tensors must live on one device")
+    if face_uv.dtype != torch.float32 or tuple(face_uv.shape) != (faces.shape[0], 3, 2) or not face_uv.is_contiguous():
+        raise ValueError(f"face_uv must be a contiguous float32 tensor of shape [{faces.shape[0]}, 3, 2], got {tuple(face_uv.shape)} {face_uv.dtype}")
+    _mesh_arg(mat_tex, "mat_tex", torch.int32, numel=mat_kd.shape[0])
+    _mesh_arg(texels, "texels", torch.uint8, 4)
+    _mesh_arg(tex_size, "tex_size", torch.int32, 2)
+    T = tex_size.shape[0]
+    _mesh_arg(tex_off, "tex_off", torch.int64, numel=T + 1)
+    return T
+
+
+def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size, cam, H, W,
+                          yfov=math.pi / 3, znear=0.05, return_visibility=False):
+    """render_views with map_Kd textures: the packed batch and its five texture tensors (MeshBatch.tensors, MeshBatch.texture_tensors).
+    face_uv fp32 [sumF, 3, 2]: one (u, v) per face corner, NaN in face_uv[f, 0, 0] = the face has none; mat_tex int32 [sumM]: a
+    batch-global texture index per material, -1 = none; texels u8 [sumTexels, 4] RGBA; tex_off int64 [T + 1]; tex_size int32 [T, 2]
+    = (height, width), row 0 the top of the image, v = 0 its bottom.  Visibility is render_views'; a textured face is coloured
+    clamp((Kd c) shade, 0, 1), c the texture at the perspective-correct (u, v) of the pixel centre - repeat wrap, bilinear, NO
+    mip-maps (head of csrc/raster.hip) - and an untextured one exactly as by render_views.  Same limits; CPU tensors run the torch
+    restatement of data.render."""
+    H, W = int(H), int(W)
+    N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
+    T = _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
+    if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
+        raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
+    views, sumF = cam.shape[1], faces.shape[0]
+    if H < 0 or W < 0 or not (0.0 < float(yfov) < math.pi) or not float(znear) > 0.0:
+        raise ValueError("render_views_textured: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
+    if sumF >= 2 ** 31:
+        raise ValueError("render_views_textured: 2^31 or more faces in one batch")
+    if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
+        raise ValueError(f"render_views_textured: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
+                         f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
+    if not verts.is_cuda:
+        from .data.render import render_views_cpu
+        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
+                                textures=(face_uv, mat_tex, texels, tex_off, tex_size))
+    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
+    vis = torch.empty((N, views, H, W), dtype=torch.int32, device=verts.device) if return_visibility else None
+    ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+    check(lib().tri_raster_render_tex(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
+                                      ptr(face_uv), ptr(mat_tex), ptr(texels), ptr(tex_off), ptr(tex_size), T, ptr(cam), N, sumF, views, H, W,
+                                      float(yfov), float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_tex")
+    return (image, vis) if return_visibility else image
+
+
+def mesh_face_colours(batch):
+    """One colour per face of a meshes.MeshBatch packed with textures -> fp32 [sumF, 3]: Kd for an untextured face, else Kd times the
+    mean of four bilinear samples of its texture (barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of
+    the face's UVs, used affinely; head of csrc/raster.hip).  batch.with_face_colours(...) of it is what ops.voxelize_meshes takes to
+    colour voxels from textures.  CPU tensors run data.render.mesh_face_colours_cpu, the same arithmetic in torch."""
+    verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off = batch.tensors
+    if face_mat is None:
+        raise ValueError("mesh_face_colours: the batch was packed without materials")
+    N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, verts, stage="mesh_face_colours")
+    T = _mesh_textures("mesh_face_colours", faces, mat_kd, *batch.texture_tensors)
+    sumF = faces.shape[0]
+    if sumF >= 2 ** 31:
+        raise ValueError("mesh_face_colours: 2^31 or more faces in one batch")
+    if not verts.is_cuda:
+        from .data.render import mesh_face_colours_cpu
+        return mesh_face_colours_cpu(*batch.tensors, *batch.texture_tensors)
+    colours = torch.empty((sumF, 3), dtype=torch.float32, device=verts.device)
+    check(lib().tri_mesh_face_colours(*(ptr(x) for x in batch.tensors), *(ptr(x) for x in batch.texture_tensors), T, N, sumF, ptr(colours),
+                                      stream()), "tri_mesh_face_colours")
+    return colours
+
+
 # ------------------------------------------------------------------------------------------------ mesh voxelisation
 VOXELIZE_SIZES = (32, 64, 128)
 VOXELIZE_MAX_FACES, VOXELIZE_MAX_VOXELS = 2 ** 24, 2 ** 31                       # csrc/voxelize.hip VX_MAX_FACES, VX_MAX_VOXELS
