@@ -533,6 +533,22 @@ int tri_raster_render_tex(const float* verts, const int* faces, const long* vert
                           const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
                           double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
 
+/* Four coverage samples per pixel, for batches with and without textures (the texture fields null and T == 0: every face is
+ * untextured).  The sample positions, in 1/256 pixel from the pixel's top-left corner: (96, 32), (224, 96), (32, 160), (160, 224) - the
+ * 4x rotated grid, the centre is not among them.  Coverage, depth and the 64-bit key of a sample are tri_raster_render's rules at the
+ * sample's position instead of the pixel centre (same face set-up, top-left rule, atomic max).  Every sample is coloured as
+ * tri_raster_render_tex colours a pixel - a textured face from the perspective-correct (u, v) at the sample's own position - and the
+ * pixel is (c0 + c1 + c2 + c3 + 2) >> 2 per channel of the four u8 colours: a multisample resolve for untextured faces, 4x
+ * supersampling for textured ones.  image u8 [N][views][3][H][W]; visibility (optional) int32 [N][views][H][W][4]: the face at each
+ * sample, -1 for none.  workspace: tri_raster_workspace_aa(...) bytes, 16-byte aligned (0 for sizes the call refuses).  Limits of
+ * one call: those of tri_raster_render, with fewer than 2^31 SAMPLES (N views H W 4) in place of pixels.  The arithmetic is spelled
+ * out at the head of csrc/raster.hip. */
+size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W);
+int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                         const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                         const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
+                         double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
+
 /* One colour per face for the voxeliser: colours fp32 [sumF][3] = Kd for an untextured face, else Kd times the mean of four bilinear
  * samples of its texture, at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of the face's UVs (used
  * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped. */

@@ -5,7 +5,7 @@ views at 224 x 224 - and ops.mesh_face_colours on the same batch.  Two of the th
 [-2, 3]: textured and untextured pixels meet in the same waves.  HIP events, warmed; the two renderers alternate window by window in
 one process, and every window is reported, so the spread is on the page.  One JSON line per size.
 
-    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--trace-only RINGS]
+    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--trace-only RINGS]
     (--trace-only: three warmed calls of each for rocprofv3 --kernel-trace --stats, which gives the resolve kernels' own times)
 """
 import argparse
@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--samples", type=int, nargs="+", choices=(1, 4), default=[1], help="coverage samples per pixel of the two renderers; with "
+                    "1 4 the four-sample calls (render_views_4, render_views_textured_4) join the alternation")
     ap.add_argument("--trace-only", type=int, default=None, metavar="RINGS")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -61,6 +63,11 @@ def main():
         calls = {"render_views": lambda: ops.render_views(*packed.tensors, *tail),
                  "render_views_textured": lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail),
                  "mesh_face_colours": lambda: ops.mesh_face_colours(packed)}
+        if 4 in a.samples:
+            calls["render_views_4"] = lambda: ops.render_views(*packed.tensors, *tail, samples=4)
+            calls["render_views_textured_4"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, samples=4)
+        if 1 not in a.samples:
+            del calls["render_views"], calls["render_views_textured"]
         for fn in calls.values():
             for _ in range(3):
                 out = fn()
@@ -74,8 +81,10 @@ def main():
             for k, fn in calls.items():
                 ms[k].append(round(window(fn, a.iters), 4))
         med = {k: float(np.median(v)) for k, v in ms.items()}
+        ratios = {"textured_over_plain": ("render_views_textured", "render_views"), "textured_4_over_plain_4": ("render_views_textured_4", "render_views_4"),
+                  "textured_4_over_textured": ("render_views_textured_4", "render_views_textured")}
         print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "views": VIEWS, "size": SIZE, "texture": TEXTURE, "iters": a.iters, "ms_per_call": ms,
-                          "median_ms_per_call": med, "textured_over_plain": round(med["render_views_textured"] / med["render_views"], 4),
+                          "median_ms_per_call": med, **{k: round(med[x] / med[y], 4) for k, (x, y) in ratios.items() if x in med and y in med},
                           "pixels_changed_by_textures": float((plain != tex).any(dim=2).float().mean())}), flush=True)
 
 

@@ -32,10 +32,28 @@
 //     samples at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) - u = (b0 u0 + b1 u1) + b2 u2 with the
 //     fp32 constants RS_B13, RS_B23, RS_B16 - summed in that order and multiplied by 0.25f; Kd for a face without a texture or with
 //     a sample that is not finite.
+//   four samples per pixel (tri_raster_render_aa only; everything above is untouched by it): the positions, in 1/256 pixel from the
+//     pixel's top-left corner, are sample 0 (96, 32), 1 (224, 96), 2 (32, 160), 3 (160, 224) - the 4x rotated grid; the centre (128, 128)
+//     is not one of them.  Vertices are snapped to 1/256 pixel, so every position is an integer and coverage stays exact in int64.
+//     Coverage, depth and the key of a sample are the rules above evaluated at P = (256 px + ox, 256 py + oy) instead of the centre:
+//     the same face set-up (dropped faces, the swap, the snap range), E_k(sample) = E_k(centre) + (ox - 128)(-dy_k) + (oy - 128) dx_k,
+//     the top-left rule, l_k = fl32(E_k) / fl32(2A), d = (l0 d0 + l1 d1) + l2 d2, an atomic max over u64 [N][views][H][W][4], the
+//     sample innermost.  The box of candidate pixels holds every pixel with a sample inside the face's bounding box,
+//     ceil((Xmin - 224) / 256) .. floor((Xmax - 32) / 256) - up to a pixel wider on each side than the box of centres; results are
+//     defined by coverage, never by the box.  Every sample is coloured exactly as the pixel it would be above: 255 for none, u8 of
+//     clamp(Kd s, 0, 1) for an untextured face, and for a textured one (u, v) from the edge functions AT THE SAMPLE'S OWN POSITION,
+//     mb_tex_sample, clamp((Kd c) s, 0, 1), with the same fallback to Kd s.  The pixel is (c0 + c1 + c2 + c3 + 2) >> 2 per channel of the
+//     four u8 colours: a multisample resolve for untextured faces, 4x supersampling for textured ones - no attribute is ever
+//     extrapolated outside its face.  The visibility output is int32 [N][views][H][W][4], the face at each sample.
 //
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
+// The four-sample kernels keep that split (by their own box): a lane moves a cursor over its box's samples to ITS next covered one
+// with integer tests only - a pixel whose four samples all lie outside one edge (the largest of that edge's four offsets is still
+// negative) is stepped over whole - and only then runs the quotients and the atomic, so a wave runs that body once per covered
+// sample of its busiest lane, not once per sample of the box; the queue kernel's lanes tile the box's samples, so neighbouring lanes
+// touch neighbouring keys.
 #include <math.h>
 #include <stdio.h>
 
@@ -50,6 +68,8 @@
 #define RS_CLEAR_BLOCKS 2048
 #define RS_SNAP_MAX 1048576.f                   // 2^20 in 1/256 pixel
 #define RS_MAX_PIXELS (1L << 31)
+#define RS_AA_LO 32                             // the leftmost / topmost and the rightmost / lowest of the four samples, in 1/256 pixel
+#define RS_AA_HI 224
 #define RS_KDIFF 0.95492965f                    // fl32(3 / pi): intensity 3, Lambert's 1 / pi
 #define RS_B13 0.33333334f                      // fl32(1 / 3), fl32(2 / 3), fl32(1 / 6): the sample positions of the face colours
 #define RS_B23 0.6666667f
@@ -63,6 +83,10 @@ struct RsFace {
     int swap;                                   // 1 when vertices 1 and 2 changed places
 };
 
+// LO, HI: the box takes pixel px when 256 px + HI >= Xmin and 256 px + LO <= Xmax - (128, 128), the pixel centres, unless the caller
+// says otherwise; the four-sample kernels say (32, 224), the leftmost / topmost and the rightmost / lowest sample.  o.e is taken at the
+// centre of pixel (x0, y0) either way.
+template <int LO = 128, int HI = 128>
 __device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
                                          float fy, float znear, RsFace& o) {
     const long v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
@@ -100,10 +124,10 @@ __device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __rest
         A2 = -A2;
     }
     o.A2 = A2;
-    o.x0 = max(0, (min(X[0], min(X[1], X[2])) + 127) >> 8);             // ceil((X - 128) / 256)
-    o.x1 = min(W - 1, (max(X[0], max(X[1], X[2])) - 128) >> 8);         // floor((X - 128) / 256)
-    o.y0 = max(0, (min(Y[0], min(Y[1], Y[2])) + 127) >> 8);
-    o.y1 = min(H - 1, (max(Y[0], max(Y[1], Y[2])) - 128) >> 8);
+    o.x0 = max(0, (min(X[0], min(X[1], X[2])) + (255 - HI)) >> 8);      // ceil((X - HI) / 256): + 127 for the centres
+    o.x1 = min(W - 1, (max(X[0], max(X[1], X[2])) - LO) >> 8);          // floor((X - LO) / 256): - 128
+    o.y0 = max(0, (min(Y[0], min(Y[1], Y[2])) + (255 - HI)) >> 8);
+    o.y1 = min(H - 1, (max(Y[0], max(Y[1], Y[2])) - LO) >> 8);
     if (o.x0 > o.x1 || o.y0 > o.y1) return false;
     const long Px = 256L * o.x0 + 128, Py = 256L * o.y0 + 128;
 #pragma unroll
@@ -116,6 +140,16 @@ __device__ __forceinline__ bool rs_setup(const MeshBatch& m, const float* __rest
         o.bias[k] = (dy < 0 || (dy == 0 && dx > 0)) ? 0 : -1;
     }
     return true;
+}
+
+// Sample s of a pixel relative to its centre, in 1/256 pixel: (-32, -96), (96, -32), (-96, 32), (32, 96).
+__device__ __forceinline__ int rs_sample_x(int s) { return s == 0 ? -32 : s == 1 ? 96 : s == 2 ? -96 : 32; }
+__device__ __forceinline__ int rs_sample_y(int s) { return 64 * s - 96; }
+
+// What edge k of f gains from the centre of a pixel to its sample s: (ox - 128)(-dy) + (oy - 128) dx.  sx = -256 dy and sy = 256 dx
+// are exact multiples, |dx|, |dy| <= 2^21: below 2^29.
+__device__ __forceinline__ int rs_sample_step(const RsFace& f, int k, int s) {
+    return rs_sample_x(s) * (f.sx[k] >> 8) + rs_sample_y(s) * (f.sy[k] >> 8);
 }
 
 __device__ __forceinline__ void rs_pixel(const RsFace& f, long e0, long e1, long e2, u64* __restrict__ kp, unsigned low) {
@@ -183,6 +217,89 @@ __global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(MeshBatch m, c
     }
 }
 
+// ---- four samples per pixel: keys u64 [N][views][H][W][4] ----
+// n2 = half the number of keys: one 16-byte store per lane and step
+__global__ __launch_bounds__(RS_THREADS) void raster_clear_aa_kernel(ulonglong2* __restrict__ keys, long n2, u64* __restrict__ qcount) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *qcount = 0;
+    for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < n2; i += (long)gridDim.x * RS_THREADS) keys[i] = make_ulonglong2(0, 0);
+}
+
+// raster_faces_kernel with the samples' box; a lane keeps boxes of up to RS_SMALL x RS_SMALL PIXELS
+__global__ __launch_bounds__(RS_THREADS) void raster_faces_aa_kernel(MeshBatch m, const float* __restrict__ cam, long sumF, int views, int H, int W,
+                                                                     float fx, float fy, float znear, u64* __restrict__ keys,
+                                                                     u64* __restrict__ qcount, uint2* __restrict__ queue, u64 qcap) {
+    const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    const int view = blockIdx.y;
+    RsFace f;
+    bool live = false, big = false;
+    int n = 0;
+    long nv = 0;
+    if (gf < sumF) {
+        n = mb_mesh_of(m, gf);
+        nv = (long)n * views + view;
+        live = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, gf, n, nv, H, W, fx, fy, znear, f);
+        big = live && (f.x1 - f.x0 >= RS_SMALL || f.y1 - f.y0 >= RS_SMALL);
+    }
+    const u64 slot = mb_queue_slot(big, qcount);                        // every lane of the wave is here
+    if (big && slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
+    if (!live || big) return;
+    const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
+    int top[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        top[k] = max(max(rs_sample_step(f, k, 0), rs_sample_step(f, k, 1)), max(rs_sample_step(f, k, 2), rs_sample_step(f, k, 3)));
+    // A cursor (y, x, s) walks the box's samples row by row; r and e are the edge functions at the centres of pixel (x0, y) and (x, y).
+    u64* row = keys + ((size_t)nv * H + f.y0) * W * 4;
+    long r0 = f.e[0], r1 = f.e[1], r2 = f.e[2], e0 = r0, e1 = r1, e2 = r2;
+    int x = f.x0, y = f.y0, s = 0;
+    auto next_pixel = [&]() {
+        s = 0;
+        if (++x <= f.x1) { e0 += f.sx[0]; e1 += f.sx[1]; e2 += f.sx[2]; return; }
+        x = f.x0; ++y; row += (size_t)W * 4;
+        r0 += f.sy[0]; r1 += f.sy[1]; r2 += f.sy[2];
+        e0 = r0; e1 = r1; e2 = r2;
+    };
+    while (y <= f.y1) {
+        long c0 = 0, c1 = 0, c2 = 0;
+        bool hit = false;
+        while (y <= f.y1) {                                             // integer tests only: the lane stops at ITS next covered sample
+            if (s == 0 && ((e0 + top[0]) | (e1 + top[1]) | (e2 + top[2])) < 0) { next_pixel(); continue; }   // all four outside one edge
+            c0 = e0 + rs_sample_step(f, 0, s); c1 = e1 + rs_sample_step(f, 1, s); c2 = e2 + rs_sample_step(f, 2, s);
+            hit = ((c0 + f.bias[0]) | (c1 + f.bias[1]) | (c2 + f.bias[2])) >= 0;
+            if (hit) break;
+            if (++s == 4) next_pixel();
+        }
+        if (!hit) break;
+        rs_pixel(f, c0, c1, c2, row + 4 * (size_t)x + s, low);          // so the wave runs the quotients and the atomic once per covered sample
+        if (++s == 4) next_pixel();
+    }
+}
+
+// raster_queue_kernel with the samples' box; the lanes tile the box's SAMPLES (RS_THREADS is a multiple of 4: a lane keeps its sample)
+__global__ __launch_bounds__(RS_THREADS) void raster_queue_aa_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, float fx,
+                                                                     float fy, float znear, u64* __restrict__ keys,
+                                                                     const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
+    const u64 count = min(*qcount, qcap);
+    const int s = threadIdx.x & 3;
+    for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
+        const uint2 item = queue[q];
+        const long gf = item.x;
+        const int n = mb_mesh_of(m, gf);
+        const long nv = (long)n * views + (int)item.y;
+        RsFace f;
+        if (!rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;                   // the same answer in every lane
+        const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
+        const int bw = f.x1 - f.x0 + 1, cnt = bw * (f.y1 - f.y0 + 1);
+        const long s0 = f.e[0] + rs_sample_step(f, 0, s), s1 = f.e[1] + rs_sample_step(f, 1, s), s2 = f.e[2] + rs_sample_step(f, 2, s);
+        u64* box = keys + (((size_t)nv * H + f.y0) * W + f.x0) * 4 + s;
+        for (int i = threadIdx.x >> 2; i < cnt; i += RS_THREADS / 4) {
+            const int iy = i / bw, ix = i - iy * bw;
+            rs_pixel(f, s0 + (long)ix * f.sx[0] + (long)iy * f.sy[0], s1 + (long)ix * f.sx[1] + (long)iy * f.sy[1],
+                     s2 + (long)ix * f.sx[2] + (long)iy * f.sy[2], box + ((size_t)iy * W + ix) * 4, low);
+        }
+    }
+}
+
 // The flat Lambert shade s of the face (a, b, c) seen from `eye` (the camera's first three values).
 __device__ __forceinline__ float rs_shade(const float* a, const float* b, const float* c, const float* eye) {
     float x[3];
@@ -211,6 +328,20 @@ __device__ __forceinline__ bool rs_texel(const MeshBatch& m, const float* __rest
     const float l0 = mb_div((float)(double)(f.e[0] + dx * f.sx[0] + dy * f.sy[0]), fa);
     const float l1 = mb_div((float)(double)(f.e[1] + dx * f.sx[1] + dy * f.sy[1]), fa);
     const float l2 = mb_div((float)(double)(f.e[2] + dx * f.sx[2] + dy * f.sy[2]), fa);
+    const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
+    const float d = (w0 + w1) + w2;
+    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
+    return mb_tex_sample(m, t, (b0 * u0 + b1 * u1) + b2 * u2, (b0 * v0 + b1 * v1) + b2 * v2, c);
+}
+
+// rs_texel's arithmetic for a face the caller has set up, where its edge functions are e0, e1, e2 (the four-sample resolve sets a face
+// up once for the samples it won; rs_texel itself stays as it is so that the one-sample kernel's code does not move).
+__device__ __forceinline__ bool rs_texel_at(const MeshBatch& m, const RsFace& f, long gf, int t, long e0, long e1, long e2, float* c) {
+    const float* uv = m.face_uv + (size_t)gf * 6;
+    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
+    const float u0 = uv[0], v0 = uv[1], u1 = uv[2 * i1], v1 = uv[2 * i1 + 1], u2 = uv[2 * i2], v2 = uv[2 * i2 + 1];
+    const float fa = (float)(double)f.A2;
+    const float l0 = mb_div((float)(double)e0, fa), l1 = mb_div((float)(double)e1, fa), l2 = mb_div((float)(double)e2, fa);
     const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
     const float d = (w0 + w1) + w2;
     const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
@@ -268,6 +399,90 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_tex_kernel(MeshBatc
     rs_resolve<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
+// u8 of clamp(kd s, 0, 1), the colour rs_resolve writes
+__device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* c) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
+        c[k] = (int)(uint8_t)(int)floorf(255.f * col + 0.5f);
+    }
+}
+
+// one thread per pixel of the four-sample key buffer: every sample is coloured as rs_resolve colours a pixel - a textured face from (u, v)
+// at the sample's own position - and the pixel is the rounded integer mean.  A face met in the sample before is not shaded or set up
+// again, and an untextured one keeps its colour.
+template <bool TEX>
+__device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx,
+                                              float fy, float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                              int* __restrict__ visibility) {
+    const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (i >= npix) return;
+    const int HW = H * W;
+    const long nv = i / HW;
+    const int pix = (int)(i - nv * HW), n = (int)(nv / views);
+    const ulonglong2* kp = (const ulonglong2*)(keys + 4 * (size_t)i);               // the workspace is 16-byte aligned
+    const ulonglong2 ka = kp[0], kb = kp[1];
+    const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
+    const int px = pix % W, py = pix / W;
+    int sum[3] = {2, 2, 2}, col[3] = {255, 255, 255}, t = -1;
+    long prev = -1;
+    float shade = 0.f, kd[3] = {0.f, 0.f, 0.f};
+    bool set = false;
+    RsFace f;
+#pragma unroll 1
+    for (int s = 0; s < 4; ++s) {
+        const u64 key = s == 0 ? ka.x : s == 1 ? ka.y : s == 2 ? kb.x : kb.y;
+        const long lf = (long)(0xFFFFFFFFu - (unsigned)key);
+        const bool none = key == 0 || lf >= F || V <= 0;
+        if (visibility) visibility[4 * (size_t)i + s] = none ? -1 : (int)lf;
+        if (none) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sum[k] += 255;
+            continue;
+        }
+        if (lf != prev) {
+            prev = lf;
+            const int* fi = m.faces + (size_t)(f0 + lf) * 3;
+            shade = rs_shade(mb_vertex(m, v0, V, fi[0]), mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
+            mb_face_kd(m, n, f0 + lf, kd);
+            if (TEX) {
+                t = mb_face_tex(m, n, f0 + lf);
+                if (t >= 0) set = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f);    // the winner: true
+            }
+            if (!TEX || t < 0) rs_colour_u8(kd, shade, col);
+        }
+        if (TEX && t >= 0) {
+            float c[3], kc[3] = {kd[0], kd[1], kd[2]};
+            const long dx = px - f.x0, dy = py - f.y0;
+            if (set && rs_texel_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
+                                   f.e[1] + dx * f.sx[1] + dy * f.sy[1] + rs_sample_step(f, 1, s),
+                                   f.e[2] + dx * f.sx[2] + dy * f.sy[2] + rs_sample_step(f, 2, s), c)) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) kc[k] = kd[k] * c[k];
+            }
+            rs_colour_u8(kc, shade, col);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sum[k] += col[k];
+    }
+    uint8_t* out = image + (size_t)nv * 3 * HW + pix;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)(sum[k] >> 2);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
+                                                                       long npix, const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                                       int* __restrict__ visibility) {
+    rs_resolve_aa<false>(m, cam, views, H, W, npix, 0.f, 0.f, 0.f, keys, image, visibility);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_tex_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
+                                                                           long npix, float fx, float fy, float znear,
+                                                                           const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                                           int* __restrict__ visibility) {
+    rs_resolve_aa<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+}
+
 // one lane per face of the whole batch: out fp32 [sumF][3], the colour the voxeliser takes for the face
 __global__ __launch_bounds__(RS_THREADS) void mesh_face_colours_kernel(MeshBatch m, long sumF, float* __restrict__ out) {
     const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -304,21 +519,37 @@ extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W
     return npix * 8 + 16 + (size_t)sumF * views * 8;                    // keys | queue count (padded to 16 bytes) | queue
 }
 
-static int rs_render(const MeshBatch& m, bool tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
-                     void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
-    const int N = m.N;
-    char msg[160];
+// the four-sample query: four keys per pixel, so fewer than 2^31 SAMPLES
+extern "C" size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W) {
+    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W * 4.0 >= (double)RS_MAX_PIXELS) return 0;
+    const size_t npix = (size_t)N * views * H * W;
+    return npix * 32 + 16 + (size_t)sumF * views * 8;                   // keys | queue count (padded to 16 bytes) | queue
+}
+
+// What every launch refuses before anything runs; samples: keys per pixel, 1 or 4.
+static int rs_check(int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, const char* who) {
+    char msg[200];
     if (!rs_sizes_ok(sumF, N, views, H, W)) { snprintf(msg, sizeof msg, "%s: negative size", who); tri_set_error(msg); return TRI_ERR_ARG; }
     if (!(yfov > 0.0 && yfov < M_PI) || !(znear > 0.0)) {
         snprintf(msg, sizeof msg, "%s: yfov must lie in (0, pi) and znear above 0", who); tri_set_error(msg); return TRI_ERR_ARG;
     }
     if (sumF >= (1L << 31)) { snprintf(msg, sizeof msg, "%s: 2^31 or more faces in a batch", who); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
     if (views > 65535) { snprintf(msg, sizeof msg, "%s: more than 65535 views", who); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
-    if ((double)N * views * H * W >= (double)RS_MAX_PIXELS) {
-        snprintf(msg, sizeof msg, "%s: 2^31 or more pixels (a visibility buffer of 16 GiB or more) in one launch", who);
+    if ((double)N * views * H * W * (double)samples >= (double)RS_MAX_PIXELS) {
+        if (samples == 1) snprintf(msg, sizeof msg, "%s: 2^31 or more pixels (a visibility buffer of 16 GiB or more) in one launch", who);
+        else snprintf(msg, sizeof msg, "%s: 2^31 or more samples (four per pixel; a visibility buffer of 16 GiB or more) in one launch - "
+                      "split the batch", who);
         tri_set_error(msg);
         return TRI_ERR_UNSUPPORTED;
     }
+    return TRI_OK;
+}
+
+static int rs_render(const MeshBatch& m, bool tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+                     void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
+    const int N = m.N;
+    const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 1, who);
+    if (bad != TRI_OK) return bad;
     const long npix = (long)N * views * H * W;
     if (npix == 0) return TRI_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -358,6 +589,41 @@ extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const
     }
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
     return rs_render(m, true, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_tex");
+}
+
+extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                    const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                    const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
+                                    int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const char* who = "tri_raster_render_aa";
+    if (T < 0) { tri_set_error("tri_raster_render_aa: negative size"); return TRI_ERR_ARG; }
+    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
+        tri_set_error("tri_raster_render_aa: T > 0 needs all five texture fields");
+        return TRI_ERR_ARG;
+    }
+    const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 4, who);
+    if (bad != TRI_OK) return bad;
+    const long npix = (long)N * views * H * W;
+    if (npix == 0) return TRI_OK;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    hipStream_t st = (hipStream_t)stream;
+    u64* keys = (u64*)workspace;
+    u64* qcount = keys + 4 * npix;
+    uint2* queue = (uint2*)(qcount + 2);
+    const u64 qcap = (u64)sumF * views;
+    const double fyd = 1.0 / tan(yfov / 2.0);
+    const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
+    raster_clear_aa_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (2 * npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(
+        (ulonglong2*)keys, 2 * npix, qcount);
+    if (sumF > 0) {
+        raster_faces_aa_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
+            m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+        raster_queue_aa_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+    }
+    const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
+    if (T > 0) raster_resolve_aa_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    else raster_resolve_aa_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
+    return tri_check_launch(who);
 }
 
 extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,

@@ -2,7 +2,7 @@
 splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
-        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on]
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on] [--antialias off|4x]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
@@ -18,6 +18,11 @@ of the models (data/materials.py load_obj_textured; textures above 256 texels on
 ops.render_views_textured: Kd x texel, repeat wrap, bilinear, no mip-maps.  Voxels made from the meshes (--voxels mesh | auto) then
 take one colour per face, ops.mesh_face_colours: Kd times the mean of four texture samples of the face.  The summary names the
 models with at least one loaded texture and the map_Kd files that could not be loaded (such a material keeps its Kd).
+
+--antialias 4x (the default is off: visibility is decided at the pixel centre alone) renders with four coverage samples per pixel,
+ops.render_views(..., samples=4): the 4x rotated grid, every sample covered, depth-tested and coloured by the one-sample rules, the
+pixel their rounded integer mean.  It works with --textures on (each sample takes the texture at its own (u, v)) and with --device
+cpu.  data/render.py says what it rests on - our unverified reading that pyrender's off-screen passes are 4x multisampled.
 
 --voxels says where the grids come from.  nrrd (the default): Text2Shape's nrrd_256_filter_div_{V}_solid/<id>/<id>.nrrd downloads
 (data/nrrd.py), which exist for chairs and tables only.  mesh: ops.voxelize_meshes (csrc/voxelize.hip) voxelises the meshes already
@@ -53,6 +58,7 @@ VOXEL_SIZES = (32, 64, 128)
 SPLITS = ("train", "val", "test")
 VOXEL_SOURCES = ("nrrd", "mesh", "auto")
 TEXTURE_MODES = ("off", "on")
+ANTIALIAS_MODES = {"off": 1, "4x": 4}                # --antialias -> samples per pixel
 
 
 def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
@@ -116,11 +122,12 @@ def pack_batch(meshes, device, textures=False):
 
 
 def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd",
-                textures=False, texture_stats=None):
+                textures=False, texture_stats=None, samples=1):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
     come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist).
     textures: read and render map_Kd textures, and colour mesh voxels from them; texture_stats, a dict, then gains the number of
-    "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded)."""
+    "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded).
+    samples: coverage samples per pixel, 1 or 4 (render.render_batch)."""
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
     load = load_obj_textured if textures else load_obj_materials
     for i in range(0, len(todo), batch_meshes):
@@ -130,7 +137,7 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
             texture_stats["textured_models"] = texture_stats.get("textured_models", 0) + sum(1 for m in meshes if len(m[7]))
             texture_stats["texture_failures"] = texture_stats.get("texture_failures", 0) + sum(len(m[8]) for m in meshes)
         packed, solid = pack_batch(meshes, device, textures)
-        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures).cpu().numpy()
+        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures, samples=samples).cpu().numpy()
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
         if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
@@ -162,6 +169,8 @@ def main(argv=None, log=print):
                     "from the meshes, or auto (the downloads where all three sizes exist for a model)")
     ap.add_argument("--textures", choices=TEXTURE_MODES, default="off", help="on: render map_Kd textures (ops.render_views_textured) and colour "
                     "mesh voxels from them; off: a textured material renders with its bare Kd")
+    ap.add_argument("--antialias", choices=tuple(ANTIALIAS_MODES), default="off", help="4x: four coverage samples per pixel (the 4x rotated grid), "
+                    "the pixel their rounded mean; off: visibility at the pixel centre alone")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.batch_meshes < 1:
         ap.error("--batch-meshes must be positive")
@@ -179,7 +188,8 @@ def main(argv=None, log=print):
             keys = read_model_ids(map_path)
         tex = {"textured_models": 0, "texture_failures": 0} if args.textures == "on" else {}
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
-                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, args.textures == "on", tex)
+                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, args.textures == "on", tex,
+                                       ANTIALIAS_MODES[args.antialias])
         stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")
         if tex:

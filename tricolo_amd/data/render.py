@@ -17,7 +17,14 @@ Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliber
     (baseColorFactor x baseColorTexture); repeat wrap, bilinear over texel centres at the perspective-correct (u, v) of the pixel
     centre, NO mip-maps (the parser bounds minification by reducing textures to 256 texels on a side), no gamma;
   * no near-plane clipping: a face with a vertex nearer than znear is dropped whole.  model_normalized.obj lies within 0.5 of its
-    centre and the camera stands 0.85 away, so no face of such a mesh comes near the plane; no anti-aliasing either.
+    centre and the camera stands 0.85 away, so no face of such a mesh comes near the plane;
+  * anti-aliasing is opt-in (samples=4 below, --antialias 4x of data/preprocess.py; the default decides visibility at the pixel
+    centre alone): coverage and depth at the four positions (96, 32), (224, 96), (32, 160), (160, 224) in 1/256 pixel from the pixel's
+    top-left corner - the 4x rotated grid - by the same exact rules, every sample coloured as a pixel is, the pixel their rounded
+    integer mean (c0 + c1 + c2 + c3 + 2) >> 2.  For untextured faces that is a multisample resolve, for textured ones 4x supersampling
+    (the (u, v) of each sample's own position; no attribute is extrapolated outside its face).  It rests on our reading, FROM MEMORY,
+    of pyrender's published source: its off-screen passes draw into a 4-sample multisample renderbuffer and blit it down.  pyrender is
+    not installed where this was written, so nobody has checked that reading, nor pyrender's sample positions, nor a pixel.
 
 On GPU tensors ops.render_views launches the HIP kernels; on CPU tensors the same call runs render_views_cpu below, a torch
 restatement of the kernel's arithmetic (spelled out at the head of csrc/raster.hip) that gives the same bits.  It exists for
@@ -37,6 +44,8 @@ DISTANCE, ELEVATION = 0.85, math.pi / 5
 SNAP_MAX = float(2 ** 20)
 KDIFF = float(np.float32(3.0 / math.pi))
 CANDIDATES_PER_PASS = 1 << 21                       # (face, pixel) pairs the fallback expands at a time
+CENTRE = ((128, 128),)                              # where a pixel is sampled, in 1/256 pixel from its top-left corner: samples=1 ...
+SAMPLE_OFFSETS = ((96, 32), (224, 96), (32, 160), (160, 224))                                   # ... and samples=4, the 4x rotated grid
 B13, B23, B16 = (float(np.float32(c)) for c in ("0.33333334", "0.6666667", "0.16666667"))      # csrc/raster.hip RS_B13, RS_B23, RS_B16
 FACE_SAMPLES = ((B13, B13, B13), (B23, B16, B16), (B16, B23, B16), (B16, B16, B23))
 TEXEL_VALUE = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0))           # byte / 255, correctly rounded
@@ -125,14 +134,18 @@ def project_faces(verts, faces, cam, H, W, yfov, znear, with_order=False):
     return out + (order,) if with_order else out
 
 
-def _visibility_one(verts, faces, cam, H, W, yfov, znear):
-    """keys int64 [H * W] of one mesh and one view: bits(d) << 32 | (0xFFFFFFFF - face), 0 for background."""
-    keys = torch.zeros((H * W,), dtype=torch.int64)
+def _visibility_one(verts, faces, cam, H, W, yfov, znear, offsets=CENTRE):
+    """keys int64 [H * W * S] of one mesh and one view, the S = len(offsets) samples of a pixel innermost:
+    bits(d) << 32 | (0xFFFFFFFF - face), 0 for background.  offsets: the sample positions in 1/256 pixel from the pixel's top-left
+    corner, CENTRE or SAMPLE_OFFSETS; the box of candidate pixels holds every pixel with a sample inside the face's bounding box."""
+    S = len(offsets)
+    lo, hi = min(min(o) for o in offsets), max(max(o) for o in offsets)              # 128, 128 or 32, 224: csrc/raster.hip rs_setup's LO, HI
+    keys = torch.zeros((H * W * S,), dtype=torch.int64)
     keep, X, Y, d, A2 = project_faces(verts, faces, cam, H, W, yfov, znear)
-    x0 = ((X.amin(1) + 127) >> 8).clamp(min=0)
-    x1 = ((X.amax(1) - 128) >> 8).clamp(max=W - 1)
-    y0 = ((Y.amin(1) + 127) >> 8).clamp(min=0)
-    y1 = ((Y.amax(1) - 128) >> 8).clamp(max=H - 1)
+    x0 = ((X.amin(1) + (255 - hi)) >> 8).clamp(min=0)
+    x1 = ((X.amax(1) - lo) >> 8).clamp(max=W - 1)
+    y0 = ((Y.amin(1) + (255 - hi)) >> 8).clamp(min=0)
+    y1 = ((Y.amax(1) - lo) >> 8).clamp(max=H - 1)
     keep = keep & (x0 <= x1) & (y0 <= y1)
     fidx = torch.nonzero(keep).reshape(-1)
     if fidx.numel() == 0:
@@ -151,24 +164,25 @@ def _visibility_one(verts, faces, cam, H, W, yfov, znear):
         local = torch.arange(int(c.sum())) - torch.repeat_interleave(torch.cumsum(c, 0) - c, c)
         iy = torch.div(local, w[rep], rounding_mode="floor")
         ix = local - iy * w[rep]
-        f = sel[rep]
-        px, py = x0[f] + ix, y0[f] + iy
-        Px, Py = 256 * px + 128, 256 * py + 128
-        inside = torch.ones_like(f, dtype=torch.bool)
-        E = []
-        for k in range(3):
-            a, b = (k + 1) % 3, (k + 2) % 3
-            dx, dy = X[f, b] - X[f, a], Y[f, b] - Y[f, a]
-            e = dx * (Py - Y[f, a]) - dy * (Px - X[f, a])
-            top_left = (dy < 0) | ((dy == 0) & (dx > 0))
-            inside &= (e > 0) | ((e == 0) & top_left)
-            E.append(e)
-        f, px, py = f[inside], px[inside], py[inside]
-        fa = A2[f].to(torch.float32)
-        lam = [e[inside].to(torch.float32) / fa for e in E]
-        depth = (lam[0] * d[f, 0] + lam[1] * d[f, 1]) + lam[2] * d[f, 2]
-        key = (depth.view(torch.int32).to(torch.int64) << 32) | (0xFFFFFFFF - f)
-        keys.scatter_reduce_(0, py * W + px, key, reduce="amax", include_self=True)
+        pair = sel[rep]
+        for s, (ox, oy) in enumerate(offsets):
+            f, px, py = pair, x0[pair] + ix, y0[pair] + iy
+            Px, Py = 256 * px + ox, 256 * py + oy
+            inside = torch.ones_like(f, dtype=torch.bool)
+            E = []
+            for k in range(3):
+                a, b = (k + 1) % 3, (k + 2) % 3
+                dx, dy = X[f, b] - X[f, a], Y[f, b] - Y[f, a]
+                e = dx * (Py - Y[f, a]) - dy * (Px - X[f, a])
+                top_left = (dy < 0) | ((dy == 0) & (dx > 0))
+                inside &= (e > 0) | ((e == 0) & top_left)
+                E.append(e)
+            f, px, py = f[inside], px[inside], py[inside]
+            fa = A2[f].to(torch.float32)
+            lam = [e[inside].to(torch.float32) / fa for e in E]
+            depth = (lam[0] * d[f, 0] + lam[1] * d[f, 1]) + lam[2] * d[f, 2]
+            key = (depth.view(torch.int32).to(torch.int64) << 32) | (0xFFFFFFFF - f)
+            keys.scatter_reduce_(0, (py * W + px) * S + s, key, reduce="amax", include_self=True)
         start = stop
     return keys
 
@@ -205,9 +219,10 @@ def sample_textures(t, u, v, texels, tex_off, tex_size):
     return ok, a + (b - a) * fy
 
 
-def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size):
-    """(has bool [HW], c fp32 [HW, 3]) of one mesh and one view: where the winning face of vis int64 [HW] is textured, and the
-    texture colour at the perspective-correct (u, v) of the pixel centre."""
+def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size, offsets=CENTRE):
+    """(has bool [HW S], c fp32 [HW S, 3]) of one mesh and one view: where the winning face of vis int64 [HW S] (the S = len(offsets)
+    samples of a pixel innermost) is textured, and the texture colour at the perspective-correct (u, v) of the sample's own position
+    - the pixel centre for CENTRE."""
     has = torch.zeros((vis.numel(),), dtype=torch.bool)
     c = torch.ones((vis.numel(), 3), dtype=torch.float32)
     pix = torch.nonzero((vis >= 0) & (face_t[vis.clamp(min=0)] >= 0)).reshape(-1)
@@ -215,7 +230,9 @@ def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texe
         return has, c
     _, X, Y, d, A2, order = project_faces(verts, faces, cam, H, W, yfov, znear, with_order=True)
     f = vis[pix]
-    Px, Py = 256 * (pix % W) + 128, 256 * torch.div(pix, W, rounding_mode="floor") + 128
+    S, off = len(offsets), torch.tensor(offsets, dtype=torch.int64)
+    pixel, s = torch.div(pix, S, rounding_mode="floor"), pix % S
+    Px, Py = 256 * (pixel % W) + off[s, 0], 256 * torch.div(pixel, W, rounding_mode="floor") + off[s, 1]
     fa = A2[f].to(torch.float32)
     w = []
     for k in range(3):
@@ -234,7 +251,8 @@ def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texe
 
 
 def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
-    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background); tex: _texels_one's pair."""
+    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background); tex: _texels_one's pair.
+    Every entry is coloured on its own, so a four-sample buffer [HW 4] gives the four sample colours of every pixel."""
     out = torch.full((3, vis.numel()), 255, dtype=torch.uint8)
     pix = torch.nonzero(vis >= 0).reshape(-1)
     if pix.numel() == 0:
@@ -258,13 +276,18 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
 
 
 def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
-                     return_visibility=False, textures=None):
+                     return_visibility=False, textures=None, samples=1):
     """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch.  textures: the five
-    texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured."""
+    texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured.  samples=4: coverage,
+    depth and colour at the four SAMPLE_OFFSETS of every pixel, the pixel their rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2 per
+    channel, the visibility int32 [N, views, H, W, 4]."""
+    if samples not in (1, 4):
+        raise ValueError(f"render_views_cpu: samples must be 1 or 4, got {samples!r}")
+    offsets = SAMPLE_OFFSETS if samples == 4 else CENTRE
     voff, foff, moff = vert_off.tolist(), face_off.tolist(), mat_off.tolist()
     N, views = len(voff) - 1, cam.shape[1]
     image = torch.full((N, views, 3, H, W), 255, dtype=torch.uint8)
-    vis = torch.full((N, views, H, W), -1, dtype=torch.int32)
+    vis = torch.full((N, views, H, W) + ((4,) if samples == 4 else ()), -1, dtype=torch.int32)
     for n in range(N):
         v = verts[voff[n]:voff[n + 1]]
         f = faces[foff[n]:foff[n + 1]]
@@ -273,16 +296,19 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
         f = clamp_index(f, v.shape[0])
         fm, kd = face_mat[foff[n]:foff[n + 1]], mat_kd[moff[n]:moff[n + 1]]
         for k in range(views):
-            keys = _visibility_one(v, f, cam[n, k], H, W, yfov, znear)
+            keys = _visibility_one(v, f, cam[n, k], H, W, yfov, znear, offsets)
             face = torch.where(keys != 0, 0xFFFFFFFF - (keys & 0xFFFFFFFF), torch.full_like(keys, -1))
-            vis[n, k] = face.to(torch.int32).view(H, W)
+            vis[n, k] = face.to(torch.int32).view(vis.shape[2:])
             tex = None
             if textures is not None:
                 face_uv, mat_tex, texels, tex_off, tex_size = textures
                 uv = face_uv[foff[n]:foff[n + 1]]
                 face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
-                tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size)
-            image[n, k] = _shade_one(v, f, fm, kd, cam[n, k], face, tex).view(3, H, W)
+                tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size, offsets)
+            colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex)
+            if samples == 4:
+                colour = ((colour.view(3, H * W, 4).to(torch.int32).sum(dim=2) + 2) >> 2).to(torch.uint8)
+            image[n, k] = colour.view(3, H, W)
     return (image, vis) if return_visibility else image
 
 
@@ -309,22 +335,23 @@ def mesh_face_colours_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
 
 
 # ------------------------------------------------------------------------------------------------ the convenient calls
-def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False):
+def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1):
     """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
     [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
-    ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures)."""
+    ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures).  samples=4:
+    four coverage samples per pixel (ops.render_views)."""
     from .. import ops
     cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
     H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
     if textures:
-        return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility)
-    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility)
+        return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples)
+    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples)
 
 
 def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False,
-                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None):
+                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1):
     """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None); textures=True
     needs the three texture lists of MeshBatch.pack."""
     batch = MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device, face_uv_list=face_uv_list, mat_tex_list=mat_tex_list,
                            textures_list=textures_list)
-    return render_batch(batch, num_views, image_size, return_visibility, textures)
+    return render_batch(batch, num_views, image_size, return_visibility, textures, samples)

@@ -1686,8 +1686,34 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
 RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
 
 
+def _render_views_aa(stage, N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, textures, cam, H, W, yfov, znear, return_visibility):
+    """The samples=4 path of render_views and render_views_textured, their arguments already checked (textures: the five texture
+    tensors, or None and T == 0 for a batch without them): tri_raster_render_aa, on CPU tensors render_views_cpu(samples=4)."""
+    views, sumF = cam.shape[1], faces.shape[0]
+    if N * views * H * W * 4 >= RENDER_MAX_PIXELS or views > 65535:
+        raise ValueError(f"{stage}: {N} meshes x {views} views x {H} x {W} pixels x 4 samples need a visibility buffer of "
+                         f"{N * views * H * W * 32} bytes; one call takes fewer than 2^31 samples and at most 65535 views - split the batch")
+    if not verts.is_cuda:
+        from .data.render import render_views_cpu
+        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
+                                textures=textures, samples=4)
+    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
+    vis = torch.empty((N, views, H, W, 4), dtype=torch.int32, device=verts.device) if return_visibility else None
+    ws = torch.empty((max(16, lib().tri_raster_workspace_aa(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+    check(lib().tri_raster_render_aa(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
+                                     *(ptr(x) for x in (textures or (None,) * 5)), T, ptr(cam), N, sumF, views, H, W, float(yfov),
+                                     float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_aa")
+    return (image, vis) if return_visibility else image
+
+
+def _render_samples(stage, samples):
+    if samples not in (1, 4):
+        raise ValueError(f"{stage}: samples must be 1 (the pixel centre) or 4 (the 4x rotated grid), got {samples!r}")
+    return int(samples)
+
+
 def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=math.pi / 3, znear=0.05,
-                 return_visibility=False):
+                 return_visibility=False, samples=1):
     """Render every mesh of a packed batch (meshes.MeshBatch.pack) from every camera -> images uint8 [N, views, 3, H, W], with
     return_visibility also int32 [N, views, H, W]: the face seen at each pixel centre, local to its mesh, -1 for background.
     face_mat int32 [sumF]: a material per face, local to the mesh; mat_kd fp32 [sumM, 3] diffuse colours with mat_off int64 [N + 1];
@@ -1696,8 +1722,13 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     (model_normalized.obj lies within 0.5 of its centre, the reference's camera stands 0.85 away) - both sides are drawn, flat
     Lambert shading, white background.  One call takes fewer than 2^31 faces and fewer than 2^31 pixels over all meshes and views
     (8 bytes of visibility key each); more raises before anything runs.  CPU tensors run data.render.render_views_cpu, the same
-    arithmetic in torch (untuned, for checking)."""
+    arithmetic in torch (untuned, for checking).
+    samples=4 takes coverage and depth at four positions per pixel - (96, 32), (224, 96), (32, 160), (160, 224) in 1/256 pixel from the
+    pixel's top-left corner, the 4x rotated grid - by the same rules, colours every sample as a pixel is coloured and writes their
+    rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2; the visibility is then int32 [N, views, H, W, 4], and one call takes fewer than
+    2^31 samples.  samples=1, the default, is the pixel centre alone; anything else raises."""
     H, W = int(H), int(W)
+    samples = _render_samples("render_views", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views")
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
@@ -1706,6 +1737,9 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
         raise ValueError("render_views: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
     if sumF >= 2 ** 31:
         raise ValueError("render_views: 2^31 or more faces in one batch")
+    if samples == 4:
+        return _render_views_aa("render_views", N, 0, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, None, cam, H, W, yfov, znear,
+                                return_visibility)
     if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
         raise ValueError(f"render_views: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
                          f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
@@ -1739,15 +1773,17 @@ def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_
 
 
 def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size, cam, H, W,
-                          yfov=math.pi / 3, znear=0.05, return_visibility=False):
+                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1):
     """render_views with map_Kd textures: the packed batch and its five texture tensors (MeshBatch.tensors, MeshBatch.texture_tensors).
     face_uv fp32 [sumF, 3, 2]: one (u, v) per face corner, NaN in face_uv[f, 0, 0] = the face has none; mat_tex int32 [sumM]: a
     batch-global texture index per material, -1 = none; texels u8 [sumTexels, 4] RGBA; tex_off int64 [T + 1]; tex_size int32 [T, 2]
     = (height, width), row 0 the top of the image, v = 0 its bottom.  Visibility is render_views'; a textured face is coloured
     clamp((Kd c) shade, 0, 1), c the texture at the perspective-correct (u, v) of the pixel centre - repeat wrap, bilinear, NO
     mip-maps (head of csrc/raster.hip) - and an untextured one exactly as by render_views.  Same limits; CPU tensors run the torch
-    restatement of data.render."""
+    restatement of data.render.  samples=4: render_views' four samples, a textured face sampled at the (u, v) of each sample's own
+    position - 4x supersampling of the texture, which eases but does not replace the missing mip-maps."""
     H, W = int(H), int(W)
+    samples = _render_samples("render_views_textured", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
     T = _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
@@ -1757,6 +1793,9 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
         raise ValueError("render_views_textured: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
     if sumF >= 2 ** 31:
         raise ValueError("render_views_textured: 2^31 or more faces in one batch")
+    if samples == 4:
+        return _render_views_aa("render_views_textured", N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off,
+                                (face_uv, mat_tex, texels, tex_off, tex_size), cam, H, W, yfov, znear, return_visibility)
     if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
         raise ValueError(f"render_views_textured: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
                          f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
