@@ -549,6 +549,29 @@ int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_
                          const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
                          double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
 
+/* The mip pyramid of every texture of a batch (csrc/mesh_batch.h lays it out).  Texture t of size (H0, W0) has
+ * L = floor(log2(max(H0, W0))) + 1 levels of size (max(1, H0 >> l), max(1, W0 >> l)); its chain starts at mip_off[t] (int64 [T + 1], the
+ * running sum of the chain lengths, formed by the caller) of mip_texels u8 [sum_mip][4], the levels one after the other from level 0,
+ * row major.  Level 0 is a copy of the texture; a texel of a level l >= 1 is the area-weighted box mean over the span of LEVEL 0 it
+ * covers, in exact integers, (2 S + D) / (2 D) with D = H0 W0 (half rounds up), alpha 255.  One launch, no host synchronisation.
+ * sum_texels and sum_mip are the numbers of texels the two arrays hold: no read leaves [0, min(tex_off[T], sum_texels) - 1], no write
+ * [0, min(mip_off[T], sum_mip) - 1], whatever the tables say.  T == 0 or sum_mip == 0: nothing runs. */
+int tri_texture_mips(const uint8_t* texels, const long* tex_off, const int* tex_size, int T, long sum_texels, const long* mip_off,
+                     long sum_mip, uint8_t* mip_texels, void* stream);
+
+/* tri_raster_render_tex (samples == 1) or tri_raster_render_aa (samples == 4) with mip-mapped textures: the same visibility, bit for
+ * bit, the same workspace (tri_raster_workspace / tri_raster_workspace_aa) and limits.  mip_texels, mip_off: the pyramid of
+ * tri_texture_mips for this batch's textures.  A textured face is coloured clamp((Kd c) shade, 0, 1) with c blended from two levels
+ * of the pyramid; the level of detail comes from (u, v) at the position itself, one whole pixel to the right and one whole pixel
+ * down (the face's plane extended; with four samples the step is still one pixel, no LOD bias).  Where the texture is magnified
+ * (rho <= 1) the colour is tri_raster_render_tex's, bit for bit.  The rule is spelled out at the head of csrc/raster.hip; it is a
+ * definition of this project, not compared with any other renderer.  T == 0: every face is untextured and the pyramid may be null. */
+int tri_raster_render_mip(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                          const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off, const float* cam,
+                          int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, void* workspace,
+                          uint8_t* image, int* visibility, void* stream);
+
 /* One colour per face for the voxeliser: colours fp32 [sumF][3] = Kd for an untextured face, else Kd times the mean of four bilinear
  * samples of its texture, at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of the face's UVs (used
  * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped. */

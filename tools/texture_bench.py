@@ -3,9 +3,11 @@ of tools/raster_bench.py - a batch of 8 procedural meshes (a sphere on a table o
 views at 224 x 224 - and ops.mesh_face_colours on the same batch.  Two of the three materials carry a 256 x 256 random-noise texture
 (the parser's largest size; noise is the worst case for the texel loads), the third has none, and every face has random UVs in
 [-2, 3]: textured and untextured pixels meet in the same waves.  HIP events, warmed; the two renderers alternate window by window in
-one process, and every window is reported, so the spread is on the page.  One JSON line per size.
+one process, and every window is reported, so the spread is on the page.  One JSON line per size.  --mip adds the mip-mapped call
+(ops.render_views_textured(..., mips=), with --samples 1 4 in both sample counts) and ops.texture_mips, the pyramid build for the
+batch's 256 x 256 textures, to the alternation.
 
-    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--trace-only RINGS]
+    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--mip] [--trace-only RINGS]
     (--trace-only: three warmed calls of each for rocprofv3 --kernel-trace --stats, which gives the resolve kernels' own times)
 """
 import argparse
@@ -54,6 +56,8 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--samples", type=int, nargs="+", choices=(1, 4), default=[1], help="coverage samples per pixel of the two renderers; with "
                     "1 4 the four-sample calls (render_views_4, render_views_textured_4) join the alternation")
+    ap.add_argument("--mip", action="store_true", help="time the mip-mapped call (render_views_mip, render_views_mip_4) and the pyramid build "
+                    "(texture_mips) beside the others")
     ap.add_argument("--trace-only", type=int, default=None, metavar="RINGS")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -66,11 +70,19 @@ def main():
         if 4 in a.samples:
             calls["render_views_4"] = lambda: ops.render_views(*packed.tensors, *tail, samples=4)
             calls["render_views_textured_4"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, samples=4)
+        if a.mip:
+            mips = ops.texture_mips(*packed.texture_tensors[2:])
+            calls["texture_mips"] = lambda: ops.texture_mips(*packed.texture_tensors[2:])
+            calls["render_views_mip"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, mips=mips)
+            if 4 in a.samples:
+                calls["render_views_mip_4"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, samples=4, mips=mips)
         if 1 not in a.samples:
+            calls.pop("render_views_mip", None)
             del calls["render_views"], calls["render_views_textured"]
         for fn in calls.values():
             for _ in range(3):
                 out = fn()
+            out = out[0] if isinstance(out, tuple) else out
         torch.cuda.synchronize()
         if a.trace_only:
             print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "finite": bool(torch.isfinite(out).all())}))
@@ -82,10 +94,13 @@ def main():
                 ms[k].append(round(window(fn, a.iters), 4))
         med = {k: float(np.median(v)) for k, v in ms.items()}
         ratios = {"textured_over_plain": ("render_views_textured", "render_views"), "textured_4_over_plain_4": ("render_views_textured_4", "render_views_4"),
-                  "textured_4_over_textured": ("render_views_textured_4", "render_views_textured")}
+                  "textured_4_over_textured": ("render_views_textured_4", "render_views_textured"),
+                  "mip_over_textured": ("render_views_mip", "render_views_textured"), "mip_4_over_textured_4": ("render_views_mip_4", "render_views_textured_4")}
         print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "views": VIEWS, "size": SIZE, "texture": TEXTURE, "iters": a.iters, "ms_per_call": ms,
                           "median_ms_per_call": med, **{k: round(med[x] / med[y], 4) for k, (x, y) in ratios.items() if x in med and y in med},
-                          "pixels_changed_by_textures": float((plain != tex).any(dim=2).float().mean())}), flush=True)
+                          "pixels_changed_by_textures": float((plain != tex).any(dim=2).float().mean()),
+                          **({"pixels_changed_by_mips": float((calls["render_views_mip"]() != tex).any(dim=2).float().mean())}
+                             if "render_views_mip" in calls else {})}), flush=True)
 
 
 if __name__ == "__main__":

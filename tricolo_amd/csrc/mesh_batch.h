@@ -15,6 +15,18 @@
 // 0 is the top row of the image and v = 0 its bottom (the OBJ convention).  mb_tex_sample below is THE sampling rule - repeat wrap,
 // bilinear, no mip-maps - of the textured resolve pass of raster.hip and of its face colours.
 //
+// The mip pyramid (optional; the two fields are null in a batch without one; raster.hip's tri_texture_mips builds it and only its mip
+// resolve kernels read it).  Texture t of size (H0, W0) has L = floor(log2(max(H0, W0))) + 1 levels, level l of size
+// (H_l, W_l) = (max(1, H0 >> l), max(1, W0 >> l)); level 0 is a copy of the texture.  mip_texels u8 [sumMipTexels][4] holds the chain
+// of texture t from mip_off[t] (int64 [T + 1]): its levels one after the other from level 0, each row major, RGBA with alpha 255.
+// There is NO table of level offsets: a kernel walks them from tex_size - level l starts sum_{k < l} H_k W_k texels into the chain, at
+// most 24 steps of two shifts, a multiply and an add (mb_mip_level), which costs less than a dependent load per sample would.
+// A texel of level l >= 1 is formed from LEVEL 0, not from the level below, in integers: texel (y, x) covers the columns j of level 0
+// with weight wx(j) = max(0, min((x + 1) W0, (j + 1) W_l) - max(x W0, j W_l)) (they add up to W0), the rows i with wy(i) likewise in
+// H; with S = sum_i sum_j wy(i) wx(j) texel0[i][j][k] and D = H0 W0 the value is (2 S + D) / (2 D) in integer division - the box mean,
+// half rounded up; int64 holds it (2 * 255 * 2^48 < 2^63).  For power-of-two sizes that is the rounded mean of the 2^l x 2^l block.
+// mb_mip_sample is mb_tex_sample's rule on one level, with that level's own (H_l, W_l).
+//
 // Contraction is switched off HERE, not only in the including files: `#pragma clang fp contract(off)` covers the code that follows it,
 // so a helper defined in a header ahead of the including file's own pragma would be compiled with contraction on - a * b + c became
 // v_fmac_f32 in such a helper while the same expression in a kernel body stayed a multiply and an add.  With an fma the cross product
@@ -41,6 +53,8 @@ struct MeshBatch {
     const long* __restrict__ tex_off;
     const int* __restrict__ tex_size;
     int T;
+    const unsigned* __restrict__ mip_texels;        // the mip pyramid: null when an initialiser stops at T
+    const long* __restrict__ mip_off;
 };
 
 // the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
@@ -116,6 +130,47 @@ __device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u
     const long ra = base + (long)ya * Wt, rb = base + (long)yb * Wt;
     const unsigned p00 = m.texels[min(max(ra + xa, 0L), last)], p10 = m.texels[min(max(ra + xb, 0L), last)];    // four independent loads
     const unsigned p01 = m.texels[min(max(rb + xa, 0L), last)], p11 = m.texels[min(max(rb + xb, 0L), last)];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float t00 = mb_div((float)((p00 >> (8 * k)) & 255u), 255.f), t10 = mb_div((float)((p10 >> (8 * k)) & 255u), 255.f);
+        const float t01 = mb_div((float)((p01 >> (8 * k)) & 255u), 255.f), t11 = mb_div((float)((p11 >> (8 * k)) & 255u), 255.f);
+        const float a = t00 + (t10 - t00) * fx, b = t01 + (t11 - t01) * fx;
+        c[k] = a + (b - a) * fy;
+    }
+    return true;
+}
+
+// The number of levels of a texture of size (H0, W0), both >= 1: floor(log2(max(H0, W0))) + 1.
+__device__ __forceinline__ int mb_mip_levels(int H0, int W0) { return 32 - __clz(max(H0, W0)); }
+
+// Level l >= 0 of the chain of a texture of size (H0, W0): its size to Hl, Wl; returns where it starts, in texels from the chain's start.
+__device__ __forceinline__ long mb_mip_level(int H0, int W0, int l, int& Hl, int& Wl) {
+    long off = 0;
+    for (int k = 0; k < l; ++k) off += (long)max(1, H0 >> k) * max(1, W0 >> k);
+    Hl = max(1, H0 >> l);
+    Wl = max(1, W0 >> l);
+    return off;
+}
+
+// mb_tex_sample's rule on level l of the pyramid of texture t (0 <= t < T; l is clamped to the texture's levels), with that level's own
+// (H_l, W_l): level 0 gives mb_tex_sample's bits.  A copy, not a shared helper, so that mb_tex_sample's code does not move.  Whatever the
+// tables hold, no texel index leaves [0, mip_off[T] - 1]; a batch without a pyramid texel reads as false.
+__device__ __forceinline__ bool mb_mip_sample(const MeshBatch& m, int t, int l, float u, float v, float* c) {
+    const int H0 = m.tex_size[2 * t], W0 = m.tex_size[2 * t + 1];
+    const long last = m.mip_off[m.T] - 1;
+    if (!(fabsf(u) < INFINITY) || !(fabsf(v) < INFINITY) || H0 < 1 || W0 < 1 || last < 0) return false;
+    int Ht, Wt;
+    const long base = m.mip_off[t] + mb_mip_level(H0, W0, min(max(l, 0), mb_mip_levels(H0, W0) - 1), Ht, Wt);
+    u = u - floorf(u);
+    v = v - floorf(v);
+    const float x = u * (float)Wt - 0.5f, y = (1.0f - v) * (float)Ht - 0.5f;
+    const float xf = floorf(x), yf = floorf(y);
+    const float fx = x - xf, fy = y - yf;
+    const int xa = mb_mod((int)fminf(xf, 2147483520.f), Wt), ya = mb_mod((int)fminf(yf, 2147483520.f), Ht);     // xf, yf >= -1
+    const int xb = xa + 1 == Wt ? 0 : xa + 1, yb = ya + 1 == Ht ? 0 : ya + 1;
+    const long ra = base + (long)ya * Wt, rb = base + (long)yb * Wt;
+    const unsigned p00 = m.mip_texels[min(max(ra + xa, 0L), last)], p10 = m.mip_texels[min(max(ra + xb, 0L), last)];
+    const unsigned p01 = m.mip_texels[min(max(rb + xa, 0L), last)], p11 = m.mip_texels[min(max(rb + xb, 0L), last)];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float t00 = mb_div((float)((p00 >> (8 * k)) & 255u), 255.f), t10 = mb_div((float)((p10 >> (8 * k)) & 255u), 255.f);

@@ -45,6 +45,24 @@
 //     mb_tex_sample, clamp((Kd c) s, 0, 1), with the same fallback to Kd s.  The pixel is (c0 + c1 + c2 + c3 + 2) >> 2 per channel of the
 //     four u8 colours: a multisample resolve for untextured faces, 4x supersampling for textured ones - no attribute is ever
 //     extrapolated outside its face.  The visibility output is int32 [N][views][H][W][4], the face at each sample.
+//   mip-mapped textures (tri_texture_mips builds the pyramid mesh_batch.h lays out - exact integer box means of level 0 - and
+//     tri_raster_render_mip alone reads it; everything above is untouched by it, visibility included).  A definition of our own:
+//     nobody has compared a pixel of it with pyrender's mip-mapping.  At a position P - the pixel centre, or a sample's own position
+//     with four samples - where face f with texture t of size (H0, W0) and L levels won:
+//     (u, v) and d at P exactly as above (l_k, w_k = l_k d_k, d, b_k, u, v); a (u, v) that is not finite leaves the face untextured there.
+//     (u_x, v_x), d_x: the same arithmetic with the edge functions E_k + sx_k, one whole pixel to the right; (u_y, v_y), d_y with
+//     E_k + sy_k, one whole pixel down.  The face's PLANE is extended beyond its edges for these two evaluations only; no colour is
+//     ever taken there.  The differences are taken before the repeat wrap.  With four samples the step is still one whole pixel and
+//     there is no LOD bias: every sample picks the level a pixel would.
+//     a = (u_x - u) W0,  b = (v_x - v) H0,  c = (u_y - u) W0,  e = (v_y - v) H0  (W0, H0 as fp32);  r2 = max(a a + b b, c c + e e);
+//     rho = sqrt(r2) correctly rounded.  Which levels:
+//       d_x or d_y not above 0 (the plane crosses the eye), or one of u_x, v_x, u_y, v_y, r2 not finite: level L - 1 alone;
+//       rho <= 1 (magnified): level 0 alone - bit for bit the colour of the textured shading above;
+//       else l = floor(log2(rho)) from the exponent bits of rho, g = rho 2^-l - 1 in [0, 1) (the mantissa of rho under exponent 0,
+//       minus 1: exact); l >= L - 1: level L - 1 alone; else per channel c = c_l + (c_{l+1} - c_l) g,
+//     c_l = mb_mip_sample (mesh_batch.h) of level l at (u, v): mb_tex_sample's rule with the level's own (H_l, W_l).  g is linear in
+//     rho, not its logarithm, so that every step is reproducible; the selection is continuous and monotone in rho - at rho = 1, at
+//     every octave and at the top level - and within 0.087 of a level of the logarithm.  colour = clamp((Kd c) s, 0, 1) as above.
 //
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
@@ -348,9 +366,77 @@ __device__ __forceinline__ bool rs_texel_at(const MeshBatch& m, const RsFace& f,
     return mb_tex_sample(m, t, (b0 * u0 + b1 * u1) + b2 * u2, (b0 * v0 + b1 * v1) + b2 * v2, c);
 }
 
+// ---- mip-mapped textures: their own copies of rs_texel's lines, so that the kernels above keep their code ----
+// (u, v) and d of a face with corner UVs q[0..5] (the swap applied) and fa = fl32(2A), where its edge functions are e0, e1, e2
+__device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa, long e0, long e1, long e2, float& u, float& v, float& d) {
+    const float l0 = mb_div((float)(double)e0, fa), l1 = mb_div((float)(double)e1, fa), l2 = mb_div((float)(double)e2, fa);
+    const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
+    d = (w0 + w1) + w2;
+    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
+    u = (b0 * q[0] + b1 * q[2]) + b2 * q[4];
+    v = (b0 * q[1] + b1 * q[3]) + b2 * q[5];
+}
+
+__device__ __forceinline__ bool rs_finite(float x) { return fabsf(x) < INFINITY; }
+
+// The mip-mapped texture colour c[0..2] of face gf (texture t, set up as f) where its edge functions are e0, e1, e2: the level of
+// detail from (u, v) there, one whole pixel to the right and one whole pixel down (head of this file); false where the face is
+// untextured there.
+__device__ __forceinline__ bool rs_texel_mip_at(const MeshBatch& m, const RsFace& f, long gf, int t, long e0, long e1, long e2, float* c) {
+    const float* uv = m.face_uv + (size_t)gf * 6;
+    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
+    const float q[6] = {uv[0], uv[1], uv[2 * i1], uv[2 * i1 + 1], uv[2 * i2], uv[2 * i2 + 1]};
+    const float fa = (float)(double)f.A2;
+    float u, v, d, ux, vx, dx, uy, vy, dy;
+    rs_uvd(f, q, fa, e0, e1, e2, u, v, d);
+    if (!rs_finite(u) || !rs_finite(v)) return false;
+    const int H0 = m.tex_size[2 * t], W0 = m.tex_size[2 * t + 1];
+    if (H0 < 1 || W0 < 1) return false;
+    rs_uvd(f, q, fa, e0 + f.sx[0], e1 + f.sx[1], e2 + f.sx[2], ux, vx, dx);
+    rs_uvd(f, q, fa, e0 + f.sy[0], e1 + f.sy[1], e2 + f.sy[2], uy, vy, dy);
+    const float a = (ux - u) * (float)W0, b = (vx - v) * (float)H0, g = (uy - u) * (float)W0, e = (vy - v) * (float)H0;
+    const float r2 = fmaxf(a * a + b * b, g * g + e * e);
+    const int top = mb_mip_levels(H0, W0) - 1;
+    int lo = top;                                                       // the footprint is unbounded: the coarsest level alone
+    float frac = 0.f;
+    bool two = false;
+    if (dx > 0.f && dy > 0.f && rs_finite(ux) && rs_finite(vx) && rs_finite(uy) && rs_finite(vy) && rs_finite(r2)) {
+        const float rho = mb_sqrt(r2);
+        if (rho <= 1.0f) lo = 0;                                        // magnified: the texture itself
+        else {
+            const unsigned bits = __float_as_uint(rho);                 // rho > 1 and finite: a normal number
+            const int l = (int)(bits >> 23) - 127;
+            if (l < top) {
+                lo = l;
+                frac = __uint_as_float((bits & 0x007FFFFFu) | 0x3F800000u) - 1.0f;
+                two = true;
+            }
+        }
+    }
+    if (!mb_mip_sample(m, t, lo, u, v, c)) return false;
+    if (two) {
+        float h[3];
+        if (!mb_mip_sample(m, t, lo + 1, u, v, h)) return false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = c[k] + (h[k] - c[k]) * frac;
+    }
+    return true;
+}
+
+// rs_texel with the pyramid: the winner of pixel (px, py) set up again, its edge functions at the pixel's centre
+__device__ __forceinline__ bool rs_texel_mip(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
+                                             float fy, float znear, int t, int px, int py, float* c) {
+    RsFace f;
+    if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) return false;        // the winner of a pixel was set up before: never taken
+    const long dx = px - f.x0, dy = py - f.y0;
+    return rs_texel_mip_at(m, f, gf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0], f.e[1] + dx * f.sx[1] + dy * f.sy[1],
+                           f.e[2] + dx * f.sx[2] + dy * f.sy[2], c);
+}
+
 // one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn.  TEX: the textured resolve pass - the
-// lanes of a wave whose face has a texture run rs_texel together, the others wait for them and keep their Kd.
-template <bool TEX>
+// lanes of a wave whose face has a texture run rs_texel together, the others wait for them and keep their Kd.  MIP: rs_texel_mip in
+// its place.
+template <bool TEX, bool MIP = false>
 __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx, float fy,
                                            float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image, int* __restrict__ visibility) {
     const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -375,7 +461,8 @@ __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __re
     if (TEX) {
         const int t = mb_face_tex(m, n, f0 + lf);
         float c[3];
-        if (t >= 0 && rs_texel(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c)) {
+        if (t >= 0 && (MIP ? rs_texel_mip(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c)
+                           : rs_texel(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c))) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) kd[k] = kd[k] * c[k];
         }
@@ -399,6 +486,12 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_tex_kernel(MeshBatc
     rs_resolve<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_mip_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
+                                                                        long npix, float fx, float fy, float znear, const u64* __restrict__ keys,
+                                                                        uint8_t* __restrict__ image, int* __restrict__ visibility) {
+    rs_resolve<true, true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+}
+
 // u8 of clamp(kd s, 0, 1), the colour rs_resolve writes
 __device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* c) {
 #pragma unroll
@@ -410,8 +503,8 @@ __device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* 
 
 // one thread per pixel of the four-sample key buffer: every sample is coloured as rs_resolve colours a pixel - a textured face from (u, v)
 // at the sample's own position - and the pixel is the rounded integer mean.  A face met in the sample before is not shaded or set up
-// again, and an untextured one keeps its colour.
-template <bool TEX>
+// again, and an untextured one keeps its colour.  MIP: rs_texel_mip_at in rs_texel_at's place.
+template <bool TEX, bool MIP = false>
 __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx,
                                               float fy, float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image,
                                               int* __restrict__ visibility) {
@@ -454,7 +547,10 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
         if (TEX && t >= 0) {
             float c[3], kc[3] = {kd[0], kd[1], kd[2]};
             const long dx = px - f.x0, dy = py - f.y0;
-            if (set && rs_texel_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
+            if (MIP ? set && rs_texel_mip_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
+                                             f.e[1] + dx * f.sx[1] + dy * f.sy[1] + rs_sample_step(f, 1, s),
+                                             f.e[2] + dx * f.sx[2] + dy * f.sy[2] + rs_sample_step(f, 2, s), c)
+                    : set && rs_texel_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
                                    f.e[1] + dx * f.sx[1] + dy * f.sy[1] + rs_sample_step(f, 1, s),
                                    f.e[2] + dx * f.sx[2] + dy * f.sy[2] + rs_sample_step(f, 2, s), c)) {
 #pragma unroll
@@ -483,6 +579,13 @@ __global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_tex_kernel(MeshB
     rs_resolve_aa<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_mip_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
+                                                                           long npix, float fx, float fy, float znear,
+                                                                           const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                                           int* __restrict__ visibility) {
+    rs_resolve_aa<true, true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+}
+
 // one lane per face of the whole batch: out fp32 [sumF][3], the colour the voxeliser takes for the face
 __global__ __launch_bounds__(RS_THREADS) void mesh_face_colours_kernel(MeshBatch m, long sumF, float* __restrict__ out) {
     const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -507,6 +610,88 @@ __global__ __launch_bounds__(RS_THREADS) void mesh_face_colours_kernel(MeshBatch
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)gf * 3 + k] = kd[k];
+}
+
+// ---- the mip pyramid (mesh_batch.h lays it out and states the texel rule) ----
+#define MIP_LANE_LEVELS 3                       // levels 0 .. 2 take one lane per texel (a footprint of at most 9 x 9), the others a wave
+// The part of S = sum_i sum_j wy(i) wx(j) texel0[i][j][k], k = R, G, B, of texel (y, x) of a level of size (Hl, Wl) that falls to the rows
+// i0 + li, i0 + li + si, ... and the columns j0 + lj, j0 + lj + sj, ... of its footprint.  src: level 0; reads stay in [0, last].
+__device__ __forceinline__ void mip_partial(const unsigned* __restrict__ texels, long src, long last, int H0, int W0, int Hl, int Wl, int y, int x,
+                                            int li, int si, int lj, int sj, long* S) {
+    const long ya = (long)y * H0, yb = ya + H0, xa = (long)x * W0, xb = xa + W0;    // the texel's span in units of 1 / (H0 Hl), 1 / (W0 Wl)
+    const long i0 = ya / Hl, i1 = (yb - 1) / Hl, j0 = xa / Wl, j1 = (xb - 1) / Wl;
+    for (long i = i0 + li; i <= i1; i += si) {
+        const long wy = max(0L, min(yb, (i + 1) * Hl) - max(ya, i * Hl));
+        const long row = src + i * W0;
+        u64 r[3] = {0, 0, 0};
+        for (long j = j0 + lj; j <= j1; j += sj) {
+            const unsigned wx = (unsigned)max(0L, min(xb, (j + 1) * Wl) - max(xa, j * Wl));     // at most Wl <= 2^24: wx byte fits 32 bits
+            const unsigned p = texels[min(max(row + j, 0L), last)];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r[k] += (u64)(wx * ((p >> (8 * k)) & 255u));
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) S[k] += wy * (long)r[k];
+    }
+}
+
+// blockIdx.y strides over the textures, the waves of blockIdx.x over the work items of a texture's chain: first the texels of levels
+// 0 .. MIP_LANE_LEVELS - 1 in groups of 64, a lane each, then every texel of the coarser levels, a wave each - its lanes tile the
+// footprint 8 x 8 and the integer sums, which do not depend on the order, are reduced across the wave.  One dword store per texel.
+__global__ __launch_bounds__(RS_THREADS) void texture_mips_kernel(const unsigned* __restrict__ texels, const long* __restrict__ tex_off,
+                                                                  const int* __restrict__ tex_size, int T, long sum_texels,
+                                                                  const long* __restrict__ mip_off, long sum_mip, unsigned* __restrict__ mip) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long last = min(tex_off[T], sum_texels) - 1, end = min(mip_off[T], sum_mip);
+    if (last < 0) return;
+    for (int t = blockIdx.y; t < T; t += gridDim.y) {
+        const int H0 = tex_size[2 * t], W0 = tex_size[2 * t + 1];
+        if (H0 < 1 || W0 < 1) continue;
+        const long src = tex_off[t], dst = mip_off[t], D = (long)H0 * W0;
+        const int L = mb_mip_levels(H0, W0);
+        long fine = 0, all = 0;                                         // the texels of the lane levels, of the whole chain
+        for (int l = 0; l < L; ++l) {
+            const long sz = (long)max(1, H0 >> l) * max(1, W0 >> l);
+            all += sz;
+            if (l < MIP_LANE_LEVELS) fine += sz;
+        }
+        const long groups = (fine + 63) >> 6, items = groups + (all - fine);
+        for (long item = (long)blockIdx.x * (RS_THREADS / 64) + wave; item < items; item += (long)gridDim.x * (RS_THREADS / 64)) {
+            const bool wide = item >= groups;                           // the same in every lane of the wave
+            const long c = wide ? fine + (item - groups) : item * 64 + lane;        // the texel, counted from the chain's start
+            if (!wide && c >= fine) continue;
+            int l = 0;
+            long start = 0, sz = D;
+            while (l < L - 1 && c >= start + sz) {
+                start += sz;
+                ++l;
+                sz = (long)max(1, H0 >> l) * max(1, W0 >> l);
+            }
+            const int Hl = max(1, H0 >> l), Wl = max(1, W0 >> l);
+            const int y = (int)((c - start) / Wl), x = (int)((c - start) - (long)y * Wl);
+            const long at = dst + c;
+            const bool writes = (wide ? lane == 0 : true) && at >= 0 && at < end;
+            if (l == 0) {                                               // level 0: the texture itself
+                if (writes) mip[at] = texels[min(max(src + c, 0L), last)];
+                continue;
+            }
+            long S[3] = {0, 0, 0};
+            if (wide) {
+                mip_partial(texels, src, last, H0, W0, Hl, Wl, y, x, lane >> 3, 8, lane & 7, 8, S);
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    for (int o = 32; o > 0; o >>= 1) S[k] += __shfl_xor(S[k], o);
+            } else {
+                mip_partial(texels, src, last, H0, W0, Hl, Wl, y, x, 0, 1, 0, 1, S);
+            }
+            if (writes) {
+                unsigned p = 0xFF000000u;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p |= ((unsigned)((2 * S[k] + D) / (2 * D)) & 255u) << (8 * k);
+                mip[at] = p;
+            }
+        }
+    }
 }
 
 static bool rs_sizes_ok(long sumF, int N, int views, int H, int W) {
@@ -545,7 +730,9 @@ static int rs_check(int N, long sumF, int views, int H, int W, double yfov, doub
     return TRI_OK;
 }
 
-static int rs_render(const MeshBatch& m, bool tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+enum { RS_PLAIN = 0, RS_TEX = 1, RS_MIP = 2 };   // which resolve kernel colours the pixels
+
+static int rs_render(const MeshBatch& m, int tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
                      void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
     const int N = m.N;
     const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 1, who);
@@ -566,7 +753,8 @@ static int rs_render(const MeshBatch& m, bool tex, const float* cam, long sumF, 
         raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
     }
     const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
-    if (tex) raster_resolve_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    if (tex == RS_MIP) raster_resolve_mip_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    else if (tex == RS_TEX) raster_resolve_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
     else raster_resolve_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
     return tri_check_launch(who);
 }
@@ -575,7 +763,7 @@ extern "C" int tri_raster_render(const float* verts, const int* faces, const lon
                                  const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
                                  double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
-    return rs_render(m, false, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
+    return rs_render(m, RS_PLAIN, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
 }
 
 extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
@@ -588,24 +776,17 @@ extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const
         return TRI_ERR_ARG;
     }
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
-    return rs_render(m, true, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_tex");
+    return rs_render(m, RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_tex");
 }
 
-extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                    const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                    const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
-                                    int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const char* who = "tri_raster_render_aa";
-    if (T < 0) { tri_set_error("tri_raster_render_aa: negative size"); return TRI_ERR_ARG; }
-    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
-        tri_set_error("tri_raster_render_aa: T > 0 needs all five texture fields");
-        return TRI_ERR_ARG;
-    }
+// the four-sample launches; tex: RS_TEX or RS_MIP, and a batch without textures (T == 0) takes the plain resolve either way
+static int rs_render_aa(const MeshBatch& m, int tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+                        void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
+    const int N = m.N;
     const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 4, who);
     if (bad != TRI_OK) return bad;
     const long npix = (long)N * views * H * W;
     if (npix == 0) return TRI_OK;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
     hipStream_t st = (hipStream_t)stream;
     u64* keys = (u64*)workspace;
     u64* qcount = keys + 4 * npix;
@@ -621,9 +802,56 @@ extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const 
         raster_queue_aa_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
     }
     const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
-    if (T > 0) raster_resolve_aa_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    if (m.T > 0 && tex == RS_MIP) raster_resolve_aa_mip_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
+    else if (m.T > 0) raster_resolve_aa_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
     else raster_resolve_aa_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
     return tri_check_launch(who);
+}
+
+extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                    const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                    const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
+                                    int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    if (T < 0) { tri_set_error("tri_raster_render_aa: negative size"); return TRI_ERR_ARG; }
+    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
+        tri_set_error("tri_raster_render_aa: T > 0 needs all five texture fields");
+        return TRI_ERR_ARG;
+    }
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    return rs_render_aa(m, RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_aa");
+}
+
+extern "C" int tri_texture_mips(const uint8_t* texels, const long* tex_off, const int* tex_size, int T, long sum_texels, const long* mip_off,
+                                long sum_mip, uint8_t* mip_texels, void* stream) {
+    if (T < 0 || sum_texels < 0 || sum_mip < 0) { tri_set_error("tri_texture_mips: negative size"); return TRI_ERR_ARG; }
+    if (T == 0 || sum_mip == 0) return TRI_OK;                          // an empty pyramid
+    if (!texels || !tex_off || !tex_size || !mip_off || !mip_texels || sum_texels == 0) {
+        tri_set_error("tri_texture_mips: T > 0 needs the texels, both offset tables, the sizes and the output");
+        return TRI_ERR_ARG;
+    }
+    if (sum_mip < sum_texels) { tri_set_error("tri_texture_mips: a pyramid holds at least the texels of its level 0"); return TRI_ERR_ARG; }
+    const unsigned gx = (unsigned)min(1024L, sum_mip / T / 128 + 1), gy = (unsigned)min(T, 256);
+    texture_mips_kernel<<<dim3(gx, gy), RS_THREADS, 0, (hipStream_t)stream>>>((const unsigned*)texels, tex_off, tex_size, T, sum_texels, mip_off,
+                                                                              sum_mip, (unsigned*)mip_texels);
+    return tri_check_launch("tri_texture_mips");
+}
+
+extern "C" int tri_raster_render_mip(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                     const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
+                                     const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear, int samples,
+                                     void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const char* who = "tri_raster_render_mip";
+    if (T < 0) { tri_set_error("tri_raster_render_mip: negative size"); return TRI_ERR_ARG; }
+    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_mip: samples must be 1 or 4"); return TRI_ERR_ARG; }
+    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size || !mip_texels || !mip_off)) {
+        tri_set_error("tri_raster_render_mip: T > 0 needs all five texture fields and both pyramid fields");
+        return TRI_ERR_ARG;
+    }
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
+                      (const unsigned*)mip_texels, mip_off};
+    if (samples == 4) return rs_render_aa(m, RS_MIP, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
+    return rs_render(m, T > 0 ? RS_MIP : RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 
 extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,

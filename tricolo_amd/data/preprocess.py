@@ -2,7 +2,7 @@
 splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
-        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on] [--antialias off|4x]
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on|mip] [--antialias off|4x]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
@@ -18,6 +18,13 @@ of the models (data/materials.py load_obj_textured; textures above 256 texels on
 ops.render_views_textured: Kd x texel, repeat wrap, bilinear, no mip-maps.  Voxels made from the meshes (--voxels mesh | auto) then
 take one colour per face, ops.mesh_face_colours: Kd times the mean of four texture samples of the face.  The summary names the
 models with at least one loaded texture and the map_Kd files that could not be loaded (such a material keeps its Kd).
+
+--textures mip is --textures on with mip-mapped texture lookups in the renderings: ops.texture_mips builds the pyramid of every
+texture once per packed batch (exact integer box means of the texture itself), and ops.render_views_textured(..., mips=) blends the
+two levels around the footprint of a pixel - with --antialias 4x, of a sample - in the texture, so that a face much smaller on
+screen than its texture shows the texture's mean colour, not four texels picked at random.  A magnified texture renders exactly as
+under --textures on.  The voxel colours are those of --textures on (ops.mesh_face_colours does not read the pyramid).  The level
+rule is a definition of our own (data/render.py, head of csrc/raster.hip): no pixel of it has been compared with pyrender's.
 
 --antialias 4x (the default is off: visibility is decided at the pixel centre alone) renders with four coverage samples per pixel,
 ops.render_views(..., samples=4): the 4x rotated grid, every sample covered, depth-tested and coloured by the one-sample rules, the
@@ -57,7 +64,7 @@ from .nrrd import read_nrrd
 VOXEL_SIZES = (32, 64, 128)
 SPLITS = ("train", "val", "test")
 VOXEL_SOURCES = ("nrrd", "mesh", "auto")
-TEXTURE_MODES = ("off", "on")
+TEXTURE_MODES = ("off", "on", "mip")
 ANTIALIAS_MODES = {"off": 1, "4x": 4}                # --antialias -> samples per pixel
 
 
@@ -111,21 +118,23 @@ def nrrd_path(data_root, mid, v):
 
 
 def pack_batch(meshes, device, textures=False):
-    """MeshBatch.pack of load_obj_materials' (or, with textures, load_obj_textured's) tuples; with textures the voxeliser's batch too."""
+    """MeshBatch.pack of load_obj_materials' (or, with textures, load_obj_textured's) tuples; with textures the voxeliser's batch too.
+    textures="mip": the packed batch carries the mip pyramid of its textures, built here, once per batch."""
     if not textures:
         packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device)
         return packed, packed
     from .. import ops
     packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_uv_list=[m[5] for m in meshes],
                             mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes])
-    return packed, packed.with_face_colours(ops.mesh_face_colours(packed))
+    solid = packed.with_face_colours(ops.mesh_face_colours(packed))
+    return (packed.with_texture_mips() if textures == "mip" else packed), solid
 
 
 def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd",
                 textures=False, texture_stats=None, samples=1):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
     come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist).
-    textures: read and render map_Kd textures, and colour mesh voxels from them; texture_stats, a dict, then gains the number of
+    textures: read and render map_Kd textures, and colour mesh voxels from them ("mip": render them mip-mapped); texture_stats, a dict, then gains the number of
     "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded).
     samples: coverage samples per pixel, 1 or 4 (render.render_batch)."""
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
@@ -141,7 +150,7 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
         if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
-            solid = pack_batch([meshes[k] for k in from_mesh], device, textures)[1]
+            solid = pack_batch([meshes[k] for k in from_mesh], device, bool(textures))[1]
         made = {f"voxel{v}": voxelize.voxelize_batch(solid, v, fill="carve").cpu().numpy() for v in VOXEL_SIZES} if from_mesh else {}
         for k, ((cat, mid), views) in enumerate(zip(batch, images)):
             if k in from_mesh:
@@ -159,7 +168,7 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
 
 
 def main(argv=None, log=print):
-    """-> {split: {"models", "written", "skipped"}}, with --textures on also "textured_models" and "texture_failures"."""
+    """-> {split: {"models", "written", "skipped"}}, with --textures on | mip also "textured_models" and "texture_failures"."""
     ap = argparse.ArgumentParser(prog="python -m tricolo_amd.data.preprocess", description=__doc__.split("\n\n")[0])
     ap.add_argument("overrides", nargs="*", help="config overrides, e.g. data=text2shape_chair_table data.dataset_root_path=...")
     ap.add_argument("--batch-meshes", type=int, default=8, help="meshes rendered per call")
@@ -168,7 +177,8 @@ def main(argv=None, log=print):
     ap.add_argument("--voxels", choices=VOXEL_SOURCES, default="nrrd", help="the grids: the nrrd_256_filter_div_{V}_solid downloads, voxelised "
                     "from the meshes, or auto (the downloads where all three sizes exist for a model)")
     ap.add_argument("--textures", choices=TEXTURE_MODES, default="off", help="on: render map_Kd textures (ops.render_views_textured) and colour "
-                    "mesh voxels from them; off: a textured material renders with its bare Kd")
+                    "mesh voxels from them; mip: the same with mip-mapped lookups in the renderings (ops.texture_mips); off: a textured "
+                    "material renders with its bare Kd")
     ap.add_argument("--antialias", choices=tuple(ANTIALIAS_MODES), default="off", help="4x: four coverage samples per pixel (the 4x rotated grid), "
                     "the pixel their rounded mean; off: visibility at the pixel centre alone")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
@@ -186,9 +196,9 @@ def main(argv=None, log=print):
                                                    os.path.join(data.dataset_path, "shapenet.json"), map_path, data.ignored_models)
         else:
             keys = read_model_ids(map_path)
-        tex = {"textured_models": 0, "texture_failures": 0} if args.textures == "on" else {}
+        tex = {"textured_models": 0, "texture_failures": 0} if args.textures != "off" else {}
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
-                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, args.textures == "on", tex,
+                                       args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, {"off": False, "on": True, "mip": "mip"}[args.textures], tex,
                                        ANTIALIAS_MODES[args.antialias])
         stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")

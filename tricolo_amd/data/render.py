@@ -15,7 +15,14 @@ Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliber
   * map_Kd textures are opt-in (ops.render_views_textured, textures=True below; the default renders a textured material with its
     bare Kd): colour = Kd x texel, the MTL rule and - from their documentation - what trimesh's SimpleMaterial becomes in pyrender
     (baseColorFactor x baseColorTexture); repeat wrap, bilinear over texel centres at the perspective-correct (u, v) of the pixel
-    centre, NO mip-maps (the parser bounds minification by reducing textures to 256 texels on a side), no gamma;
+    centre, no gamma.  That call has NO mip-maps (the parser reduces textures to 256 texels on a side, which bounds the minification
+    but a face much smaller on screen than its texture still aliases).  Mip-mapping is opt-in as well (mips= of
+    ops.render_views_textured, textures="mip" below, --textures mip of data/preprocess.py): ops.texture_mips builds a pyramid of exact
+    integer box means of every texture, and a pixel (with samples=4, a sample) blends the two levels around log2(rho), rho the longer
+    of the two steps of (u, v), in texels, to the pixel on the right and to the pixel below - isotropic, no LOD bias; a magnified
+    texture (rho <= 1) keeps the colours of the plain call bit for bit.  pyrender samples its textures through a mip chain too, but
+    the level rule here is OUR OWN DEFINITION (head of csrc/raster.hip), like the voxeliser's: nobody has compared a pixel of it with
+    pyrender's output, nor its level selection with OpenGL's;
   * no near-plane clipping: a face with a vertex nearer than znear is dropped whole.  model_normalized.obj lies within 0.5 of its
     centre and the camera stands 0.85 away, so no face of such a mesh comes near the plane;
   * anti-aliasing is opt-in (samples=4 below, --antialias 4x of data/preprocess.py; the default decides visibility at the pixel
@@ -200,16 +207,30 @@ def face_textures(face_mat, mat_tex, face_uv, T):
 def sample_textures(t, u, v, texels, tex_off, tex_size):
     """csrc/mesh_batch.h mb_tex_sample: textures t int64 [P] (0 <= t < T) at u, v fp32 [P] -> (ok bool [P], c fp32 [P, 3]); rows of c
     with ok False (a non-finite u or v) mean nothing."""
+    return _sample_level(u, v, tex_size[t, 0].to(torch.int64), tex_size[t, 1].to(torch.int64), tex_off[t], int(tex_off[-1]) - 1, texels)
+
+
+def sample_mip_level(t, level, u, v, mip_texels, mip_off, tex_size):
+    """csrc/mesh_batch.h mb_mip_sample: level `level` int64 [P] (0 <= level < the texture's levels) of the pyramids of textures t
+    int64 [P] at u, v fp32 [P] -> (ok, c) as sample_textures; the level's start is walked from tex_size as the kernels walk it."""
+    H0, W0 = tex_size[t, 0].to(torch.int64), tex_size[t, 1].to(torch.int64)
+    base = mip_off[t].clone()
+    for k in range(int(level.max()) if level.numel() else 0):
+        base += torch.where(k < level, (H0 >> k).clamp(min=1) * (W0 >> k).clamp(min=1), torch.zeros_like(base))
+    return _sample_level(u, v, (H0 >> level).clamp(min=1), (W0 >> level).clamp(min=1), base, int(mip_off[-1]) - 1, mip_texels)
+
+
+def _sample_level(u, v, Ht, Wt, base, last, texels):
+    """The sampling rule itself on one image per row: size (Ht, Wt) int64 [P], its first texel at base int64 [P] of texels, no index
+    beyond `last`."""
     ok = torch.isfinite(u) & torch.isfinite(v)
     u, v = torch.where(ok, u, torch.zeros_like(u)), torch.where(ok, v, torch.zeros_like(v))
-    Ht, Wt = tex_size[t, 0].to(torch.int64), tex_size[t, 1].to(torch.int64)
     u, v = u - torch.floor(u), v - torch.floor(v)
     x, y = u * Wt.to(torch.float32) - 0.5, (1.0 - v) * Ht.to(torch.float32) - 0.5
     xf, yf = torch.floor(x), torch.floor(y)
     fx, fy = (x - xf)[:, None], (y - yf)[:, None]
     xa, ya = torch.remainder(xf.to(torch.int64), Wt), torch.remainder(yf.to(torch.int64), Ht)
     xb, yb = torch.where(xa + 1 == Wt, torch.zeros_like(xa), xa + 1), torch.where(ya + 1 == Ht, torch.zeros_like(ya), ya + 1)
-    base, last = tex_off[t], int(tex_off[-1]) - 1
 
     def texel(row, col):
         return TEXEL_VALUE[texels[(base + row * Wt + col).clamp(0, last), :3].to(torch.int64)]
@@ -219,10 +240,58 @@ def sample_textures(t, u, v, texels, tex_off, tex_size):
     return ok, a + (b - a) * fy
 
 
-def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size, offsets=CENTRE):
+def texture_mips_cpu(texels, tex_off, tex_size):
+    """ops.texture_mips on CPU tensors -> (mip_texels u8 [sumMipTexels, 4], mip_off int64 [T + 1]): the integers of csrc/mesh_batch.h in
+    torch.  Per level and axis the weights wy [H_l, H0], wx [W_l, W0] of the interval overlaps, S = wy texel0 wx^T in int64, the texel
+    (2 S + D) // (2 D) with D = H0 W0; level 0 is copied.  Dense weight matrices: untuned, for checking."""
+    from ..meshes import mip_level_sizes, mip_offsets
+    mip_off = mip_offsets(tex_size)
+    out = torch.empty((int(mip_off[-1]), 4), dtype=torch.uint8)
+    for t, (H0, W0) in enumerate(tex_size.tolist()):
+        src = texels[int(tex_off[t]):int(tex_off[t]) + H0 * W0]
+        at = int(mip_off[t])
+        out[at:at + H0 * W0] = src
+        at += H0 * W0
+        tex = src[:, :3].reshape(H0, W0, 3).to(torch.int64)
+        for Hl, Wl in mip_level_sizes(H0, W0)[1:]:
+            w = []
+            for n0, nl in ((H0, Hl), (W0, Wl)):                                     # overlap of [y n0, (y + 1) n0] with [i nl, (i + 1) nl]
+                y, i = torch.arange(nl)[:, None], torch.arange(n0)[None, :]
+                w.append((torch.minimum((y + 1) * n0, (i + 1) * nl) - torch.maximum(y * n0, i * nl)).clamp(min=0))
+            S = torch.einsum("yi,ijk,xj->yxk", w[0], tex, w[1])
+            D = H0 * W0
+            out[at:at + Hl * Wl, :3] = torch.div(2 * S + D, 2 * D, rounding_mode="floor").reshape(-1, 3).to(torch.uint8)
+            out[at:at + Hl * Wl, 3] = 255
+            at += Hl * Wl
+    return out, mip_off
+
+
+def sample_mips(t, u, v, right, down, mip_texels, mip_off, tex_size):
+    """The level of detail and the blend of two pyramid levels (head of csrc/raster.hip, rs_texel_mip_at): textures t int64 [P] at
+    u, v fp32 [P]; right, down: (u, v, d) of the same face one whole pixel to the right and one whole pixel down -> (ok, c) as
+    sample_textures."""
+    (ux, vx, dx), (uy, vy, dy) = right, down
+    H0, W0 = tex_size[t, 0].to(torch.int64), tex_size[t, 1].to(torch.int64)
+    Hf, Wf = H0.to(torch.float32), W0.to(torch.float32)
+    a, b, c, e = (ux - u) * Wf, (vx - v) * Hf, (uy - u) * Wf, (vy - v) * Hf
+    r2 = torch.maximum(a * a + b * b, c * c + e * e)
+    bounded = (dx > 0) & (dy > 0) & torch.isfinite(ux) & torch.isfinite(vx) & torch.isfinite(uy) & torch.isfinite(vy) & torch.isfinite(r2)
+    rho = torch.sqrt(torch.where(bounded, r2, torch.ones_like(r2)))
+    top = torch.frexp(torch.maximum(H0, W0).to(torch.float64))[1].to(torch.int64) - 1     # levels - 1: the bit length of the longer side, - 1
+    mant, ex = torch.frexp(rho)                                                     # rho = mant 2^ex with mant in [0.5, 1)
+    l, g = ex.to(torch.int64) - 1, mant * 2.0 - 1.0                                 # floor(log2(rho)) and rho 2^-l - 1, both exact
+    two = bounded & (rho > 1.0) & (l < top)
+    lo = torch.where(bounded, torch.where(rho <= 1.0, torch.zeros_like(top), torch.where(l < top, l, top)), top)
+    ok, c0 = sample_mip_level(t, lo, u, v, mip_texels, mip_off, tex_size)
+    _, c1 = sample_mip_level(t, torch.where(two, lo + 1, lo), u, v, mip_texels, mip_off, tex_size)
+    return ok, torch.where(two[:, None], c0 + (c1 - c0) * g[:, None], c0)
+
+
+def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size, offsets=CENTRE, mips=None):
     """(has bool [HW S], c fp32 [HW S, 3]) of one mesh and one view: where the winning face of vis int64 [HW S] (the S = len(offsets)
     samples of a pixel innermost) is textured, and the texture colour at the perspective-correct (u, v) of the sample's own position
-    - the pixel centre for CENTRE."""
+    - the pixel centre for CENTRE.  mips: the pyramid pair; the colour is then sample_mips', its footprint from the positions one whole
+    pixel (256) to the right and down."""
     has = torch.zeros((vis.numel(),), dtype=torch.bool)
     c = torch.ones((vis.numel(), 3), dtype=torch.float32)
     pix = torch.nonzero((vis >= 0) & (face_t[vis.clamp(min=0)] >= 0)).reshape(-1)
@@ -234,17 +303,24 @@ def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texe
     pixel, s = torch.div(pix, S, rounding_mode="floor"), pix % S
     Px, Py = 256 * (pixel % W) + off[s, 0], 256 * torch.div(pixel, W, rounding_mode="floor") + off[s, 1]
     fa = A2[f].to(torch.float32)
-    w = []
-    for k in range(3):
-        a, b = (k + 1) % 3, (k + 2) % 3
-        e = (X[f, b] - X[f, a]) * (Py - Y[f, a]) - (Y[f, b] - Y[f, a]) * (Px - X[f, a])
-        w.append((e.to(torch.float32) / fa) * d[f, k])
-    dd = (w[0] + w[1]) + w[2]
-    bw = [wk / dd for wk in w]
     uv = face_uv[f].gather(1, order[f][:, :, None].expand(-1, 3, 2))
-    u = (bw[0] * uv[:, 0, 0] + bw[1] * uv[:, 1, 0]) + bw[2] * uv[:, 2, 0]
-    v = (bw[0] * uv[:, 0, 1] + bw[1] * uv[:, 1, 1]) + bw[2] * uv[:, 2, 1]
-    ok, col = sample_textures(face_t[f], u, v, texels, tex_off, tex_size)
+
+    def uvd(Px, Py):
+        w = []
+        for k in range(3):
+            a, b = (k + 1) % 3, (k + 2) % 3
+            e = (X[f, b] - X[f, a]) * (Py - Y[f, a]) - (Y[f, b] - Y[f, a]) * (Px - X[f, a])
+            w.append((e.to(torch.float32) / fa) * d[f, k])
+        dd = (w[0] + w[1]) + w[2]
+        bw = [wk / dd for wk in w]
+        return ((bw[0] * uv[:, 0, 0] + bw[1] * uv[:, 1, 0]) + bw[2] * uv[:, 2, 0],
+                (bw[0] * uv[:, 0, 1] + bw[1] * uv[:, 1, 1]) + bw[2] * uv[:, 2, 1], dd)
+
+    u, v, _ = uvd(Px, Py)
+    if mips is None:
+        ok, col = sample_textures(face_t[f], u, v, texels, tex_off, tex_size)
+    else:
+        ok, col = sample_mips(face_t[f], u, v, uvd(Px + 256, Py), uvd(Px, Py + 256), mips[0], mips[1], tex_size)
     has[pix[ok]] = True
     c[pix[ok]] = col[ok]
     return has, c
@@ -276,11 +352,12 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
 
 
 def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
-                     return_visibility=False, textures=None, samples=1):
+                     return_visibility=False, textures=None, samples=1, mips=None):
     """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch.  textures: the five
     texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured.  samples=4: coverage,
     depth and colour at the four SAMPLE_OFFSETS of every pixel, the pixel their rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2 per
-    channel, the visibility int32 [N, views, H, W, 4]."""
+    channel, the visibility int32 [N, views, H, W, 4].  mips: the pyramid pair (texture_mips_cpu) for the mip-mapped colours of
+    ops.render_views_textured(..., mips=)."""
     if samples not in (1, 4):
         raise ValueError(f"render_views_cpu: samples must be 1 or 4, got {samples!r}")
     offsets = SAMPLE_OFFSETS if samples == 4 else CENTRE
@@ -304,7 +381,7 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
                 face_uv, mat_tex, texels, tex_off, tex_size = textures
                 uv = face_uv[foff[n]:foff[n + 1]]
                 face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
-                tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size, offsets)
+                tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size, offsets, mips)
             colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex)
             if samples == 4:
                 colour = ((colour.view(3, H * W, 4).to(torch.int32).sum(dim=2) + 2) >> 2).to(torch.uint8)
@@ -338,20 +415,29 @@ def mesh_face_colours_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
 def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1):
     """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
     [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
-    ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures).  samples=4:
-    four coverage samples per pixel (ops.render_views)."""
+    ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures).
+    textures="mip": render_views_textured with the mip pyramid of the batch's textures, built here (MeshBatch.with_texture_mips)
+    unless the batch carries one.  samples=4: four coverage samples per pixel (ops.render_views)."""
     from .. import ops
+    if not isinstance(textures, bool) and textures != "mip":
+        raise ValueError(f"textures must be False, True or \"mip\", got {textures!r}")
     cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
     H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
     if textures:
-        return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples)
+        mips = None
+        if textures == "mip":
+            if batch.tex_size is None:
+                raise ValueError("render_batch: the batch was packed without textures (MeshBatch.pack(..., face_uv_list=, mat_tex_list=, textures_list=))")
+            mips = (batch if batch.mip_texels is not None else batch.with_texture_mips()).mip_tensors
+        return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples,
+                                         mips=mips)
     return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples)
 
 
 def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False,
                   textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1):
     """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None); textures=True
-    needs the three texture lists of MeshBatch.pack."""
+    and textures="mip" need the three texture lists of MeshBatch.pack."""
     batch = MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device, face_uv_list=face_uv_list, mat_tex_list=mat_tex_list,
                            textures_list=textures_list)
     return render_batch(batch, num_views, image_size, return_visibility, textures, samples)

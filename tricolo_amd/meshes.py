@@ -121,6 +121,38 @@ def check_textures(face_uv, mat_tex, texels, tex_off, tex_size, num_faces, num_m
         raise ValueError("tex_off must be the running sum of H * W over tex_size and end at the number of texels")
 
 
+def mip_level_sizes(height, width):
+    """[(H_l, W_l)] of the mip chain of a texture of size (height, width), both >= 1: floor(log2(max(H, W))) + 1 levels, level l of
+    size (max(1, H >> l), max(1, W >> l)) (csrc/mesh_batch.h)."""
+    height, width = int(height), int(width)
+    return [(max(1, height >> l), max(1, width >> l)) for l in range(max(height, width).bit_length())]
+
+
+def mip_offsets(tex_size):
+    """int64 [T + 1] on the host: where the chain of every texture starts in the pyramid, the running sum of the chain lengths."""
+    off = [0]
+    for h, w in tex_size.to("cpu", torch.int64).tolist():
+        off.append(off[-1] + sum(hl * wl for hl, wl in mip_level_sizes(h, w)))
+    return torch.tensor(off, dtype=torch.int64)
+
+
+def check_texture_mips(mip_texels, mip_off, tex_size):
+    """The two pyramid fields of csrc/mesh_batch.h against the batch's tex_size, validated on the host (ValueError): shapes and
+    dtypes, one device, mip_off the running sum of the chain lengths ending at the number of pyramid texels."""
+    for name, x, dtype, tail in (("mip_texels", mip_texels, torch.uint8, (4,)), ("mip_off", mip_off, torch.int64, ())):
+        if not torch.is_tensor(x) or x.dtype != dtype or x.dim() != 1 + len(tail) or tuple(x.shape[1:]) != tail:
+            raise ValueError(f"{name} must be a {dtype} tensor of shape {['*', *tail]}")
+    if not mip_texels.device == mip_off.device == tex_size.device:
+        raise ValueError("the mip pyramid must live on the device of the textures it was built from")
+    T = tex_size.shape[0]
+    if mip_off.shape[0] != T + 1:
+        raise ValueError(f"mip_off holds {mip_off.shape[0]} offsets for {T} textures")
+    want = mip_offsets(tex_size)
+    if not torch.equal(mip_off.cpu(), want) or int(want[-1]) != mip_texels.shape[0]:
+        raise ValueError(f"mip_off must be the running sum of the chain lengths of tex_size and end at the number of pyramid texels: "
+                         f"{int(want[-1])} for these textures, got {mip_texels.shape[0]}")
+
+
 def pack_textures(face_uv_list, mat_tex_list, textures_list, device=None):
     """Per mesh: face_uv fp32 [F, 3, 2] (a NaN row = no texture coordinates), mat_tex int [M] indexing that mesh's own list of
     textures (-1 = none), textures a list of uint8 [H, W, 4] RGBA arrays or tensors (row 0 = top)
@@ -162,7 +194,7 @@ def host_boxes(verts_list):
 @dataclass
 class MeshBatch:
     """A packed batch on one device; the three material tensors are None for a batch packed without materials, the five texture
-    tensors for a batch packed without textures."""
+    tensors for a batch packed without textures, the two pyramid tensors until with_texture_mips() has built them."""
     verts: torch.Tensor
     faces: torch.Tensor
     vert_off: torch.Tensor
@@ -177,6 +209,8 @@ class MeshBatch:
     texels: torch.Tensor | None = None
     tex_off: torch.Tensor | None = None
     tex_size: torch.Tensor | None = None
+    mip_texels: torch.Tensor | None = None          # the mip pyramid of the textures (with_texture_mips); None without one
+    mip_off: torch.Tensor | None = None
 
     @classmethod
     def pack(cls, verts_list, faces_list, face_mat_list=None, kd_list=None, device=None, *, face_uv_list=None, mat_tex_list=None,
@@ -213,6 +247,22 @@ class MeshBatch:
     @property
     def texture_tensors(self):                      # the next five arguments of ops.render_views_textured and ops.mesh_face_colours
         return self.face_uv, self.mat_tex, self.texels, self.tex_off, self.tex_size
+
+    @property
+    def mip_tensors(self):                          # the mips= pair of ops.render_views_textured, None for a batch without a pyramid
+        return None if self.mip_texels is None else (self.mip_texels, self.mip_off)
+
+    def with_texture_mips(self):
+        """The batch with the mip pyramid of its textures (ops.texture_mips, built once on the batch's device; validated by
+        check_texture_mips): what render_batch(..., textures="mip") renders from.  Everything else is shared, not copied."""
+        from dataclasses import replace
+
+        from . import ops
+        if self.tex_size is None:
+            raise ValueError("with_texture_mips: the batch was packed without textures")
+        mip_texels, mip_off = ops.texture_mips(self.texels, self.tex_off, self.tex_size)
+        check_texture_mips(mip_texels, mip_off, self.tex_size)
+        return replace(self, mip_texels=mip_texels, mip_off=mip_off)
 
     def with_face_colours(self, colours):
         """The batch with one material per face, `colours` fp32 [sumF, 3] (ops.mesh_face_colours) as their Kd, and no textures: what

@@ -1686,9 +1686,11 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
 RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
 
 
-def _render_views_aa(stage, N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, textures, cam, H, W, yfov, znear, return_visibility):
+def _render_views_aa(stage, N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, textures, cam, H, W, yfov, znear, return_visibility,
+                     mips=None):
     """The samples=4 path of render_views and render_views_textured, their arguments already checked (textures: the five texture
-    tensors, or None and T == 0 for a batch without them): tri_raster_render_aa, on CPU tensors render_views_cpu(samples=4)."""
+    tensors, or None and T == 0 for a batch without them; mips: the checked pyramid pair, or None): tri_raster_render_aa or, with
+    mips, tri_raster_render_mip; on CPU tensors render_views_cpu(samples=4)."""
     views, sumF = cam.shape[1], faces.shape[0]
     if N * views * H * W * 4 >= RENDER_MAX_PIXELS or views > 65535:
         raise ValueError(f"{stage}: {N} meshes x {views} views x {H} x {W} pixels x 4 samples need a visibility buffer of "
@@ -1696,10 +1698,15 @@ def _render_views_aa(stage, N, T, verts, faces, vert_off, face_off, face_mat, ma
     if not verts.is_cuda:
         from .data.render import render_views_cpu
         return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
-                                textures=textures, samples=4)
+                                textures=textures, samples=4, mips=mips)
     image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
     vis = torch.empty((N, views, H, W, 4), dtype=torch.int32, device=verts.device) if return_visibility else None
     ws = torch.empty((max(16, lib().tri_raster_workspace_aa(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+    if mips is not None:
+        check(lib().tri_raster_render_mip(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
+                                          *(ptr(x) for x in textures), T, ptr(mips[0]), ptr(mips[1]), ptr(cam), N, sumF, views, H, W,
+                                          float(yfov), float(znear), 4, ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_mip")
+        return (image, vis) if return_visibility else image
     check(lib().tri_raster_render_aa(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
                                      *(ptr(x) for x in (textures or (None,) * 5)), T, ptr(cam), N, sumF, views, H, W, float(yfov),
                                      float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_aa")
@@ -1772,8 +1779,61 @@ def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_
     return T
 
 
+def texture_mips(texels, tex_off, tex_size):
+    """The mip pyramid of every texture of a packed batch (MeshBatch.texture_tensors[2:]) -> (mip_texels u8 [sumMipTexels, 4], mip_off
+    int64 [T + 1]) on the textures' device, laid out as csrc/mesh_batch.h says: texture t of size (H0, W0) has floor(log2(max(H0, W0)))
+    + 1 levels of size (max(1, H0 >> l), max(1, W0 >> l)), its chain from mip_off[t], level 0 (a copy of the texture) first.  A texel
+    of a level l >= 1 is the area-weighted box mean of the part of LEVEL 0 it covers, in exact integers, half rounded up; alpha 255.
+    On the GPU one launch of tri_texture_mips builds all levels of all textures; the sizes (not the texels) are read back once to
+    size the output and form mip_off.  CPU tensors run data.render.texture_mips_cpu, the same integers in torch.  T == 0 gives an
+    empty pyramid."""
+    from .meshes import TEXTURE_MAX_SIDE, mip_offsets
+    if not all(torch.is_tensor(x) for x in (texels, tex_off, tex_size)) or len({x.device for x in (texels, tex_off, tex_size)}) != 1:
+        raise ValueError("texture_mips: texels, tex_off and tex_size must be tensors on one device")
+    _mesh_arg(texels, "texels", torch.uint8, 4)
+    _mesh_arg(tex_size, "tex_size", torch.int32, 2)
+    T = tex_size.shape[0]
+    _mesh_arg(tex_off, "tex_off", torch.int64, numel=T + 1)
+    size = tex_size.to("cpu", torch.int64)
+    if T and (int(size.min()) < 1 or int(size.max()) > TEXTURE_MAX_SIDE):
+        raise ValueError(f"texture_mips: every texture needs 1 <= H, W <= 2^24, got sizes from {int(size.min())} to {int(size.max())}")
+    if int((size[:, 0] * size[:, 1]).sum()) != texels.shape[0]:
+        raise ValueError(f"texture_mips: tex_size describes {int((size[:, 0] * size[:, 1]).sum())} texels, texels holds {texels.shape[0]}")
+    if not texels.is_cuda:
+        from .data.render import texture_mips_cpu
+        return texture_mips_cpu(texels, tex_off, tex_size)
+    off = mip_offsets(size)
+    mip_off = off.to(texels.device)
+    mip_texels = torch.empty((int(off[-1]), 4), dtype=torch.uint8, device=texels.device)
+    check(lib().tri_texture_mips(ptr(texels), ptr(tex_off), ptr(tex_size), T, texels.shape[0], ptr(mip_off), mip_texels.shape[0],
+                                 ptr(mip_texels), stream()), "tri_texture_mips")
+    return mip_texels, mip_off
+
+
+def _mesh_mips(stage, texels, tex_size, mips):
+    """Checks the pyramid pair (texture_mips) a call was given for its textures -> (mip_texels, mip_off): one device with the batch,
+    dtypes and shapes, the total tex_size asks for and mip_off, the running sum of its chain lengths - the kernels clamp every texel
+    index to mip_off[T] - 1, so that table must not overstate the pyramid.  The few sizes and offsets are read back for it: a call
+    with mips= waits for the stream once."""
+    from .meshes import mip_offsets
+    if not isinstance(mips, (tuple, list)) or len(mips) != 2 or not all(torch.is_tensor(x) for x in mips):
+        raise ValueError(f"{stage}: mips must be the pair (mip_texels, mip_off) of ops.texture_mips")
+    mip_texels, mip_off = mips
+    if mip_texels.device != texels.device or mip_off.device != texels.device:
+        raise ValueError(f"{stage}: the mip pyramid lives on {mip_texels.device}, the batch on {texels.device}: all tensors must live on one device")
+    _mesh_arg(mip_texels, "mip_texels", torch.uint8, 4)
+    _mesh_arg(mip_off, "mip_off", torch.int64, numel=tex_size.shape[0] + 1)
+    want = mip_offsets(tex_size)
+    if mip_texels.shape[0] != int(want[-1]):
+        raise ValueError(f"{stage}: the pyramids of these textures hold {int(want[-1])} texels in all, mip_texels holds {mip_texels.shape[0]} - "
+                         "was it built from another batch?")
+    if not torch.equal(mip_off.cpu(), want):
+        raise ValueError(f"{stage}: mip_off must be the running sum of the chain lengths of tex_size")
+    return mip_texels, mip_off
+
+
 def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size, cam, H, W,
-                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1):
+                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1, mips=None):
     """render_views with map_Kd textures: the packed batch and its five texture tensors (MeshBatch.tensors, MeshBatch.texture_tensors).
     face_uv fp32 [sumF, 3, 2]: one (u, v) per face corner, NaN in face_uv[f, 0, 0] = the face has none; mat_tex int32 [sumM]: a
     batch-global texture index per material, -1 = none; texels u8 [sumTexels, 4] RGBA; tex_off int64 [T + 1]; tex_size int32 [T, 2]
@@ -1781,11 +1841,19 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
     clamp((Kd c) shade, 0, 1), c the texture at the perspective-correct (u, v) of the pixel centre - repeat wrap, bilinear, NO
     mip-maps (head of csrc/raster.hip) - and an untextured one exactly as by render_views.  Same limits; CPU tensors run the torch
     restatement of data.render.  samples=4: render_views' four samples, a textured face sampled at the (u, v) of each sample's own
-    position - 4x supersampling of the texture, which eases but does not replace the missing mip-maps."""
+    position - 4x supersampling of the texture, which eases but does not replace mip-maps.
+    mips=(mip_texels, mip_off), the pair of texture_mips for these textures (MeshBatch.with_texture_mips().mip_tensors), turns
+    mip-mapping on: the level of detail of a pixel - or of a sample, with samples=4 - comes from (u, v) there, one whole pixel to the
+    right and one whole pixel down, rho is the longer of the two steps in texels, and the colour blends the two pyramid levels around
+    log2(rho) (head of csrc/raster.hip; no LOD bias, no anisotropy).  Where the texture is magnified (rho <= 1) the colour is the one
+    without mips, bit for bit; visibility never changes.  The rule is this project's own definition: no pixel of it has been compared
+    with pyrender's mip-mapping.  mips=None, the default, is the call as it was."""
     H, W = int(H), int(W)
     samples = _render_samples("render_views_textured", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
     T = _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
+    if mips is not None:
+        mips = _mesh_mips("render_views_textured", texels, tex_size, mips)
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
     views, sumF = cam.shape[1], faces.shape[0]
@@ -1795,17 +1863,23 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
         raise ValueError("render_views_textured: 2^31 or more faces in one batch")
     if samples == 4:
         return _render_views_aa("render_views_textured", N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off,
-                                (face_uv, mat_tex, texels, tex_off, tex_size), cam, H, W, yfov, znear, return_visibility)
+                                (face_uv, mat_tex, texels, tex_off, tex_size), cam, H, W, yfov, znear, return_visibility, mips)
     if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
         raise ValueError(f"render_views_textured: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
                          f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
     if not verts.is_cuda:
         from .data.render import render_views_cpu
         return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
-                                textures=(face_uv, mat_tex, texels, tex_off, tex_size))
+                                textures=(face_uv, mat_tex, texels, tex_off, tex_size), mips=mips)
     image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
     vis = torch.empty((N, views, H, W), dtype=torch.int32, device=verts.device) if return_visibility else None
     ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+    if mips is not None:
+        check(lib().tri_raster_render_mip(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
+                                          ptr(face_uv), ptr(mat_tex), ptr(texels), ptr(tex_off), ptr(tex_size), T, ptr(mips[0]), ptr(mips[1]),
+                                          ptr(cam), N, sumF, views, H, W, float(yfov), float(znear), 1, ptr(ws), ptr(image), ptr(vis), stream()),
+              "tri_raster_render_mip")
+        return (image, vis) if return_visibility else image
     check(lib().tri_raster_render_tex(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
                                       ptr(face_uv), ptr(mat_tex), ptr(texels), ptr(tex_off), ptr(tex_size), T, ptr(cam), N, sumF, views, H, W,
                                       float(yfov), float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_tex")
