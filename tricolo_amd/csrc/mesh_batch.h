@@ -13,7 +13,7 @@
 // unsigned and clamped to T - 1, and with T == 0 every material is untextured.  Texture t is the tex_size[t] = (height, width) texels
 // from tex_off[t] (int64 [T + 1]) of texels u8 [sumTexels][4] = R, G, B, alpha (ignored, written as 255): one aligned dword each.  Row
 // 0 is the top row of the image and v = 0 its bottom (the OBJ convention).  mb_tex_sample below is THE sampling rule - repeat wrap,
-// bilinear, no mip-maps - of the textured resolve pass of raster.hip and of its face colours.
+// bilinear (mb_bilinear), no mip-maps - of the textured resolve pass of raster.hip and of its face colours.
 //
 // The mip pyramid (optional; the two fields are null in a batch without one; raster.hip's tri_texture_mips builds it and only its mip
 // resolve kernels read it).  Texture t of size (H0, W0) has L = floor(log2(max(H0, W0))) + 1 levels, level l of size
@@ -110,16 +110,12 @@ __device__ __forceinline__ int mb_mod(int i, int n) {
     return r < 0 ? r + n : r;
 }
 
-// c[0..2] = texture t (0 <= t < T) at (u, v), every operation rounded on its own; false, with c untouched, for a non-finite u or v:
+// c[0..2] = the image of size (Ht, Wt) whose texels start at `base` of `texels`, at a finite (u, v), every operation rounded on its own:
 //   u <- u - floorf(u), v likewise (repeat);  x = u W - 0.5,  y = (1 - v) H - 0.5;  x0 = floorf(x), fx = x - x0, y likewise;
 //   the four neighbours at columns x0, x0 + 1 modulo W and rows y0, y0 + 1 modulo H;  a channel is t = byte / 255 correctly rounded;
 //   a = t00 + (t10 - t00) fx (row y0),  b = t01 + (t11 - t01) fx (row y0 + 1),  c = a + (b - a) fy.
-// The host validates the tables (1 <= H, W <= 2^24, tex_off the running sum of H W); whatever they hold, no texel index leaves
-// [0, tex_off[T] - 1], and a texture without a texel reads as false.
-__device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u, float v, float* c) {
-    const int Ht = m.tex_size[2 * t], Wt = m.tex_size[2 * t + 1];
-    const long base = m.tex_off[t], last = m.tex_off[m.T] - 1;
-    if (!(fabsf(u) < INFINITY) || !(fabsf(v) < INFINITY) || Ht < 1 || Wt < 1 || last < 0) return false;
+// THE bilinear tap of a texture and of a pyramid level.  Ht, Wt >= 1 and last >= 0: whatever the tables hold, no texel index leaves [0, last].
+__device__ __forceinline__ void mb_bilinear(const unsigned* __restrict__ texels, long base, long last, int Ht, int Wt, float u, float v, float* c) {
     u = u - floorf(u);
     v = v - floorf(v);
     const float x = u * (float)Wt - 0.5f, y = (1.0f - v) * (float)Ht - 0.5f;
@@ -128,8 +124,8 @@ __device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u
     const int xa = mb_mod((int)fminf(xf, 2147483520.f), Wt), ya = mb_mod((int)fminf(yf, 2147483520.f), Ht);     // xf, yf >= -1
     const int xb = xa + 1 == Wt ? 0 : xa + 1, yb = ya + 1 == Ht ? 0 : ya + 1;
     const long ra = base + (long)ya * Wt, rb = base + (long)yb * Wt;
-    const unsigned p00 = m.texels[min(max(ra + xa, 0L), last)], p10 = m.texels[min(max(ra + xb, 0L), last)];    // four independent loads
-    const unsigned p01 = m.texels[min(max(rb + xa, 0L), last)], p11 = m.texels[min(max(rb + xb, 0L), last)];
+    const unsigned p00 = texels[min(max(ra + xa, 0L), last)], p10 = texels[min(max(ra + xb, 0L), last)];        // four independent loads
+    const unsigned p01 = texels[min(max(rb + xa, 0L), last)], p11 = texels[min(max(rb + xb, 0L), last)];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float t00 = mb_div((float)((p00 >> (8 * k)) & 255u), 255.f), t10 = mb_div((float)((p10 >> (8 * k)) & 255u), 255.f);
@@ -137,6 +133,18 @@ __device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u
         const float a = t00 + (t10 - t00) * fx, b = t01 + (t11 - t01) * fx;
         c[k] = a + (b - a) * fy;
     }
+}
+
+__device__ __forceinline__ bool mb_finite(float x) { return fabsf(x) < INFINITY; }
+
+// c[0..2] = texture t (0 <= t < T) at (u, v) by mb_bilinear; false, with c untouched, for a non-finite u or v.  The host validates the
+// tables (1 <= H, W <= 2^24, tex_off the running sum of H W); whatever they hold, no texel index leaves [0, tex_off[T] - 1], and a
+// texture without a texel reads as false.
+__device__ __forceinline__ bool mb_tex_sample(const MeshBatch& m, int t, float u, float v, float* c) {
+    const int Ht = m.tex_size[2 * t], Wt = m.tex_size[2 * t + 1];
+    const long last = m.tex_off[m.T] - 1;
+    if (!mb_finite(u) || !mb_finite(v) || Ht < 1 || Wt < 1 || last < 0) return false;
+    mb_bilinear(m.texels, m.tex_off[t], last, Ht, Wt, u, v, c);
     return true;
 }
 
@@ -153,31 +161,15 @@ __device__ __forceinline__ long mb_mip_level(int H0, int W0, int l, int& Hl, int
 }
 
 // mb_tex_sample's rule on level l of the pyramid of texture t (0 <= t < T; l is clamped to the texture's levels), with that level's own
-// (H_l, W_l): level 0 gives mb_tex_sample's bits.  A copy, not a shared helper, so that mb_tex_sample's code does not move.  Whatever the
-// tables hold, no texel index leaves [0, mip_off[T] - 1]; a batch without a pyramid texel reads as false.
+// (H_l, W_l): level 0 gives mb_tex_sample's bits.  Whatever the tables hold, no texel index leaves [0, mip_off[T] - 1]; a batch without a
+// pyramid texel reads as false.
 __device__ __forceinline__ bool mb_mip_sample(const MeshBatch& m, int t, int l, float u, float v, float* c) {
     const int H0 = m.tex_size[2 * t], W0 = m.tex_size[2 * t + 1];
     const long last = m.mip_off[m.T] - 1;
-    if (!(fabsf(u) < INFINITY) || !(fabsf(v) < INFINITY) || H0 < 1 || W0 < 1 || last < 0) return false;
-    int Ht, Wt;
-    const long base = m.mip_off[t] + mb_mip_level(H0, W0, min(max(l, 0), mb_mip_levels(H0, W0) - 1), Ht, Wt);
-    u = u - floorf(u);
-    v = v - floorf(v);
-    const float x = u * (float)Wt - 0.5f, y = (1.0f - v) * (float)Ht - 0.5f;
-    const float xf = floorf(x), yf = floorf(y);
-    const float fx = x - xf, fy = y - yf;
-    const int xa = mb_mod((int)fminf(xf, 2147483520.f), Wt), ya = mb_mod((int)fminf(yf, 2147483520.f), Ht);     // xf, yf >= -1
-    const int xb = xa + 1 == Wt ? 0 : xa + 1, yb = ya + 1 == Ht ? 0 : ya + 1;
-    const long ra = base + (long)ya * Wt, rb = base + (long)yb * Wt;
-    const unsigned p00 = m.mip_texels[min(max(ra + xa, 0L), last)], p10 = m.mip_texels[min(max(ra + xb, 0L), last)];
-    const unsigned p01 = m.mip_texels[min(max(rb + xa, 0L), last)], p11 = m.mip_texels[min(max(rb + xb, 0L), last)];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float t00 = mb_div((float)((p00 >> (8 * k)) & 255u), 255.f), t10 = mb_div((float)((p10 >> (8 * k)) & 255u), 255.f);
-        const float t01 = mb_div((float)((p01 >> (8 * k)) & 255u), 255.f), t11 = mb_div((float)((p11 >> (8 * k)) & 255u), 255.f);
-        const float a = t00 + (t10 - t00) * fx, b = t01 + (t11 - t01) * fx;
-        c[k] = a + (b - a) * fy;
-    }
+    if (!mb_finite(u) || !mb_finite(v) || H0 < 1 || W0 < 1 || last < 0) return false;
+    int Hl, Wl;
+    const long base = m.mip_off[t] + mb_mip_level(H0, W0, min(max(l, 0), mb_mip_levels(H0, W0) - 1), Hl, Wl);
+    mb_bilinear(m.mip_texels, base, last, Hl, Wl, u, v, c);
     return true;
 }
 

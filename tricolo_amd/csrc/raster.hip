@@ -67,11 +67,14 @@
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
-// The four-sample kernels keep that split (by their own box): a lane moves a cursor over its box's samples to ITS next covered one
-// with integer tests only - a pixel whose four samples all lie outside one edge (the largest of that edge's four offsets is still
-// negative) is stepped over whole - and only then runs the quotients and the atomic, so a wave runs that body once per covered
-// sample of its busiest lane, not once per sample of the box; the queue kernel's lanes tile the box's samples, so neighbouring lanes
-// touch neighbouring keys.
+// Every mode is that one sequence (rs_render: clear, faces, queue, resolve), its kernels templates on the keys per pixel S, 1 or 4, and
+// the resolve on the mode as well; the face set-up (rs_setup), a key (rs_pixel), (u, v, d) at a position (rs_uvd), the texel of a face
+// there (rs_texel, over mesh_batch.h's one bilinear tap) and a colour (rs_colour_u8) are each stated once for all of them.  With four
+// samples the split is by the samples' box, and the two inner walks differ on purpose: the one-sample lane visits every pixel of its
+// box; the four-sample lane moves a cursor over its box's samples to ITS next covered one with integer tests only - a pixel whose four
+// samples all lie outside one edge (the largest of that edge's four offsets is still negative) is stepped over whole - and only then
+// runs the quotients and the atomic, so a wave runs that body once per covered sample of its busiest lane, not once per sample of the
+// box.  The queue kernel's lanes tile the box's samples, so neighbouring lanes touch neighbouring keys.
 #include <math.h>
 #include <stdio.h>
 
@@ -179,12 +182,20 @@ __device__ __forceinline__ void rs_pixel(const RsFace& f, long e0, long e1, long
     if (*kp < key) atomicMax(kp, key);                                  // keys only grow: a stale read costs an atomic, never a pixel
 }
 
-__global__ __launch_bounds__(RS_THREADS) void raster_clear_kernel(u64* __restrict__ keys, long npix, u64* __restrict__ qcount) {
+// S below: the keys per pixel, 1 (the pixel centre; keys u64 [N][views][H][W]) or 4 (keys u64 [N][views][H][W][4]).  RS_LO(S), RS_HI(S): rs_setup's box.
+#define RS_LO(S) ((S) == 4 ? RS_AA_LO : 128)
+#define RS_HI(S) ((S) == 4 ? RS_AA_HI : 128)
+
+// n stores of a K and the queue count.  K: a key with one sample, two keys at once with four - 16 bytes per lane and step, which the
+// one-sample call does not take: its clear measured 4 us slower with them (profiles/r13/NOTES_one_rasteriser.md)
+template <typename K>
+__global__ __launch_bounds__(RS_THREADS) void raster_clear_kernel(K* __restrict__ keys, long n, u64* __restrict__ qcount) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *qcount = 0;
-    for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < npix; i += (long)gridDim.x * RS_THREADS) keys[i] = 0;
+    for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * RS_THREADS) keys[i] = K{};
 }
 
-// blockIdx.y = view, one lane per face of the whole batch
+// blockIdx.y = view, one lane per face of the whole batch; a lane keeps boxes of up to RS_SMALL x RS_SMALL pixels
+template <int S>
 __global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(MeshBatch m, const float* __restrict__ cam, long sumF, int views, int H, int W,
                                                                   float fx, float fy, float znear, u64* __restrict__ keys,
                                                                   u64* __restrict__ qcount, uint2* __restrict__ queue, u64 qcap) {
@@ -197,78 +208,28 @@ __global__ __launch_bounds__(RS_THREADS) void raster_faces_kernel(MeshBatch m, c
     if (gf < sumF) {
         n = mb_mesh_of(m, gf);
         nv = (long)n * views + view;
-        live = rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f);
+        live = rs_setup<RS_LO(S), RS_HI(S)>(m, cam, gf, n, nv, H, W, fx, fy, znear, f);
         big = live && (f.x1 - f.x0 >= RS_SMALL || f.y1 - f.y0 >= RS_SMALL);
     }
     const u64 slot = mb_queue_slot(big, qcount);                        // every lane of the wave is here
     if (big && slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
     if (!live || big) return;
     const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
-    u64* row = keys + ((size_t)nv * H + f.y0) * W;
+    u64* row = keys + ((size_t)nv * H + f.y0) * W * S;
     long r0 = f.e[0], r1 = f.e[1], r2 = f.e[2];
-    for (int y = f.y0; y <= f.y1; ++y, row += W, r0 += f.sy[0], r1 += f.sy[1], r2 += f.sy[2]) {
-        long e0 = r0, e1 = r1, e2 = r2;
-        for (int x = f.x0; x <= f.x1; ++x, e0 += f.sx[0], e1 += f.sx[1], e2 += f.sx[2]) rs_pixel(f, e0, e1, e2, row + x, low);
-    }
-}
-
-// fixed grid; workgroup b takes queue entries b, b + gridDim.x, ... up to the count the first kernel left on the device
-__global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, float fx,
-                                                                  float fy, float znear, u64* __restrict__ keys,
-                                                                  const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
-    const u64 count = min(*qcount, qcap);
-    for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
-        const uint2 item = queue[q];
-        const long gf = item.x;
-        const int n = mb_mesh_of(m, gf);
-        const long nv = (long)n * views + (int)item.y;
-        RsFace f;
-        if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;                      // the same answer in every lane
-        const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
-        const int bw = f.x1 - f.x0 + 1, cnt = bw * (f.y1 - f.y0 + 1);
-        u64* box = keys + ((size_t)nv * H + f.y0) * W + f.x0;
-        for (int i = threadIdx.x; i < cnt; i += RS_THREADS) {
-            const int iy = i / bw, ix = i - iy * bw;
-            rs_pixel(f, f.e[0] + (long)ix * f.sx[0] + (long)iy * f.sy[0], f.e[1] + (long)ix * f.sx[1] + (long)iy * f.sy[1],
-                     f.e[2] + (long)ix * f.sx[2] + (long)iy * f.sy[2], box + (size_t)iy * W + ix, low);
+    if (S == 1) {
+        for (int y = f.y0; y <= f.y1; ++y, row += W, r0 += f.sy[0], r1 += f.sy[1], r2 += f.sy[2]) {
+            long e0 = r0, e1 = r1, e2 = r2;
+            for (int x = f.x0; x <= f.x1; ++x, e0 += f.sx[0], e1 += f.sx[1], e2 += f.sx[2]) rs_pixel(f, e0, e1, e2, row + x, low);
         }
+        return;
     }
-}
-
-// ---- four samples per pixel: keys u64 [N][views][H][W][4] ----
-// n2 = half the number of keys: one 16-byte store per lane and step
-__global__ __launch_bounds__(RS_THREADS) void raster_clear_aa_kernel(ulonglong2* __restrict__ keys, long n2, u64* __restrict__ qcount) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *qcount = 0;
-    for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < n2; i += (long)gridDim.x * RS_THREADS) keys[i] = make_ulonglong2(0, 0);
-}
-
-// raster_faces_kernel with the samples' box; a lane keeps boxes of up to RS_SMALL x RS_SMALL PIXELS
-__global__ __launch_bounds__(RS_THREADS) void raster_faces_aa_kernel(MeshBatch m, const float* __restrict__ cam, long sumF, int views, int H, int W,
-                                                                     float fx, float fy, float znear, u64* __restrict__ keys,
-                                                                     u64* __restrict__ qcount, uint2* __restrict__ queue, u64 qcap) {
-    const long gf = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-    const int view = blockIdx.y;
-    RsFace f;
-    bool live = false, big = false;
-    int n = 0;
-    long nv = 0;
-    if (gf < sumF) {
-        n = mb_mesh_of(m, gf);
-        nv = (long)n * views + view;
-        live = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, gf, n, nv, H, W, fx, fy, znear, f);
-        big = live && (f.x1 - f.x0 >= RS_SMALL || f.y1 - f.y0 >= RS_SMALL);
-    }
-    const u64 slot = mb_queue_slot(big, qcount);                        // every lane of the wave is here
-    if (big && slot < qcap) queue[slot] = make_uint2((unsigned)gf, (unsigned)view);
-    if (!live || big) return;
-    const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
     int top[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         top[k] = max(max(rs_sample_step(f, k, 0), rs_sample_step(f, k, 1)), max(rs_sample_step(f, k, 2), rs_sample_step(f, k, 3)));
     // A cursor (y, x, s) walks the box's samples row by row; r and e are the edge functions at the centres of pixel (x0, y) and (x, y).
-    u64* row = keys + ((size_t)nv * H + f.y0) * W * 4;
-    long r0 = f.e[0], r1 = f.e[1], r2 = f.e[2], e0 = r0, e1 = r1, e2 = r2;
+    long e0 = r0, e1 = r1, e2 = r2;
     int x = f.x0, y = f.y0, s = 0;
     auto next_pixel = [&]() {
         s = 0;
@@ -293,27 +254,30 @@ __global__ __launch_bounds__(RS_THREADS) void raster_faces_aa_kernel(MeshBatch m
     }
 }
 
-// raster_queue_kernel with the samples' box; the lanes tile the box's SAMPLES (RS_THREADS is a multiple of 4: a lane keeps its sample)
-__global__ __launch_bounds__(RS_THREADS) void raster_queue_aa_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, float fx,
-                                                                     float fy, float znear, u64* __restrict__ keys,
-                                                                     const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
+// fixed grid; workgroup b takes queue entries b, b + gridDim.x, ... up to the count the first kernel left on the device.  The lanes tile
+// the box's SAMPLES (RS_THREADS is a multiple of S: a lane keeps its sample s, whose step from the pixel's centre is 0 with one sample)
+template <int S>
+__global__ __launch_bounds__(RS_THREADS) void raster_queue_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, float fx,
+                                                                  float fy, float znear, u64* __restrict__ keys,
+                                                                  const u64* __restrict__ qcount, const uint2* __restrict__ queue, u64 qcap) {
     const u64 count = min(*qcount, qcap);
-    const int s = threadIdx.x & 3;
+    const int s = threadIdx.x % S;
     for (u64 q = blockIdx.x; q < count; q += gridDim.x) {
         const uint2 item = queue[q];
         const long gf = item.x;
         const int n = mb_mesh_of(m, gf);
         const long nv = (long)n * views + (int)item.y;
         RsFace f;
-        if (!rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;                   // the same answer in every lane
+        if (!rs_setup<RS_LO(S), RS_HI(S)>(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) continue;  // the same answer in every lane
         const unsigned low = 0xFFFFFFFFu - (unsigned)(gf - m.face_off[n]);
         const int bw = f.x1 - f.x0 + 1, cnt = bw * (f.y1 - f.y0 + 1);
-        const long s0 = f.e[0] + rs_sample_step(f, 0, s), s1 = f.e[1] + rs_sample_step(f, 1, s), s2 = f.e[2] + rs_sample_step(f, 2, s);
-        u64* box = keys + (((size_t)nv * H + f.y0) * W + f.x0) * 4 + s;
-        for (int i = threadIdx.x >> 2; i < cnt; i += RS_THREADS / 4) {
+        const long s0 = f.e[0] + (S == 1 ? 0 : rs_sample_step(f, 0, s)), s1 = f.e[1] + (S == 1 ? 0 : rs_sample_step(f, 1, s)),
+                   s2 = f.e[2] + (S == 1 ? 0 : rs_sample_step(f, 2, s));
+        u64* box = keys + (((size_t)nv * H + f.y0) * W + f.x0) * S + s;
+        for (int i = threadIdx.x / S; i < cnt; i += RS_THREADS / S) {
             const int iy = i / bw, ix = i - iy * bw;
             rs_pixel(f, s0 + (long)ix * f.sx[0] + (long)iy * f.sy[0], s1 + (long)ix * f.sx[1] + (long)iy * f.sy[1],
-                     s2 + (long)ix * f.sx[2] + (long)iy * f.sy[2], box + ((size_t)iy * W + ix) * 4, low);
+                     s2 + (long)ix * f.sx[2] + (long)iy * f.sy[2], box + ((size_t)iy * W + ix) * S, low);
         }
     }
 }
@@ -333,43 +297,16 @@ __device__ __forceinline__ float rs_shade(const float* a, const float* b, const 
     return 0.1f + RS_KDIFF * ndl;
 }
 
-// The texture colour c[0..2] of face gf (texture t) at the centre of pixel (px, py): false where the face is untextured there.
-__device__ __forceinline__ bool rs_texel(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
-                                         float fy, float znear, int t, int px, int py, float* c) {
-    RsFace f;
-    if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) return false;        // the winner of a pixel was set up before: never taken
-    const float* uv = m.face_uv + (size_t)gf * 6;
-    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
-    const float u0 = uv[0], v0 = uv[1], u1 = uv[2 * i1], v1 = uv[2 * i1 + 1], u2 = uv[2 * i2], v2 = uv[2 * i2 + 1];
+// The edge functions of f at the centre of pixel (px, py); f.e holds them at the centre of pixel (x0, y0).
+__device__ __forceinline__ void rs_edges(const RsFace& f, int px, int py, long* e) {
     const long dx = px - f.x0, dy = py - f.y0;
-    const float fa = (float)(double)f.A2;
-    const float l0 = mb_div((float)(double)(f.e[0] + dx * f.sx[0] + dy * f.sy[0]), fa);
-    const float l1 = mb_div((float)(double)(f.e[1] + dx * f.sx[1] + dy * f.sy[1]), fa);
-    const float l2 = mb_div((float)(double)(f.e[2] + dx * f.sx[2] + dy * f.sy[2]), fa);
-    const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
-    const float d = (w0 + w1) + w2;
-    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
-    return mb_tex_sample(m, t, (b0 * u0 + b1 * u1) + b2 * u2, (b0 * v0 + b1 * v1) + b2 * v2, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e[k] = f.e[k] + dx * f.sx[k] + dy * f.sy[k];
 }
 
-// rs_texel's arithmetic for a face the caller has set up, where its edge functions are e0, e1, e2 (the four-sample resolve sets a face
-// up once for the samples it won; rs_texel itself stays as it is so that the one-sample kernel's code does not move).
-__device__ __forceinline__ bool rs_texel_at(const MeshBatch& m, const RsFace& f, long gf, int t, long e0, long e1, long e2, float* c) {
-    const float* uv = m.face_uv + (size_t)gf * 6;
-    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
-    const float u0 = uv[0], v0 = uv[1], u1 = uv[2 * i1], v1 = uv[2 * i1 + 1], u2 = uv[2 * i2], v2 = uv[2 * i2 + 1];
-    const float fa = (float)(double)f.A2;
-    const float l0 = mb_div((float)(double)e0, fa), l1 = mb_div((float)(double)e1, fa), l2 = mb_div((float)(double)e2, fa);
-    const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
-    const float d = (w0 + w1) + w2;
-    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
-    return mb_tex_sample(m, t, (b0 * u0 + b1 * u1) + b2 * u2, (b0 * v0 + b1 * v1) + b2 * v2, c);
-}
-
-// ---- mip-mapped textures: their own copies of rs_texel's lines, so that the kernels above keep their code ----
-// (u, v) and d of a face with corner UVs q[0..5] (the swap applied) and fa = fl32(2A), where its edge functions are e0, e1, e2
-__device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa, long e0, long e1, long e2, float& u, float& v, float& d) {
-    const float l0 = mb_div((float)(double)e0, fa), l1 = mb_div((float)(double)e1, fa), l2 = mb_div((float)(double)e2, fa);
+// THE (u, v) and d of a face with corner UVs q[0..5] (the swap applied) and fa = fl32(2A), where its edge functions are e[0..2]
+__device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa, const long* e, float& u, float& v, float& d) {
+    const float l0 = mb_div((float)(double)e[0], fa), l1 = mb_div((float)(double)e[1], fa), l2 = mb_div((float)(double)e[2], fa);
     const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
     d = (w0 + w1) + w2;
     const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
@@ -377,42 +314,46 @@ __device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa
     v = (b0 * q[1] + b1 * q[3]) + b2 * q[5];
 }
 
-__device__ __forceinline__ bool rs_finite(float x) { return fabsf(x) < INFINITY; }
+// The level of detail at a position with (u, v), d, from (ux, vx), dx one whole pixel to the right and (uy, vy), dy one whole pixel down
+// (head of this file), for a texture of size (H0, W0): the level to sample; true when level lo + 1 is blended in by frac.
+__device__ __forceinline__ bool rs_mip_lod(int H0, int W0, float u, float v, float ux, float vx, float dx, float uy, float vy, float dy, int& lo,
+                                           float& frac) {
+    const float a = (ux - u) * (float)W0, b = (vx - v) * (float)H0, g = (uy - u) * (float)W0, e = (vy - v) * (float)H0;
+    const float r2 = fmaxf(a * a + b * b, g * g + e * e);
+    const int top = mb_mip_levels(H0, W0) - 1;
+    lo = top;                                                           // the footprint is unbounded: the coarsest level alone
+    frac = 0.f;
+    if (!(dx > 0.f && dy > 0.f && mb_finite(ux) && mb_finite(vx) && mb_finite(uy) && mb_finite(vy) && mb_finite(r2))) return false;
+    const float rho = mb_sqrt(r2);
+    if (rho <= 1.0f) { lo = 0; return false; }                          // magnified: the texture itself
+    const unsigned bits = __float_as_uint(rho);                         // rho > 1 and finite: a normal number
+    const int l = (int)(bits >> 23) - 127;
+    if (l >= top) return false;
+    lo = l;
+    frac = __uint_as_float((bits & 0x007FFFFFu) | 0x3F800000u) - 1.0f;
+    return true;
+}
 
-// The mip-mapped texture colour c[0..2] of face gf (texture t, set up as f) where its edge functions are e0, e1, e2: the level of
-// detail from (u, v) there, one whole pixel to the right and one whole pixel down (head of this file); false where the face is
-// untextured there.
-__device__ __forceinline__ bool rs_texel_mip_at(const MeshBatch& m, const RsFace& f, long gf, int t, long e0, long e1, long e2, float* c) {
+// The texture colour c[0..2] of face gf (texture t), set up by the caller as f, where its edge functions are e[0..2]: false where the
+// face is untextured there.  MIP: from the pyramid, the level of detail from (u, v) there, one whole pixel to the right and one down.
+template <bool MIP>
+__device__ __forceinline__ bool rs_texel(const MeshBatch& m, const RsFace& f, long gf, int t, const long* e, float* c) {
     const float* uv = m.face_uv + (size_t)gf * 6;
     const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
     const float q[6] = {uv[0], uv[1], uv[2 * i1], uv[2 * i1 + 1], uv[2 * i2], uv[2 * i2 + 1]};
     const float fa = (float)(double)f.A2;
-    float u, v, d, ux, vx, dx, uy, vy, dy;
-    rs_uvd(f, q, fa, e0, e1, e2, u, v, d);
-    if (!rs_finite(u) || !rs_finite(v)) return false;
+    float u, v, d;
+    rs_uvd(f, q, fa, e, u, v, d);
+    if (!MIP) return mb_tex_sample(m, t, u, v, c);
+    if (!mb_finite(u) || !mb_finite(v)) return false;
     const int H0 = m.tex_size[2 * t], W0 = m.tex_size[2 * t + 1];
     if (H0 < 1 || W0 < 1) return false;
-    rs_uvd(f, q, fa, e0 + f.sx[0], e1 + f.sx[1], e2 + f.sx[2], ux, vx, dx);
-    rs_uvd(f, q, fa, e0 + f.sy[0], e1 + f.sy[1], e2 + f.sy[2], uy, vy, dy);
-    const float a = (ux - u) * (float)W0, b = (vx - v) * (float)H0, g = (uy - u) * (float)W0, e = (vy - v) * (float)H0;
-    const float r2 = fmaxf(a * a + b * b, g * g + e * e);
-    const int top = mb_mip_levels(H0, W0) - 1;
-    int lo = top;                                                       // the footprint is unbounded: the coarsest level alone
-    float frac = 0.f;
-    bool two = false;
-    if (dx > 0.f && dy > 0.f && rs_finite(ux) && rs_finite(vx) && rs_finite(uy) && rs_finite(vy) && rs_finite(r2)) {
-        const float rho = mb_sqrt(r2);
-        if (rho <= 1.0f) lo = 0;                                        // magnified: the texture itself
-        else {
-            const unsigned bits = __float_as_uint(rho);                 // rho > 1 and finite: a normal number
-            const int l = (int)(bits >> 23) - 127;
-            if (l < top) {
-                lo = l;
-                frac = __uint_as_float((bits & 0x007FFFFFu) | 0x3F800000u) - 1.0f;
-                two = true;
-            }
-        }
-    }
+    const long ex[3] = {e[0] + f.sx[0], e[1] + f.sx[1], e[2] + f.sx[2]}, ey[3] = {e[0] + f.sy[0], e[1] + f.sy[1], e[2] + f.sy[2]};
+    float ux, vx, dx, uy, vy, dy, frac;
+    rs_uvd(f, q, fa, ex, ux, vx, dx);
+    rs_uvd(f, q, fa, ey, uy, vy, dy);
+    int lo;
+    const bool two = rs_mip_lod(H0, W0, u, v, ux, vx, dx, uy, vy, dy, lo, frac);
     if (!mb_mip_sample(m, t, lo, u, v, c)) return false;
     if (two) {
         float h[3];
@@ -423,20 +364,18 @@ __device__ __forceinline__ bool rs_texel_mip_at(const MeshBatch& m, const RsFace
     return true;
 }
 
-// rs_texel with the pyramid: the winner of pixel (px, py) set up again, its edge functions at the pixel's centre
-__device__ __forceinline__ bool rs_texel_mip(const MeshBatch& m, const float* __restrict__ cam, long gf, int n, long nv, int H, int W, float fx,
-                                             float fy, float znear, int t, int px, int py, float* c) {
-    RsFace f;
-    if (!rs_setup(m, cam, gf, n, nv, H, W, fx, fy, znear, f)) return false;        // the winner of a pixel was set up before: never taken
-    const long dx = px - f.x0, dy = py - f.y0;
-    return rs_texel_mip_at(m, f, gf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0], f.e[1] + dx * f.sx[1] + dy * f.sy[1],
-                           f.e[2] + dx * f.sx[2] + dy * f.sy[2], c);
+// c = u8 of clamp(kd s, 0, 1), the colour of a pixel or of a sample
+__device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* c) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
+        c[k] = (int)(uint8_t)(int)floorf(255.f * col + 0.5f);
+    }
 }
 
 // one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn.  TEX: the textured resolve pass - the
-// lanes of a wave whose face has a texture run rs_texel together, the others wait for them and keep their Kd.  MIP: rs_texel_mip in
-// its place.
-template <bool TEX, bool MIP = false>
+// lanes of a wave whose face has a texture set it up again and run rs_texel together, the others wait for them and keep their Kd.
+template <bool TEX, bool MIP>
 __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx, float fy,
                                            float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image, int* __restrict__ visibility) {
     const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -460,51 +399,27 @@ __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __re
     mb_face_kd(m, n, f0 + lf, kd);
     if (TEX) {
         const int t = mb_face_tex(m, n, f0 + lf);
-        float c[3];
-        if (t >= 0 && (MIP ? rs_texel_mip(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c)
-                           : rs_texel(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, t, pix % W, pix / W, c))) {
+        RsFace f;
+        if (t >= 0 && rs_setup(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f)) {    // the winner of a pixel was set up before: true
+            long e[3];
+            float c[3];
+            rs_edges(f, pix % W, pix / W, e);
+            if (rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) kd[k] = kd[k] * c[k];
+                for (int k = 0; k < 3; ++k) kd[k] = kd[k] * c[k];
+            }
         }
     }
+    int col[3];
+    rs_colour_u8(kd, shade, col);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
-        out[(size_t)k * HW] = (uint8_t)(int)floorf(255.f * col + 0.5f);
-    }
-}
-
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, long npix,
-                                                                    const u64* __restrict__ keys, uint8_t* __restrict__ image,
-                                                                    int* __restrict__ visibility) {
-    rs_resolve<false>(m, cam, views, H, W, npix, 0.f, 0.f, 0.f, keys, image, visibility);
-}
-
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_tex_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
-                                                                        long npix, float fx, float fy, float znear, const u64* __restrict__ keys,
-                                                                        uint8_t* __restrict__ image, int* __restrict__ visibility) {
-    rs_resolve<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
-}
-
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_mip_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
-                                                                        long npix, float fx, float fy, float znear, const u64* __restrict__ keys,
-                                                                        uint8_t* __restrict__ image, int* __restrict__ visibility) {
-    rs_resolve<true, true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
-}
-
-// u8 of clamp(kd s, 0, 1), the colour rs_resolve writes
-__device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* c) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float col = fminf(fmaxf(kd[k] * shade, 0.f), 1.f);
-        c[k] = (int)(uint8_t)(int)floorf(255.f * col + 0.5f);
-    }
+    for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)col[k];
 }
 
 // one thread per pixel of the four-sample key buffer: every sample is coloured as rs_resolve colours a pixel - a textured face from (u, v)
 // at the sample's own position - and the pixel is the rounded integer mean.  A face met in the sample before is not shaded or set up
-// again, and an untextured one keeps its colour.  MIP: rs_texel_mip_at in rs_texel_at's place.
-template <bool TEX, bool MIP = false>
+// again, and an untextured one keeps its colour.
+template <bool TEX, bool MIP>
 __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx,
                                               float fy, float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image,
                                               int* __restrict__ visibility) {
@@ -516,9 +431,8 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
     const ulonglong2* kp = (const ulonglong2*)(keys + 4 * (size_t)i);               // the workspace is 16-byte aligned
     const ulonglong2 ka = kp[0], kb = kp[1];
     const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
-    const int px = pix % W, py = pix / W;
     int sum[3] = {2, 2, 2}, col[3] = {255, 255, 255}, t = -1;
-    long prev = -1;
+    long prev = -1, centre[3] = {0, 0, 0};
     float shade = 0.f, kd[3] = {0.f, 0.f, 0.f};
     bool set = false;
     RsFace f;
@@ -540,19 +454,17 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
             mb_face_kd(m, n, f0 + lf, kd);
             if (TEX) {
                 t = mb_face_tex(m, n, f0 + lf);
-                if (t >= 0) set = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f);    // the winner: true
+                if (t >= 0) {
+                    set = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f);     // the winner: true
+                    rs_edges(f, pix % W, pix / W, centre);
+                }
             }
             if (!TEX || t < 0) rs_colour_u8(kd, shade, col);
         }
         if (TEX && t >= 0) {
             float c[3], kc[3] = {kd[0], kd[1], kd[2]};
-            const long dx = px - f.x0, dy = py - f.y0;
-            if (MIP ? set && rs_texel_mip_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
-                                             f.e[1] + dx * f.sx[1] + dy * f.sy[1] + rs_sample_step(f, 1, s),
-                                             f.e[2] + dx * f.sx[2] + dy * f.sy[2] + rs_sample_step(f, 2, s), c)
-                    : set && rs_texel_at(m, f, f0 + lf, t, f.e[0] + dx * f.sx[0] + dy * f.sy[0] + rs_sample_step(f, 0, s),
-                                   f.e[1] + dx * f.sx[1] + dy * f.sy[1] + rs_sample_step(f, 1, s),
-                                   f.e[2] + dx * f.sx[2] + dy * f.sy[2] + rs_sample_step(f, 2, s), c)) {
+            const long e[3] = {centre[0] + rs_sample_step(f, 0, s), centre[1] + rs_sample_step(f, 1, s), centre[2] + rs_sample_step(f, 2, s)};
+            if (set && rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) kc[k] = kd[k] * c[k];
             }
@@ -566,24 +478,13 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
     for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)(sum[k] >> 2);
 }
 
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
-                                                                       long npix, const u64* __restrict__ keys, uint8_t* __restrict__ image,
-                                                                       int* __restrict__ visibility) {
-    rs_resolve_aa<false>(m, cam, views, H, W, npix, 0.f, 0.f, 0.f, keys, image, visibility);
-}
-
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_tex_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
-                                                                           long npix, float fx, float fy, float znear,
-                                                                           const u64* __restrict__ keys, uint8_t* __restrict__ image,
-                                                                           int* __restrict__ visibility) {
-    rs_resolve_aa<true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
-}
-
-__global__ __launch_bounds__(RS_THREADS) void raster_resolve_aa_mip_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W,
-                                                                           long npix, float fx, float fy, float znear,
-                                                                           const u64* __restrict__ keys, uint8_t* __restrict__ image,
-                                                                           int* __restrict__ visibility) {
-    rs_resolve_aa<true, true>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+// the resolve kernel of S keys per pixel; TEX, MIP: the mode of the call
+template <int S, bool TEX, bool MIP>
+__global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, long npix,
+                                                                    float fx, float fy, float znear, const u64* __restrict__ keys,
+                                                                    uint8_t* __restrict__ image, int* __restrict__ visibility) {
+    if (S == 4) rs_resolve_aa<TEX, MIP>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+    else rs_resolve<TEX, MIP>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
 // one lane per face of the whole batch: out fp32 [sumF][3], the colour the voxeliser takes for the face
@@ -698,18 +599,16 @@ static bool rs_sizes_ok(long sumF, int N, int views, int H, int W) {
     return N >= 0 && sumF >= 0 && views >= 0 && H >= 0 && W >= 0;
 }
 
-extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W) {
-    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W >= (double)RS_MAX_PIXELS) return 0;
-    const size_t npix = (size_t)N * views * H * W;
-    return npix * 8 + 16 + (size_t)sumF * views * 8;                    // keys | queue count (padded to 16 bytes) | queue
+// keys (samples per pixel) | queue count (padded to 16 bytes) | queue; 0 for what rs_check refuses by its sizes
+static size_t rs_workspace(long sumF, int N, int views, int H, int W, int samples) {
+    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W * (double)samples >= (double)RS_MAX_PIXELS) return 0;
+    return (size_t)N * views * H * W * samples * 8 + 16 + (size_t)sumF * views * 8;
 }
 
+extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W) { return rs_workspace(sumF, N, views, H, W, 1); }
+
 // the four-sample query: four keys per pixel, so fewer than 2^31 SAMPLES
-extern "C" size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W) {
-    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W * 4.0 >= (double)RS_MAX_PIXELS) return 0;
-    const size_t npix = (size_t)N * views * H * W;
-    return npix * 32 + 16 + (size_t)sumF * views * 8;                   // keys | queue count (padded to 16 bytes) | queue
-}
+extern "C" size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W) { return rs_workspace(sumF, N, views, H, W, 4); }
 
 // What every launch refuses before anything runs; samples: keys per pixel, 1 or 4.
 static int rs_check(int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, const char* who) {
@@ -730,32 +629,55 @@ static int rs_check(int N, long sumF, int views, int H, int W, double yfov, doub
     return TRI_OK;
 }
 
+// The texture arguments of entry point `who`: T and, for T > 0, the five texture fields (given: all of them are there); pyramid: the
+// two pyramid fields are among them.
+static int rs_check_textures(const char* who, int T, bool given, bool pyramid) {
+    char msg[200];
+    if (T < 0) { snprintf(msg, sizeof msg, "%s: negative size", who); tri_set_error(msg); return TRI_ERR_ARG; }
+    if (T > 0 && !given) {
+        snprintf(msg, sizeof msg, "%s: T > 0 needs all five texture fields%s", who, pyramid ? " and both pyramid fields" : "");
+        tri_set_error(msg);
+        return TRI_ERR_ARG;
+    }
+    return TRI_OK;
+}
+
 enum { RS_PLAIN = 0, RS_TEX = 1, RS_MIP = 2 };   // which resolve kernel colours the pixels
 
-static int rs_render(const MeshBatch& m, int tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+typedef void (*RsResolve)(MeshBatch, const float*, int, int, int, long, float, float, float, const u64*, uint8_t*, int*);
+
+// THE launch sequence: clear, faces, queue, resolve, with `samples` keys per pixel (1 or 4).  A batch without textures (T == 0) takes
+// the plain resolve whatever the mode: mb_face_tex finds no texture in it.
+static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
                      void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
+    static const RsResolve resolve[2][3] = {
+        {raster_resolve_kernel<1, false, false>, raster_resolve_kernel<1, true, false>, raster_resolve_kernel<1, true, true>},
+        {raster_resolve_kernel<4, false, false>, raster_resolve_kernel<4, true, false>, raster_resolve_kernel<4, true, true>}};
     const int N = m.N;
-    const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 1, who);
+    const int bad = rs_check(N, sumF, views, H, W, yfov, znear, samples, who);
     if (bad != TRI_OK) return bad;
-    const long npix = (long)N * views * H * W;
+    const long npix = (long)N * views * H * W, nkeys = npix * samples;
     if (npix == 0) return TRI_OK;
+    const bool aa = samples == 4;
     hipStream_t st = (hipStream_t)stream;
     u64* keys = (u64*)workspace;
-    u64* qcount = keys + npix;
+    u64* qcount = keys + nkeys;
     uint2* queue = (uint2*)(qcount + 2);
     const u64 qcap = (u64)sumF * views;
     const double fyd = 1.0 / tan(yfov / 2.0);
     const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
-    raster_clear_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(keys, npix, qcount);
+    const long stores = aa ? nkeys / 2 : nkeys;
+    const unsigned clear = (unsigned)min((long)RS_CLEAR_BLOCKS, (stores + RS_THREADS - 1) / RS_THREADS);
+    if (aa) raster_clear_kernel<<<clear, RS_THREADS, 0, st>>>((ulonglong2*)keys, stores, qcount);      // the workspace is 16-byte aligned
+    else raster_clear_kernel<<<clear, RS_THREADS, 0, st>>>(keys, stores, qcount);
     if (sumF > 0) {
-        raster_faces_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
-            m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
-        raster_queue_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+        (aa ? raster_faces_kernel<4> : raster_faces_kernel<1>)<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views),
+                                                                 RS_THREADS, 0, st>>>(m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
+        (aa ? raster_queue_kernel<4> : raster_queue_kernel<1>)<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount,
+                                                                                                       queue, qcap);
     }
-    const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
-    if (tex == RS_MIP) raster_resolve_mip_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
-    else if (tex == RS_TEX) raster_resolve_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
-    else raster_resolve_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
+    resolve[aa][m.T > 0 ? mode : RS_PLAIN]<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy,
+                                                                                                                    zn, keys, image, visibility);
     return tri_check_launch(who);
 }
 
@@ -763,62 +685,34 @@ extern "C" int tri_raster_render(const float* verts, const int* faces, const lon
                                  const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
                                  double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
-    return rs_render(m, RS_PLAIN, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
+    return rs_render(m, RS_PLAIN, 1, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
+}
+
+// the one-sample and the four-sample textured launches share their arguments
+static int rs_render_tex(const char* who, int samples, const float* verts, const int* faces, const long* vert_off, const long* face_off,
+                         const int* face_mat, const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex,
+                         const uint8_t* texels, const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
+                         int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, false);
+    if (bad != TRI_OK) return bad;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    return rs_render(m, RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 
 extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
                                      const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
                                      const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
                                      int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    if (T < 0) { tri_set_error("tri_raster_render_tex: negative size"); return TRI_ERR_ARG; }
-    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
-        tri_set_error("tri_raster_render_tex: T > 0 needs all five texture fields");
-        return TRI_ERR_ARG;
-    }
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
-    return rs_render(m, RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_tex");
-}
-
-// the four-sample launches; tex: RS_TEX or RS_MIP, and a batch without textures (T == 0) takes the plain resolve either way
-static int rs_render_aa(const MeshBatch& m, int tex, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
-                        void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
-    const int N = m.N;
-    const int bad = rs_check(N, sumF, views, H, W, yfov, znear, 4, who);
-    if (bad != TRI_OK) return bad;
-    const long npix = (long)N * views * H * W;
-    if (npix == 0) return TRI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    u64* keys = (u64*)workspace;
-    u64* qcount = keys + 4 * npix;
-    uint2* queue = (uint2*)(qcount + 2);
-    const u64 qcap = (u64)sumF * views;
-    const double fyd = 1.0 / tan(yfov / 2.0);
-    const float fy = (float)fyd, fx = (float)(fyd * (double)H / (double)W), zn = (float)znear;
-    raster_clear_aa_kernel<<<(unsigned)min((long)RS_CLEAR_BLOCKS, (2 * npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(
-        (ulonglong2*)keys, 2 * npix, qcount);
-    if (sumF > 0) {
-        raster_faces_aa_kernel<<<dim3((unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), (unsigned)views), RS_THREADS, 0, st>>>(
-            m, cam, sumF, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
-        raster_queue_aa_kernel<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount, queue, qcap);
-    }
-    const unsigned blocks = (unsigned)((npix + RS_THREADS - 1) / RS_THREADS);
-    if (m.T > 0 && tex == RS_MIP) raster_resolve_aa_mip_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
-    else if (m.T > 0) raster_resolve_aa_tex_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy, zn, keys, image, visibility);
-    else raster_resolve_aa_kernel<<<blocks, RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, keys, image, visibility);
-    return tri_check_launch(who);
+    return rs_render_tex("tri_raster_render_tex", 1, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off,
+                         tex_size, T, cam, N, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream);
 }
 
 extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
                                     const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
                                     int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    if (T < 0) { tri_set_error("tri_raster_render_aa: negative size"); return TRI_ERR_ARG; }
-    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
-        tri_set_error("tri_raster_render_aa: T > 0 needs all five texture fields");
-        return TRI_ERR_ARG;
-    }
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
-    return rs_render_aa(m, RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render_aa");
+    return rs_render_tex("tri_raster_render_aa", 4, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off,
+                         tex_size, T, cam, N, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream);
 }
 
 extern "C" int tri_texture_mips(const uint8_t* texels, const long* tex_off, const int* tex_size, int T, long sum_texels, const long* mip_off,
@@ -842,16 +736,12 @@ extern "C" int tri_raster_render_mip(const float* verts, const int* faces, const
                                      const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear, int samples,
                                      void* workspace, uint8_t* image, int* visibility, void* stream) {
     const char* who = "tri_raster_render_mip";
-    if (T < 0) { tri_set_error("tri_raster_render_mip: negative size"); return TRI_ERR_ARG; }
-    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_mip: samples must be 1 or 4"); return TRI_ERR_ARG; }
-    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size || !mip_texels || !mip_off)) {
-        tri_set_error("tri_raster_render_mip: T > 0 needs all five texture fields and both pyramid fields");
-        return TRI_ERR_ARG;
-    }
+    if (T >= 0 && samples != 1 && samples != 4) { tri_set_error("tri_raster_render_mip: samples must be 1 or 4"); return TRI_ERR_ARG; }
+    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size && mip_texels && mip_off, true);
+    if (bad != TRI_OK) return bad;
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
                       (const unsigned*)mip_texels, mip_off};
-    if (samples == 4) return rs_render_aa(m, RS_MIP, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
-    return rs_render(m, T > 0 ? RS_MIP : RS_TEX, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
+    return rs_render(m, RS_MIP, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 
 extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
@@ -859,10 +749,8 @@ extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const
                                      const long* tex_off, const int* tex_size, int T, int N, long sumF, float* colours, void* stream) {
     if (N < 0 || sumF < 0 || T < 0) { tri_set_error("tri_mesh_face_colours: negative size"); return TRI_ERR_ARG; }
     if (sumF >= (1L << 31)) { tri_set_error("tri_mesh_face_colours: 2^31 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
-    if (T > 0 && (!face_uv || !mat_tex || !texels || !tex_off || !tex_size)) {
-        tri_set_error("tri_mesh_face_colours: T > 0 needs all five texture fields");
-        return TRI_ERR_ARG;
-    }
+    const int bad = rs_check_textures("tri_mesh_face_colours", T, face_uv && mat_tex && texels && tex_off && tex_size, false);
+    if (bad != TRI_OK) return bad;
     if (sumF == 0 || N == 0) return TRI_OK;
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
     mesh_face_colours_kernel<<<(unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, (hipStream_t)stream>>>(m, sumF, colours);

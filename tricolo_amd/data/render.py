@@ -267,7 +267,7 @@ def texture_mips_cpu(texels, tex_off, tex_size):
 
 
 def sample_mips(t, u, v, right, down, mip_texels, mip_off, tex_size):
-    """The level of detail and the blend of two pyramid levels (head of csrc/raster.hip, rs_texel_mip_at): textures t int64 [P] at
+    """The level of detail and the blend of two pyramid levels (head of csrc/raster.hip, rs_texel<true>): textures t int64 [P] at
     u, v fp32 [P]; right, down: (u, v, d) of the same face one whole pixel to the right and one whole pixel down -> (ok, c) as
     sample_textures."""
     (ux, vx, dx), (uy, vy, dy) = right, down

@@ -1686,30 +1686,39 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
 RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
 
 
-def _render_views_aa(stage, N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, textures, cam, H, W, yfov, znear, return_visibility,
-                     mips=None):
-    """The samples=4 path of render_views and render_views_textured, their arguments already checked (textures: the five texture
-    tensors, or None and T == 0 for a batch without them; mips: the checked pyramid pair, or None): tri_raster_render_aa or, with
-    mips, tri_raster_render_mip; on CPU tensors render_views_cpu(samples=4)."""
-    views, sumF = cam.shape[1], faces.shape[0]
-    if N * views * H * W * 4 >= RENDER_MAX_PIXELS or views > 65535:
-        raise ValueError(f"{stage}: {N} meshes x {views} views x {H} x {W} pixels x 4 samples need a visibility buffer of "
-                         f"{N * views * H * W * 32} bytes; one call takes fewer than 2^31 samples and at most 65535 views - split the batch")
-    if not verts.is_cuda:
+def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples):
+    """The body of render_views and render_views_textured, whose own arguments are checked (batch: the seven tensors of the packed
+    batch; textures: its five texture tensors, or None; mips: the checked pyramid pair, or None): the camera, the limits, then the one
+    entry point of csrc/raster.hip for the mode, or data.render.render_views_cpu on CPU tensors."""
+    if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
+        raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
+    views, sumF, dev = cam.shape[1], batch[1].shape[0], batch[0].device
+    if H < 0 or W < 0 or not (0.0 < float(yfov) < math.pi) or not float(znear) > 0.0:
+        raise ValueError(f"{stage}: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
+    if sumF >= 2 ** 31:
+        raise ValueError(f"{stage}: 2^31 or more faces in one batch")
+    if N * views * H * W * samples >= RENDER_MAX_PIXELS or views > 65535:
+        what, unit = ("pixels x 4 samples", "samples") if samples == 4 else ("pixels", "pixels")
+        raise ValueError(f"{stage}: {N} meshes x {views} views x {H} x {W} {what} need a visibility buffer of "
+                         f"{N * views * H * W * samples * 8} bytes; one call takes fewer than 2^31 {unit} and at most 65535 views - split the batch")
+    if not batch[0].is_cuda:
         from .data.render import render_views_cpu
-        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
-                                textures=textures, samples=4, mips=mips)
-    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
-    vis = torch.empty((N, views, H, W, 4), dtype=torch.int32, device=verts.device) if return_visibility else None
-    ws = torch.empty((max(16, lib().tri_raster_workspace_aa(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
+        return render_views_cpu(*batch, cam, H, W, yfov, znear, return_visibility, textures=textures, samples=samples, mips=mips)
+    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=dev)
+    vis = torch.empty((N, views, H, W) + ((4,) if samples == 4 else ()), dtype=torch.int32, device=dev) if return_visibility else None
+    size = (lib().tri_raster_workspace_aa if samples == 4 else lib().tri_raster_workspace)(sumF, N, views, H, W)
+    ws = torch.empty((max(16, size),), dtype=torch.uint8, device=dev)
+    mesh = [ptr(x) for x in batch]
+    tex = [ptr(x) for x in (textures or (None,) * 5)] + [textures[4].shape[0] if textures else 0]
+    view = [ptr(cam), N, sumF, views, H, W, float(yfov), float(znear)]
+    out = [ptr(ws), ptr(image), ptr(vis), stream()]
     if mips is not None:
-        check(lib().tri_raster_render_mip(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
-                                          *(ptr(x) for x in textures), T, ptr(mips[0]), ptr(mips[1]), ptr(cam), N, sumF, views, H, W,
-                                          float(yfov), float(znear), 4, ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_mip")
-        return (image, vis) if return_visibility else image
-    check(lib().tri_raster_render_aa(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
-                                     *(ptr(x) for x in (textures or (None,) * 5)), T, ptr(cam), N, sumF, views, H, W, float(yfov),
-                                     float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_aa")
+        name, args = "tri_raster_render_mip", mesh + tex + [ptr(mips[0]), ptr(mips[1])] + view + [samples] + out
+    elif samples == 4 or textures is not None:
+        name, args = "tri_raster_render_aa" if samples == 4 else "tri_raster_render_tex", mesh + tex + view + out
+    else:
+        name, args = "tri_raster_render", mesh + view + out
+    check(getattr(lib(), name)(*args), name)
     return (image, vis) if return_visibility else image
 
 
@@ -1737,29 +1746,8 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     H, W = int(H), int(W)
     samples = _render_samples("render_views", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views")
-    if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
-        raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
-    views, sumF = cam.shape[1], faces.shape[0]
-    if H < 0 or W < 0 or not (0.0 < float(yfov) < math.pi) or not float(znear) > 0.0:
-        raise ValueError("render_views: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
-    if sumF >= 2 ** 31:
-        raise ValueError("render_views: 2^31 or more faces in one batch")
-    if samples == 4:
-        return _render_views_aa("render_views", N, 0, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, None, cam, H, W, yfov, znear,
-                                return_visibility)
-    if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
-        raise ValueError(f"render_views: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
-                         f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
-    if not verts.is_cuda:
-        from .data.render import render_views_cpu
-        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility)
-    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
-    vis = torch.empty((N, views, H, W), dtype=torch.int32, device=verts.device) if return_visibility else None
-    ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
-    check(lib().tri_raster_render(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off), ptr(cam),
-                                  N, sumF, views, H, W, float(yfov), float(znear), ptr(ws), ptr(image), ptr(vis), stream()),
-          "tri_raster_render")
-    return (image, vis) if return_visibility else image
+    return _render("render_views", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off), None, None, cam, H, W, yfov, znear,
+                   return_visibility, samples)
 
 
 def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size):
@@ -1851,39 +1839,11 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
     H, W = int(H), int(W)
     samples = _render_samples("render_views_textured", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
-    T = _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
+    _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
     if mips is not None:
         mips = _mesh_mips("render_views_textured", texels, tex_size, mips)
-    if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
-        raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
-    views, sumF = cam.shape[1], faces.shape[0]
-    if H < 0 or W < 0 or not (0.0 < float(yfov) < math.pi) or not float(znear) > 0.0:
-        raise ValueError("render_views_textured: H and W must not be negative, yfov must lie in (0, pi), znear above 0")
-    if sumF >= 2 ** 31:
-        raise ValueError("render_views_textured: 2^31 or more faces in one batch")
-    if samples == 4:
-        return _render_views_aa("render_views_textured", N, T, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off,
-                                (face_uv, mat_tex, texels, tex_off, tex_size), cam, H, W, yfov, znear, return_visibility, mips)
-    if N * views * H * W >= RENDER_MAX_PIXELS or views > 65535:
-        raise ValueError(f"render_views_textured: {N} meshes x {views} views x {H} x {W} pixels need a visibility buffer of "
-                         f"{N * views * H * W * 8} bytes; one call takes fewer than 2^31 pixels and at most 65535 views - split the batch")
-    if not verts.is_cuda:
-        from .data.render import render_views_cpu
-        return render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov, znear, return_visibility,
-                                textures=(face_uv, mat_tex, texels, tex_off, tex_size), mips=mips)
-    image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=verts.device)
-    vis = torch.empty((N, views, H, W), dtype=torch.int32, device=verts.device) if return_visibility else None
-    ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W)),), dtype=torch.uint8, device=verts.device)
-    if mips is not None:
-        check(lib().tri_raster_render_mip(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
-                                          ptr(face_uv), ptr(mat_tex), ptr(texels), ptr(tex_off), ptr(tex_size), T, ptr(mips[0]), ptr(mips[1]),
-                                          ptr(cam), N, sumF, views, H, W, float(yfov), float(znear), 1, ptr(ws), ptr(image), ptr(vis), stream()),
-              "tri_raster_render_mip")
-        return (image, vis) if return_visibility else image
-    check(lib().tri_raster_render_tex(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off),
-                                      ptr(face_uv), ptr(mat_tex), ptr(texels), ptr(tex_off), ptr(tex_size), T, ptr(cam), N, sumF, views, H, W,
-                                      float(yfov), float(znear), ptr(ws), ptr(image), ptr(vis), stream()), "tri_raster_render_tex")
-    return (image, vis) if return_visibility else image
+    return _render("render_views_textured", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off),
+                   (face_uv, mat_tex, texels, tex_off, tex_size), mips, cam, H, W, yfov, znear, return_visibility, samples)
 
 
 def mesh_face_colours(batch):
