@@ -572,6 +572,34 @@ int tri_raster_render_mip(const float* verts, const int* faces, const long* vert
                           int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, void* workspace,
                           uint8_t* image, int* visibility, void* stream);
 
+/* Smooth shading: any of the six modes above with the batch's corner normals face_vn fp32 [sumF][3][3] (csrc/mesh_batch.h: one normal
+ * per face corner in the order of `faces`, not necessarily of unit length; a NaN in face_vn[f][0][0] marks a face without normals,
+ * which is shaded flat exactly as before).  The mode follows from the arguments: the five texture fields may be null with T == 0 (no
+ * face is textured), the two pyramid fields may be null (no mip-mapping; they come together or not at all), samples is 1 or 4.
+ * Visibility is tri_raster_render's (tri_raster_render_aa's with four samples), bit for bit: only the resolve pass differs.  At the
+ * pixel centre - with four samples at each sample's own position - the normal is interpolated with the perspective-correct weights
+ * of the textured modes, turned toward the eye by the sign of its dot product with eye - vertex 0, and lit as the flat one is:
+ * Kd (0.1 + 3 / pi max(n_y / |n|, 0)); where the interpolated normal is not finite or has no length the position takes the flat
+ * shade.  The arithmetic is spelled out at the head of csrc/raster.hip.  workspace: tri_raster_workspace(...) bytes for samples == 1,
+ * tri_raster_workspace_aa(...) for samples == 4; the same limits.  A null face_vn is TRI_ERR_ARG. */
+int tri_raster_render_smooth(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                             const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                             const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
+                             const float* face_vn, const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear,
+                             int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
+
+/* Vertex normals of a packed batch, written as corner normals face_vn_out fp32 [sumF][3][3] for tri_raster_render_smooth.  A
+ * definition of this project (head of csrc/mesh_normals.hip): area-weighted - the fp32 cross product of every face, clamped to
+ * +-2^16 per component and rounded to fixed point with 36 fractional bits, is summed per VERTEX INDEX of its mesh with 64-bit integer
+ * atomics, so the result does not depend on the order of the faces and is bit-reproducible - then normalised in float64 and rounded
+ * to fp32.  fill 0: a face whose face_vn_in[f][0][0] is not NaN keeps its nine incoming values bit for bit and only the others are
+ * computed (face_vn_in may be null: all are computed); fill 1: every face is computed.  A face with a corner whose sum is (0, 0, 0) is
+ * written as nine NaNs.  workspace: tri_mesh_vertex_normals_workspace(sumV) bytes of device memory (24 per vertex), 8-byte aligned.
+ * Three launches on the stream, no host synchronisation.  Fewer than 2^31 faces and vertices. */
+size_t tri_mesh_vertex_normals_workspace(long sumV);
+int tri_mesh_vertex_normals(const float* verts, const int* faces, const long* vert_off, const long* face_off, int N, long sumV, long sumF,
+                            int fill, void* workspace, const float* face_vn_in, float* face_vn_out, void* stream);
+
 /* One colour per face for the voxeliser: colours fp32 [sumF][3] = Kd for an untextured face, else Kd times the mean of four bilinear
  * samples of its texture, at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of the face's UVs (used
  * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped. */

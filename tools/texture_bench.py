@@ -5,9 +5,10 @@ views at 224 x 224 - and ops.mesh_face_colours on the same batch.  Two of the th
 [-2, 3]: textured and untextured pixels meet in the same waves.  HIP events, warmed; the two renderers alternate window by window in
 one process, and every window is reported, so the spread is on the page.  One JSON line per size.  --mip adds the mip-mapped call
 (ops.render_views_textured(..., mips=), with --samples 1 4 in both sample counts) and ops.texture_mips, the pyramid build for the
-batch's 256 x 256 textures, to the alternation.
+batch's 256 x 256 textures, to the alternation.  --normals adds the smooth-shaded calls (normals= of both renderers, the batch's
+computed vertex normals, in every sample count asked for) and ops.mesh_vertex_normals itself.
 
-    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--mip] [--trace-only RINGS]
+    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--mip] [--normals] [--trace-only RINGS]
     (--trace-only: three warmed calls of each for rocprofv3 --kernel-trace --stats, which gives the resolve kernels' own times)
 """
 import argparse
@@ -58,6 +59,8 @@ def main():
                     "1 4 the four-sample calls (render_views_4, render_views_textured_4) join the alternation")
     ap.add_argument("--mip", action="store_true", help="time the mip-mapped call (render_views_mip, render_views_mip_4) and the pyramid build "
                     "(texture_mips) beside the others")
+    ap.add_argument("--normals", action="store_true", help="time the smooth-shaded calls (render_views_smooth, render_views_textured_smooth and their "
+                    "_4 partners) and the vertex normals (mesh_vertex_normals) beside the others")
     ap.add_argument("--trace-only", type=int, default=None, metavar="RINGS")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -76,6 +79,15 @@ def main():
             calls["render_views_mip"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, mips=mips)
             if 4 in a.samples:
                 calls["render_views_mip_4"] = lambda: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail, samples=4, mips=mips)
+        if a.normals:
+            geometry = (packed.verts, packed.faces, packed.vert_off, packed.face_off)
+            vn = ops.mesh_vertex_normals(*geometry)
+            calls["mesh_vertex_normals"] = lambda: ops.mesh_vertex_normals(*geometry)
+            for smp in a.samples:
+                tag = "_4" if smp == 4 else ""
+                calls["render_views_smooth" + tag] = lambda smp=smp: ops.render_views(*packed.tensors, *tail, samples=smp, normals=vn)
+                calls["render_views_textured_smooth" + tag] = lambda smp=smp: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail,
+                                                                                                         samples=smp, normals=vn)
         if 1 not in a.samples:
             calls.pop("render_views_mip", None)
             del calls["render_views"], calls["render_views_textured"]
@@ -95,12 +107,17 @@ def main():
         med = {k: float(np.median(v)) for k, v in ms.items()}
         ratios = {"textured_over_plain": ("render_views_textured", "render_views"), "textured_4_over_plain_4": ("render_views_textured_4", "render_views_4"),
                   "textured_4_over_textured": ("render_views_textured_4", "render_views_textured"),
-                  "mip_over_textured": ("render_views_mip", "render_views_textured"), "mip_4_over_textured_4": ("render_views_mip_4", "render_views_textured_4")}
+                  "mip_over_textured": ("render_views_mip", "render_views_textured"), "mip_4_over_textured_4": ("render_views_mip_4", "render_views_textured_4"),
+                  "smooth_over_plain": ("render_views_smooth", "render_views"), "smooth_4_over_plain_4": ("render_views_smooth_4", "render_views_4"),
+                  "textured_smooth_over_textured": ("render_views_textured_smooth", "render_views_textured"),
+                  "textured_smooth_4_over_textured_4": ("render_views_textured_smooth_4", "render_views_textured_4")}
         print(json.dumps({"faces_per_mesh": faces, "batch": a.batch, "views": VIEWS, "size": SIZE, "texture": TEXTURE, "iters": a.iters, "ms_per_call": ms,
                           "median_ms_per_call": med, **{k: round(med[x] / med[y], 4) for k, (x, y) in ratios.items() if x in med and y in med},
                           "pixels_changed_by_textures": float((plain != tex).any(dim=2).float().mean()),
                           **({"pixels_changed_by_mips": float((calls["render_views_mip"]() != tex).any(dim=2).float().mean())}
-                             if "render_views_mip" in calls else {})}), flush=True)
+                             if "render_views_mip" in calls else {}),
+                          **({"pixels_changed_by_normals": float((calls["render_views_smooth"]() != plain).any(dim=2).float().mean())}
+                             if "render_views_smooth" in calls else {})}), flush=True)
 
 
 if __name__ == "__main__":

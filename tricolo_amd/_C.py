@@ -159,6 +159,9 @@ SIGNATURES = {
     "tri_raster_render_aa": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
     "tri_texture_mips": (I, [P, P, P, I, L, P, L, P, P]),
     "tri_raster_render_mip": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
+    "tri_raster_render_smooth": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
+    "tri_mesh_vertex_normals_workspace": (Z, [L]),
+    "tri_mesh_vertex_normals": (I, [P, P, P, P, I, L, L, I, P, P, P, P]),
     "tri_mesh_face_colours": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, L, P, P]),
     "tri_voxelize_workspace": (Z, [L, I, I]),
     "tri_voxelize_meshes": (I, [P, P, P, P, P, P, P, P, I, L, I, I, P, P, P, P]),

@@ -27,6 +27,13 @@
 // half rounded up; int64 holds it (2 * 255 * 2^48 < 2^63).  For power-of-two sizes that is the rounded mean of the 2^l x 2^l block.
 // mb_mip_sample is mb_tex_sample's rule on one level, with that level's own (H_l, W_l).
 //
+// Corner normals (optional; null when an initialiser stops at mip_off, as the sampler's, the voxeliser's and every raster entry point's
+// but tri_raster_render_smooth's does).  face_vn fp32 [sumF][3][3] holds one normal per face corner in the order of `faces`, indexed by
+// global face like face_uv; a face whose face_vn[f][0][0] is NaN has no normals (the host writes NaN into all nine values) and is
+// shaded flat.  Normals need not be unit length.  They come from the `vn` lines of the OBJ file (data/materials.py load_obj_normals)
+// or from mesh_normals.hip (tri_mesh_vertex_normals: area-weighted, by vertex index); only the SMOOTH resolve kernels of raster.hip
+// read them.
+//
 // Contraction is switched off HERE, not only in the including files: `#pragma clang fp contract(off)` covers the code that follows it,
 // so a helper defined in a header ahead of the including file's own pragma would be compiled with contraction on - a * b + c became
 // v_fmac_f32 in such a helper while the same expression in a kernel body stayed a multiply and an add.  With an fma the cross product
@@ -55,6 +62,7 @@ struct MeshBatch {
     int T;
     const unsigned* __restrict__ mip_texels;        // the mip pyramid: null when an initialiser stops at T
     const long* __restrict__ mip_off;
+    const float* __restrict__ face_vn;              // the corner normals: null when an initialiser stops at mip_off
 };
 
 // the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)

@@ -63,13 +63,29 @@
 //     c_l = mb_mip_sample (mesh_batch.h) of level l at (u, v): mb_tex_sample's rule with the level's own (H_l, W_l).  g is linear in
 //     rho, not its logarithm, so that every step is reproducible; the selection is continuous and monotone in rho - at rho = 1, at
 //     every octave and at the top level - and within 0.087 of a level of the logarithm.  colour = clamp((Kd c) s, 0, 1) as above.
+//   smooth shading (tri_raster_render_smooth only; the batch's corner normals face_vn are laid out in mesh_batch.h; everything above
+//     is untouched by it, visibility included - the clear, faces and queue passes are the same kernels).  At a position P - the pixel
+//     centre, or a sample's own position with four samples - where face f won and f has normals (its marker is not NaN):
+//     the face is set up again, its edge functions are formed at P, and the perspective-correct weights are those of the textured
+//     shading (rs_weights): l_k = fl32(E_k) / fl32(2A), w_k = l_k d_k, d = (w0 + w1) + w2, b_k = w_k / d;
+//     n_j = (b0 n0_j + b1 n1_j) + b2 n2_j per component, corners 1 and 2 swapped with the face's vertices as the UVs are;
+//     if an n_j is not finite, or len = sqrt((n_x^2 + n_y^2) + n_z^2) correctly rounded is 0, the position takes the flat shade s
+//     above, bit for bit; otherwise e = eye - a with a the face's vertex 0 (the e of the flat shade), side = (n_x e_x + n_y e_y) + n_z e_z,
+//     ndl = max(+-n_y / len, 0) with the sign of `side`, s = 0.1 + fl32(3 / pi) ndl, and the colour is formed exactly as above: u8 of
+//     clamp(Kd s, 0, 1), or of clamp((Kd c) s, 0, 1) with the texel c of the textured and mip-mapped modes.  A face without normals
+//     is shaded flat.  The interpolated normal is turned toward the eye per POSITION, as the flat one is per face, because neither
+//     ShapeNet's winding nor its vn lines can be trusted: compared with one-sided lighting that brightens the last pixels before a
+//     silhouette, where the interpolated normal already points away from the eye.  The turn is ours; so is the reading that the
+//     reference's pyrender meshes are smooth-shaded (data/render.py).  With four samples an untextured face WITH normals is coloured
+//     per sample - its shade varies across the pixel - and no longer once per face; a face without normals keeps that path.
 //
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
 // Every mode is that one sequence (rs_render: clear, faces, queue, resolve), its kernels templates on the keys per pixel S, 1 or 4, and
-// the resolve on the mode as well; the face set-up (rs_setup), a key (rs_pixel), (u, v, d) at a position (rs_uvd), the texel of a face
-// there (rs_texel, over mesh_batch.h's one bilinear tap) and a colour (rs_colour_u8) are each stated once for all of them.  With four
+// the resolve on the mode and on SMOOTH as well; the face set-up (rs_setup), a key (rs_pixel), the perspective-correct weights at a
+// position (rs_weights) and (u, v, d) from them (rs_uvd), the texel of a face there (rs_texel, over mesh_batch.h's one bilinear tap),
+// the smooth shade there (rs_smooth_shade) and a colour (rs_colour_u8) are each stated once for all of them.  With four
 // samples the split is by the samples' box, and the two inner walks differ on purpose: the one-sample lane visits every pixel of its
 // box; the four-sample lane moves a cursor over its box's samples to ITS next covered one with integer tests only - a pixel whose four
 // samples all lie outside one edge (the largest of that edge's four offsets is still negative) is stepped over whole - and only then
@@ -304,14 +320,46 @@ __device__ __forceinline__ void rs_edges(const RsFace& f, int px, int py, long* 
     for (int k = 0; k < 3; ++k) e[k] = f.e[k] + dx * f.sx[k] + dy * f.sy[k];
 }
 
-// THE (u, v) and d of a face with corner UVs q[0..5] (the swap applied) and fa = fl32(2A), where its edge functions are e[0..2]
-__device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa, const long* e, float& u, float& v, float& d) {
+// THE perspective-correct weights b0, b1, b2 and d of a face with fa = fl32(2A), where its edge functions are e[0..2]
+__device__ __forceinline__ void rs_weights(const RsFace& f, float fa, const long* e, float& b0, float& b1, float& b2, float& d) {
     const float l0 = mb_div((float)(double)e[0], fa), l1 = mb_div((float)(double)e[1], fa), l2 = mb_div((float)(double)e[2], fa);
     const float w0 = l0 * f.d[0], w1 = l1 * f.d[1], w2 = l2 * f.d[2];
     d = (w0 + w1) + w2;
-    const float b0 = mb_div(w0, d), b1 = mb_div(w1, d), b2 = mb_div(w2, d);
+    b0 = mb_div(w0, d); b1 = mb_div(w1, d); b2 = mb_div(w2, d);
+}
+
+// THE (u, v) and d of a face with corner UVs q[0..5] (the swap applied) and fa = fl32(2A), where its edge functions are e[0..2]
+__device__ __forceinline__ void rs_uvd(const RsFace& f, const float* q, float fa, const long* e, float& u, float& v, float& d) {
+    float b0, b1, b2;
+    rs_weights(f, fa, e, b0, b1, b2, d);
     u = (b0 * q[0] + b1 * q[2]) + b2 * q[4];
     v = (b0 * q[1] + b1 * q[3]) + b2 * q[5];
+}
+
+// true when global face gf carries corner normals: the marker face_vn[gf][0][0] is not NaN
+__device__ __forceinline__ bool rs_has_vn(const MeshBatch& m, long gf) {
+    const float n0 = m.face_vn[(size_t)gf * 9];
+    return n0 == n0;
+}
+
+// The smooth Lambert shade of face gf (with corner normals; set up by the caller as f; a: its vertex 0) where its edge functions are
+// e[0..2], seen from `eye`: the normal interpolated with the perspective-correct weights and turned toward the eye (head of this
+// file).  Leaves `shade` - the caller's flat one - as it is where the interpolated normal is not finite or has no length.
+__device__ __forceinline__ void rs_smooth_shade(const MeshBatch& m, const RsFace& f, long gf, const long* e, const float* a, const float* eye,
+                                                float& shade) {
+    const float* vn = m.face_vn + (size_t)gf * 9;
+    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
+    float b0, b1, b2, d, n[3];
+    rs_weights(f, (float)(double)f.A2, e, b0, b1, b2, d);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) n[j] = (b0 * vn[j] + b1 * vn[3 * i1 + j]) + b2 * vn[3 * i2 + j];
+    if (!(mb_finite(n[0]) && mb_finite(n[1]) && mb_finite(n[2]))) return;
+    const float len = mb_sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    if (len == 0.f) return;
+    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
+    const float side = (n[0] * ex + n[1] * ey) + n[2] * ez;
+    const float ny = mb_div(n[1], len);
+    shade = 0.1f + RS_KDIFF * fmaxf(side < 0.f ? -ny : ny, 0.f);
 }
 
 // The level of detail at a position with (u, v), d, from (ux, vx), dx one whole pixel to the right and (uy, vy), dy one whole pixel down
@@ -375,7 +423,8 @@ __device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* 
 
 // one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn.  TEX: the textured resolve pass - the
 // lanes of a wave whose face has a texture set it up again and run rs_texel together, the others wait for them and keep their Kd.
-template <bool TEX, bool MIP>
+// SMOOTH: a face with corner normals is set up again as well and takes rs_smooth_shade at the pixel centre.
+template <bool TEX, bool MIP, bool SMOOTH>
 __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx, float fy,
                                            float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image, int* __restrict__ visibility) {
     const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -394,17 +443,20 @@ __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __re
     }
     if (visibility) visibility[i] = (int)lf;
     const int* fi = m.faces + (size_t)(f0 + lf) * 3;
-    const float shade = rs_shade(mb_vertex(m, v0, V, fi[0]), mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
+    const float* a = mb_vertex(m, v0, V, fi[0]);
+    float shade = rs_shade(a, mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
     float kd[3];
     mb_face_kd(m, n, f0 + lf, kd);
-    if (TEX) {
-        const int t = mb_face_tex(m, n, f0 + lf);
+    if (TEX || SMOOTH) {
+        const int t = TEX ? mb_face_tex(m, n, f0 + lf) : -1;
+        const bool vn = SMOOTH && rs_has_vn(m, f0 + lf);
         RsFace f;
-        if (t >= 0 && rs_setup(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f)) {    // the winner of a pixel was set up before: true
+        if ((t >= 0 || vn) && rs_setup(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f)) {    // the winner of a pixel was set up before: true
             long e[3];
             float c[3];
             rs_edges(f, pix % W, pix / W, e);
-            if (rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
+            if (vn) rs_smooth_shade(m, f, f0 + lf, e, a, cam + (size_t)nv * 12, shade);
+            if (t >= 0 && rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) kd[k] = kd[k] * c[k];
             }
@@ -418,8 +470,9 @@ __device__ __forceinline__ void rs_resolve(const MeshBatch& m, const float* __re
 
 // one thread per pixel of the four-sample key buffer: every sample is coloured as rs_resolve colours a pixel - a textured face from (u, v)
 // at the sample's own position - and the pixel is the rounded integer mean.  A face met in the sample before is not shaded or set up
-// again, and an untextured one keeps its colour.
-template <bool TEX, bool MIP>
+// again, and an untextured one keeps its colour.  SMOOTH: a face with corner normals is shaded per sample, by rs_smooth_shade at the
+// sample's own position, textured or not; a face without them keeps the once-per-face path.
+template <bool TEX, bool MIP, bool SMOOTH>
 __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx,
                                               float fy, float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image,
                                               int* __restrict__ visibility) {
@@ -434,7 +487,8 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
     int sum[3] = {2, 2, 2}, col[3] = {255, 255, 255}, t = -1;
     long prev = -1, centre[3] = {0, 0, 0};
     float shade = 0.f, kd[3] = {0.f, 0.f, 0.f};
-    bool set = false;
+    bool set = false, vn = false;
+    const float* a = m.verts;
     RsFace f;
 #pragma unroll 1
     for (int s = 0; s < 4; ++s) {
@@ -450,25 +504,28 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
         if (lf != prev) {
             prev = lf;
             const int* fi = m.faces + (size_t)(f0 + lf) * 3;
-            shade = rs_shade(mb_vertex(m, v0, V, fi[0]), mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
+            a = mb_vertex(m, v0, V, fi[0]);
+            shade = rs_shade(a, mb_vertex(m, v0, V, fi[1]), mb_vertex(m, v0, V, fi[2]), cam + (size_t)nv * 12);
             mb_face_kd(m, n, f0 + lf, kd);
-            if (TEX) {
-                t = mb_face_tex(m, n, f0 + lf);
-                if (t >= 0) {
+            if (SMOOTH) vn = rs_has_vn(m, f0 + lf);
+            if (TEX || SMOOTH) {
+                if (TEX) t = mb_face_tex(m, n, f0 + lf);
+                if (t >= 0 || vn) {
                     set = rs_setup<RS_AA_LO, RS_AA_HI>(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f);     // the winner: true
                     rs_edges(f, pix % W, pix / W, centre);
                 }
             }
-            if (!TEX || t < 0) rs_colour_u8(kd, shade, col);
+            if (t < 0 && !vn) rs_colour_u8(kd, shade, col);
         }
-        if (TEX && t >= 0) {
-            float c[3], kc[3] = {kd[0], kd[1], kd[2]};
+        if (t >= 0 || vn) {
+            float c[3], kc[3] = {kd[0], kd[1], kd[2]}, sh = shade;
             const long e[3] = {centre[0] + rs_sample_step(f, 0, s), centre[1] + rs_sample_step(f, 1, s), centre[2] + rs_sample_step(f, 2, s)};
-            if (set && rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
+            if (vn && set) rs_smooth_shade(m, f, f0 + lf, e, a, cam + (size_t)nv * 12, sh);
+            if (t >= 0 && set && rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) kc[k] = kd[k] * c[k];
             }
-            rs_colour_u8(kc, shade, col);
+            rs_colour_u8(kc, sh, col);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) sum[k] += col[k];
@@ -478,13 +535,13 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
     for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)(sum[k] >> 2);
 }
 
-// the resolve kernel of S keys per pixel; TEX, MIP: the mode of the call
-template <int S, bool TEX, bool MIP>
+// the resolve kernel of S keys per pixel; TEX, MIP: the mode of the call; SMOOTH: the batch carries corner normals (m.face_vn)
+template <int S, bool TEX, bool MIP, bool SMOOTH>
 __global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, long npix,
                                                                     float fx, float fy, float znear, const u64* __restrict__ keys,
                                                                     uint8_t* __restrict__ image, int* __restrict__ visibility) {
-    if (S == 4) rs_resolve_aa<TEX, MIP>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
-    else rs_resolve<TEX, MIP>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+    if (S == 4) rs_resolve_aa<TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+    else rs_resolve<TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
 // one lane per face of the whole batch: out fp32 [sumF][3], the colour the voxeliser takes for the face
@@ -647,12 +704,15 @@ enum { RS_PLAIN = 0, RS_TEX = 1, RS_MIP = 2 };   // which resolve kernel colours
 typedef void (*RsResolve)(MeshBatch, const float*, int, int, int, long, float, float, float, const u64*, uint8_t*, int*);
 
 // THE launch sequence: clear, faces, queue, resolve, with `samples` keys per pixel (1 or 4).  A batch without textures (T == 0) takes
-// the plain resolve whatever the mode: mb_face_tex finds no texture in it.
+// the plain resolve whatever the mode: mb_face_tex finds no texture in it.  A batch with corner normals (m.face_vn) takes the SMOOTH
+// resolve of its mode; the three passes before it are the same kernels either way.
 static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
                      void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
-    static const RsResolve resolve[2][3] = {
-        {raster_resolve_kernel<1, false, false>, raster_resolve_kernel<1, true, false>, raster_resolve_kernel<1, true, true>},
-        {raster_resolve_kernel<4, false, false>, raster_resolve_kernel<4, true, false>, raster_resolve_kernel<4, true, true>}};
+    static const RsResolve resolve[2][2][3] = {
+        {{raster_resolve_kernel<1, false, false, false>, raster_resolve_kernel<1, true, false, false>, raster_resolve_kernel<1, true, true, false>},
+         {raster_resolve_kernel<4, false, false, false>, raster_resolve_kernel<4, true, false, false>, raster_resolve_kernel<4, true, true, false>}},
+        {{raster_resolve_kernel<1, false, false, true>, raster_resolve_kernel<1, true, false, true>, raster_resolve_kernel<1, true, true, true>},
+         {raster_resolve_kernel<4, false, false, true>, raster_resolve_kernel<4, true, false, true>, raster_resolve_kernel<4, true, true, true>}}};
     const int N = m.N;
     const int bad = rs_check(N, sumF, views, H, W, yfov, znear, samples, who);
     if (bad != TRI_OK) return bad;
@@ -676,7 +736,7 @@ static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam
         (aa ? raster_queue_kernel<4> : raster_queue_kernel<1>)<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount,
                                                                                                        queue, qcap);
     }
-    resolve[aa][m.T > 0 ? mode : RS_PLAIN]<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy,
+    resolve[m.face_vn != nullptr][aa][m.T > 0 ? mode : RS_PLAIN]<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy,
                                                                                                                     zn, keys, image, visibility);
     return tri_check_launch(who);
 }
@@ -742,6 +802,26 @@ extern "C" int tri_raster_render_mip(const float* verts, const int* faces, const
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
                       (const unsigned*)mip_texels, mip_off};
     return rs_render(m, RS_MIP, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
+}
+
+extern "C" int tri_raster_render_smooth(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                        const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                        const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
+                                        const float* face_vn, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
+                                        double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const char* who = "tri_raster_render_smooth";
+    if (!face_vn) { tri_set_error("tri_raster_render_smooth: face_vn must not be null"); return TRI_ERR_ARG; }
+    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_smooth: samples must be 1 or 4"); return TRI_ERR_ARG; }
+    if (T > 0 && (mip_texels != nullptr) != (mip_off != nullptr)) {         // T == 0: an empty pyramid may be null, nothing is textured
+        tri_set_error("tri_raster_render_smooth: the two pyramid fields come together or not at all");
+        return TRI_ERR_ARG;
+    }
+    const bool pyramid = mip_texels && mip_off;
+    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, pyramid);
+    if (bad != TRI_OK) return bad;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
+                      (const unsigned*)mip_texels, mip_off, face_vn};
+    return rs_render(m, pyramid ? RS_MIP : RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 
 extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,

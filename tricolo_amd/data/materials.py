@@ -1,6 +1,7 @@
 """Per-face diffuse colours of a Wavefront OBJ: the `usemtl` groups of the file and the `Kd` of the `mtllib` files next to it,
 as far as the renderer of data/render.py uses them.  load_obj_materials ignores map_Kd textures (and every other MTL statement);
-load_obj_textured also reads the `vt` texture coordinates and decodes the map_Kd images for ops.render_views_textured."""
+load_obj_textured also reads the `vt` texture coordinates and decodes the map_Kd images for ops.render_views_textured;
+load_obj_normals reads the `vn` normals of the face corners for the smooth shading of ops.render_views(..., normals=)."""
 from __future__ import annotations
 
 import math
@@ -63,6 +64,46 @@ def load_obj_materials(path):
     if face_material.shape[0] != faces.shape[0]:
         raise ValueError(f"{path}: {face_material.shape[0]} material entries for {faces.shape[0]} faces")
     return verts, faces, face_material, torch.from_numpy(np.asarray(kd, dtype=np.float32).reshape(-1, 3)), names
+
+
+def load_obj_normals(path):
+    """-> face_vn float32 [F, 3, 3]: the `vn x y z` of every face corner in the order of meshes.load_obj's faces (the third index of
+    tokens i/j/k and i//k; 1-based, negative = counted back from the vn lines read so far; polygons fan like their vertices,
+    (0, k, k + 1)).  All nine values are NaN for a face with a corner that has no vn index (tokens i and i/j), an index outside the
+    file's vn lines, a vn line that cannot be parsed, or a value that is not finite: such a face is shaded flat, or takes computed
+    normals (MeshBatch.with_vertex_normals).  The normals are taken as they stand, not normalised.  CRLF is tolerated."""
+    _, faces = load_obj(path)
+    with open(path, "rb") as f:
+        lines = [ln.strip() for ln in f.read().replace(b"\r", b"").split(b"\n")]
+    vn, rows = [], []
+    nan = (math.nan, math.nan, math.nan)
+    for ln in lines:
+        head = ln[:3]
+        if head in (b"vn ", b"vn\t"):
+            tok = ln.split()
+            try:
+                value = (float(tok[1]), float(tok[2]), float(tok[3]))
+            except (IndexError, ValueError):
+                value = nan
+            vn.append(value if all(math.isfinite(x) for x in value) else nan)
+        elif head[:2] in (b"f ", b"f\t"):
+            corner = []
+            for tok in ln.split()[1:]:
+                part = tok.split(b"/")
+                try:
+                    j = int(part[2]) if len(part) >= 3 and part[2] else 0
+                except ValueError:
+                    j = 0
+                j = j - 1 if j > 0 else len(vn) + j if j < 0 else -1
+                corner.append(vn[j] if 0 <= j < len(vn) else nan)
+            for k in range(1, len(corner) - 1):
+                tri = (corner[0], corner[k], corner[k + 1])
+                rows.append(tri if all(c[0] == c[0] for c in tri) else (nan, nan, nan))
+    face_vn = torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(-1, 3, 3))
+    face_vn[~torch.isfinite(face_vn).all(dim=2).all(dim=1)] = math.nan           # a value that overflows fp32 is not finite either
+    if face_vn.shape[0] != faces.shape[0]:
+        raise ValueError(f"{path}: {face_vn.shape[0]} normal rows for {faces.shape[0]} faces")
+    return face_vn
 
 
 def load_mtl_textures(path):

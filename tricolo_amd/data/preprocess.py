@@ -2,7 +2,8 @@
 splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
-        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on|mip] [--antialias off|4x]
+        [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on|mip] [--antialias off|4x] \\
+        [--shading flat|smooth]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
@@ -10,8 +11,8 @@ shapenet.json; for Text2ShapeC13 the existing map file is read instead - and `<e
 with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V]) and images (uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
 `<dirname(dataset_path)>/ShapeNetCore.v2/<category>/<model_id>/models/model_normalized.obj` by ops.render_views (csrc/raster.hip), a
 batch of meshes per call.  data/render.py says what that renderer restates of the reference's pyrender scene, what it deliberately
-does differently (Lambert shading, flat normals, no culling, textures only on request) and that no pixel has been compared with
-pyrender's.
+does differently (Lambert shading, flat normals unless asked otherwise, no culling, textures only on request) and that no pixel has
+been compared with pyrender's.
 
 --textures on (the default is off: a textured material renders with its bare Kd) reads the `vt` coordinates and the map_Kd images
 of the models (data/materials.py load_obj_textured; textures above 256 texels on a side are reduced) and renders through
@@ -30,6 +31,15 @@ rule is a definition of our own (data/render.py, head of csrc/raster.hip): no pi
 ops.render_views(..., samples=4): the 4x rotated grid, every sample covered, depth-tested and coloured by the one-sample rules, the
 pixel their rounded integer mean.  It works with --textures on (each sample takes the texture at its own (u, v)) and with --device
 cpu.  data/render.py says what it rests on - our unverified reading that pyrender's off-screen passes are 4x multisampled.
+
+--shading smooth (the default is flat: a pixel is lit by the normal of its face) reads the `vn` normals of the models beside whatever
+else is loaded (data/materials.py load_obj_normals), computes vertex normals for the faces that have none (ops.mesh_vertex_normals,
+once per packed batch: area-weighted, by vertex index) and renders with normals=: the corner normals are interpolated across the
+face, at the pixel centre or with --antialias 4x at every sample, turned toward the eye and lit as before.  It works with every
+--textures and --antialias choice and with --device cpu, and leaves the voxels alone.  The summary then counts the faces that came
+with vn and the faces that took computed normals.  It rests on our unverified readings, from memory, that pyrender shades trimesh
+meshes smoothly by default and that trimesh keeps a file's vn; the area weighting (trimesh: angle weighting) and the turn toward
+the eye at every position are our own (data/render.py).
 
 --voxels says where the grids come from.  nrrd (the default): Text2Shape's nrrd_256_filter_div_{V}_solid/<id>/<id>.nrrd downloads
 (data/nrrd.py), which exist for chairs and tables only.  mesh: ops.voxelize_meshes (csrc/voxelize.hip) voxelises the meshes already
@@ -58,7 +68,7 @@ import torch
 from .. import config as tcfg
 from ..meshes import MeshBatch
 from . import render, voxelize
-from .materials import load_obj_materials, load_obj_textured
+from .materials import load_obj_materials, load_obj_normals, load_obj_textured
 from .nrrd import read_nrrd
 
 VOXEL_SIZES = (32, 64, 128)
@@ -66,6 +76,7 @@ SPLITS = ("train", "val", "test")
 VOXEL_SOURCES = ("nrrd", "mesh", "auto")
 TEXTURE_MODES = ("off", "on", "mip")
 ANTIALIAS_MODES = {"off": 1, "4x": 4}                # --antialias -> samples per pixel
+SHADING_MODES = render.SHADING_MODES                 # ("flat", "smooth")
 
 
 def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
@@ -117,26 +128,38 @@ def nrrd_path(data_root, mid, v):
     return os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd")
 
 
-def pack_batch(meshes, device, textures=False):
+def pack_batch(meshes, device, textures=False, face_vn_list=None):
     """MeshBatch.pack of load_obj_materials' (or, with textures, load_obj_textured's) tuples; with textures the voxeliser's batch too.
-    textures="mip": the packed batch carries the mip pyramid of its textures, built here, once per batch."""
+    textures="mip": the packed batch carries the mip pyramid of its textures, built here, once per batch.  face_vn_list
+    (load_obj_normals of the same files): the renderer's batch carries them, completed by computed vertex normals once per batch; the
+    voxeliser's batch is what it is without them."""
+    from dataclasses import replace
     if not textures:
-        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device)
-        return packed, packed
-    from .. import ops
-    packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_uv_list=[m[5] for m in meshes],
-                            mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes])
-    solid = packed.with_face_colours(ops.mesh_face_colours(packed))
-    return (packed.with_texture_mips() if textures == "mip" else packed), solid
+        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_vn_list=face_vn_list)
+        solid = packed if face_vn_list is None else replace(packed, face_vn=None)
+    else:
+        from .. import ops
+        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_uv_list=[m[5] for m in meshes],
+                                mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes], face_vn_list=face_vn_list)
+        solid = packed.with_face_colours(ops.mesh_face_colours(packed))
+        if textures == "mip":
+            packed = packed.with_texture_mips()
+    if face_vn_list is not None:
+        packed = packed.with_vertex_normals(fill="missing")
+    return packed, solid
 
 
 def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd",
-                textures=False, texture_stats=None, samples=1):
+                textures=False, texture_stats=None, samples=1, shading="flat", normal_stats=None):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
     come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist).
     textures: read and render map_Kd textures, and colour mesh voxels from them ("mip": render them mip-mapped); texture_stats, a dict, then gains the number of
     "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded).
-    samples: coverage samples per pixel, 1 or 4 (render.render_batch)."""
+    samples: coverage samples per pixel, 1 or 4 (render.render_batch).  shading="smooth": read the `vn` normals, complete them with
+    computed vertex normals and render smooth-shaded; normal_stats, a dict, then gains the number of "faces_with_vn" (rendered with
+    the file's normals) and of "faces_with_computed_normals"."""
+    if shading not in SHADING_MODES:
+        raise ValueError(f"shading must be one of {SHADING_MODES}, got {shading!r}")
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
     load = load_obj_textured if textures else load_obj_materials
     for i in range(0, len(todo), batch_meshes):
@@ -145,8 +168,16 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
         if textures and texture_stats is not None:
             texture_stats["textured_models"] = texture_stats.get("textured_models", 0) + sum(1 for m in meshes if len(m[7]))
             texture_stats["texture_failures"] = texture_stats.get("texture_failures", 0) + sum(len(m[8]) for m in meshes)
-        packed, solid = pack_batch(meshes, device, textures)
-        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures, samples=samples).cpu().numpy()
+        normals = None
+        if shading == "smooth":
+            normals = [load_obj_normals(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
+        packed, solid = pack_batch(meshes, device, textures, normals)
+        if normals is not None and normal_stats is not None:
+            given = sum(int((~torch.isnan(vn[:, 0, 0])).sum()) for vn in normals)
+            normal_stats["faces_with_vn"] = normal_stats.get("faces_with_vn", 0) + given
+            normal_stats["faces_with_computed_normals"] = (normal_stats.get("faces_with_computed_normals", 0)
+                                                           + int((~torch.isnan(packed.face_vn[:, 0, 0])).sum()) - given)
+        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures, samples=samples, shading=shading).cpu().numpy()
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
         if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
@@ -168,7 +199,8 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
 
 
 def main(argv=None, log=print):
-    """-> {split: {"models", "written", "skipped"}}, with --textures on | mip also "textured_models" and "texture_failures"."""
+    """-> {split: {"models", "written", "skipped"}}, with --textures on | mip also "textured_models" and "texture_failures", with
+    --shading smooth also "faces_with_vn" and "faces_with_computed_normals"."""
     ap = argparse.ArgumentParser(prog="python -m tricolo_amd.data.preprocess", description=__doc__.split("\n\n")[0])
     ap.add_argument("overrides", nargs="*", help="config overrides, e.g. data=text2shape_chair_table data.dataset_root_path=...")
     ap.add_argument("--batch-meshes", type=int, default=8, help="meshes rendered per call")
@@ -181,6 +213,8 @@ def main(argv=None, log=print):
                     "material renders with its bare Kd")
     ap.add_argument("--antialias", choices=tuple(ANTIALIAS_MODES), default="off", help="4x: four coverage samples per pixel (the 4x rotated grid), "
                     "the pixel their rounded mean; off: visibility at the pixel centre alone")
+    ap.add_argument("--shading", choices=SHADING_MODES, default="flat", help="smooth: interpolate the models' vn normals, and computed vertex "
+                    "normals where a face has none (ops.mesh_vertex_normals), across every face; flat: the normal of the face")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.batch_meshes < 1:
         ap.error("--batch-meshes must be positive")
@@ -197,13 +231,16 @@ def main(argv=None, log=print):
         else:
             keys = read_model_ids(map_path)
         tex = {"textured_models": 0, "texture_failures": 0} if args.textures != "off" else {}
+        nrm = {"faces_with_vn": 0, "faces_with_computed_normals": 0} if args.shading == "smooth" else {}
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
                                        args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, {"off": False, "on": True, "mip": "mip"}[args.textures], tex,
-                                       ANTIALIAS_MODES[args.antialias])
-        stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex}
+                                       ANTIALIAS_MODES[args.antialias], args.shading, nrm)
+        stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex, **nrm}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")
         if tex:
             log(f"  {tex['textured_models']} of the written models have a texture, {tex['texture_failures']} map_Kd files could not be loaded")
+        if nrm:
+            log(f"  {nrm['faces_with_vn']} faces rendered with the normals of their file, {nrm['faces_with_computed_normals']} with computed ones")
     return stats
 
 

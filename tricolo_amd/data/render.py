@@ -10,7 +10,17 @@ are not installed where this was written: NOBODY HAS COMPARED A PIXEL OF THIS RE
 
 Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliberate differences:
   * Lambert diffuse plus ambient, Kd (0.1 + 3/pi max(n . l, 0)), instead of pyrender's metallic-roughness BRDF;
-  * flat face normals (no vertex normals, no smoothing), turned toward the eye;
+  * flat face normals by default, turned toward the eye.  Smooth shading is opt-in (normals= of ops.render_views and
+    ops.render_views_textured, shading="smooth" below, --shading smooth of data/preprocess.py): the corner normals of the batch - the
+    `vn` lines of the OBJ file (data/materials.py load_obj_normals) and, for faces without, vertex normals computed by
+    ops.mesh_vertex_normals - are interpolated with the perspective-correct weights at the pixel centre (with samples=4, at each
+    sample's own position) and lit as the flat normal is.  It rests on two readings FROM MEMORY of the published sources that nobody
+    has checked, neither library being installed where this was written: that pyrender.Mesh.from_trimesh defaults to smooth=True, so
+    the reference's images are shaded with per-vertex normals, and that trimesh keeps the `vn` of a file as vertex_normals or
+    computes them.  Two things are OUR OWN DEFINITION: the computed normals are weighted by face AREA and summed by vertex index
+    (trimesh weighs by the face's angle at the vertex, and we do not merge vertices by position), and the interpolated normal is
+    turned toward the eye per position, like the flat one per face, because neither ShapeNet's winding nor its vn can be trusted -
+    compared with one-sided lighting that brightens the last pixels before a silhouette.  No pixel has been compared with pyrender's;
   * no back-face culling: both sides of a face are drawn (ShapeNet's winding is unreliable);
   * map_Kd textures are opt-in (ops.render_views_textured, textures=True below; the default renders a textured material with its
     bare Kd): colour = Kd x texel, the MTL rule and - from their documentation - what trimesh's SimpleMaterial becomes in pyrender
@@ -287,6 +297,46 @@ def sample_mips(t, u, v, right, down, mip_texels, mip_off, tex_size):
     return ok, torch.where(two[:, None], c0 + (c1 - c0) * g[:, None], c0)
 
 
+def _weights(X, Y, d, fa, f, Px, Py):
+    """csrc/raster.hip rs_weights: ([b0, b1, b2], d) fp32 [P] of the faces f int64 [P] of project_faces' (X, Y, d) at the positions
+    (Px, Py) in 1/256 pixel, fa = fl32(2A) of those faces: l_k = fl32(E_k) / fa, w_k = l_k d_k, d = (w0 + w1) + w2, b_k = w_k / d."""
+    w = []
+    for k in range(3):
+        a, b = (k + 1) % 3, (k + 2) % 3
+        e = (X[f, b] - X[f, a]) * (Py - Y[f, a]) - (Y[f, b] - Y[f, a]) * (Px - X[f, a])
+        w.append((e.to(torch.float32) / fa) * d[f, k])
+    dd = (w[0] + w[1]) + w[2]
+    return [wk / dd for wk in w], dd
+
+
+def _smooth_one(verts, faces, cam, H, W, yfov, znear, vis, face_vn, offsets=CENTRE):
+    """(has bool [HW S], shade fp32 [HW S]) of one mesh and one view: where the winning face of vis int64 [HW S] has corner normals
+    (face_vn fp32 [F, 3, 3], the mesh's rows) and their interpolation at the sample's own position is finite and has a length, and the
+    smooth shade there (head of csrc/raster.hip, rs_smooth_shade); everywhere else the caller keeps the flat shade."""
+    has = torch.zeros((vis.numel(),), dtype=torch.bool)
+    shade = torch.zeros((vis.numel(),), dtype=torch.float32)
+    pix = torch.nonzero((vis >= 0) & ~torch.isnan(face_vn[vis.clamp(min=0), 0, 0])).reshape(-1)
+    if pix.numel() == 0:
+        return has, shade
+    _, X, Y, d, A2, order = project_faces(verts, faces, cam, H, W, yfov, znear, with_order=True)
+    f = vis[pix]
+    S, off = len(offsets), torch.tensor(offsets, dtype=torch.int64)
+    pixel, s = torch.div(pix, S, rounding_mode="floor"), pix % S
+    Px, Py = 256 * (pixel % W) + off[s, 0], 256 * torch.div(pixel, W, rounding_mode="floor") + off[s, 1]
+    bw, _ = _weights(X, Y, d, A2[f].to(torch.float32), f, Px, Py)
+    vn = face_vn[f].gather(1, order[f][:, :, None].expand(-1, 3, 3))
+    n = [(bw[0] * vn[:, 0, j] + bw[1] * vn[:, 1, j]) + bw[2] * vn[:, 2, j] for j in range(3)]
+    length = torch.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
+    ok = torch.isfinite(n[0]) & torch.isfinite(n[1]) & torch.isfinite(n[2]) & (length != 0)
+    e = cam[:3] - verts[faces[f, 0]]
+    side = (n[0] * e[:, 0] + n[1] * e[:, 1]) + n[2] * e[:, 2]
+    ny = n[1] / torch.where(ok, length, torch.ones_like(length))
+    ndl = torch.where(side < 0, -ny, ny).clamp(min=0.0)
+    has[pix[ok]] = True
+    shade[pix[ok]] = (0.1 + _f32(KDIFF) * ndl)[ok]
+    return has, shade
+
+
 def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texels, tex_off, tex_size, offsets=CENTRE, mips=None):
     """(has bool [HW S], c fp32 [HW S, 3]) of one mesh and one view: where the winning face of vis int64 [HW S] (the S = len(offsets)
     samples of a pixel innermost) is textured, and the texture colour at the perspective-correct (u, v) of the sample's own position
@@ -306,13 +356,7 @@ def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texe
     uv = face_uv[f].gather(1, order[f][:, :, None].expand(-1, 3, 2))
 
     def uvd(Px, Py):
-        w = []
-        for k in range(3):
-            a, b = (k + 1) % 3, (k + 2) % 3
-            e = (X[f, b] - X[f, a]) * (Py - Y[f, a]) - (Y[f, b] - Y[f, a]) * (Px - X[f, a])
-            w.append((e.to(torch.float32) / fa) * d[f, k])
-        dd = (w[0] + w[1]) + w[2]
-        bw = [wk / dd for wk in w]
+        bw, dd = _weights(X, Y, d, fa, f, Px, Py)
         return ((bw[0] * uv[:, 0, 0] + bw[1] * uv[:, 1, 0]) + bw[2] * uv[:, 2, 0],
                 (bw[0] * uv[:, 0, 1] + bw[1] * uv[:, 1, 1]) + bw[2] * uv[:, 2, 1], dd)
 
@@ -326,8 +370,9 @@ def _texels_one(verts, faces, cam, H, W, yfov, znear, vis, face_t, face_uv, texe
     return has, c
 
 
-def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
-    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background); tex: _texels_one's pair.
+def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None, smooth=None):
+    """u8 [3, HW] of one mesh and one view from its visibility buffer vis int64 [HW] (-1 = background); tex: _texels_one's pair;
+    smooth: _smooth_one's pair, whose shade replaces the flat one where it has one.
     Every entry is coloured on its own, so a four-sample buffer [HW 4] gives the four sample colours of every pixel."""
     out = torch.full((3, vis.numel()), 255, dtype=torch.uint8)
     pix = torch.nonzero(vis >= 0).reshape(-1)
@@ -343,6 +388,8 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
     ny = cy / torch.where(ok, length, torch.ones_like(length))
     ndl = torch.where(ok, torch.where(side < 0, -ny, ny).clamp(min=0.0), torch.zeros_like(ny))
     shade = 0.1 + _f32(KDIFF) * ndl
+    if smooth is not None:
+        shade = torch.where(smooth[0][pix], smooth[1][pix], shade)
     colour = face_kd(face_mat[f], kd)
     if tex is not None:
         colour = torch.where(tex[0][pix][:, None], colour * tex[1][pix], colour)
@@ -352,12 +399,13 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None):
 
 
 def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
-                     return_visibility=False, textures=None, samples=1, mips=None):
+                     return_visibility=False, textures=None, samples=1, mips=None, normals=None):
     """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch.  textures: the five
     texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured.  samples=4: coverage,
     depth and colour at the four SAMPLE_OFFSETS of every pixel, the pixel their rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2 per
     channel, the visibility int32 [N, views, H, W, 4].  mips: the pyramid pair (texture_mips_cpu) for the mip-mapped colours of
-    ops.render_views_textured(..., mips=)."""
+    ops.render_views_textured(..., mips=).  normals: the batch's corner normals face_vn fp32 [sumF, 3, 3] for the smooth shade of
+    ops.render_views(..., normals=) - interpolated at every sample's own position - in any of those modes."""
     if samples not in (1, 4):
         raise ValueError(f"render_views_cpu: samples must be 1 or 4, got {samples!r}")
     offsets = SAMPLE_OFFSETS if samples == 4 else CENTRE
@@ -382,7 +430,10 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
                 uv = face_uv[foff[n]:foff[n + 1]]
                 face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
                 tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size, offsets, mips)
-            colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex)
+            smooth = None
+            if normals is not None:
+                smooth = _smooth_one(v, f, cam[n, k], H, W, yfov, znear, face, normals[foff[n]:foff[n + 1]], offsets)
+            colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex, smooth)
             if samples == 4:
                 colour = ((colour.view(3, H * W, 4).to(torch.int32).sum(dim=2) + 2) >> 2).to(torch.uint8)
             image[n, k] = colour.view(3, H, W)
@@ -411,16 +462,61 @@ def mesh_face_colours_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
     return out
 
 
+NORMAL_CLAMP, NORMAL_SCALE = float(2 ** 16), float(2 ** 36)                       # csrc/mesh_normals.hip MN_CLAMP, MN_SCALE
+
+
+def mesh_vertex_normals_cpu(verts, faces, vert_off, face_off, face_vn=None, fill_all=False):
+    """ops.mesh_vertex_normals on CPU tensors -> face_vn fp32 [sumF, 3, 3]: the integers and the float64 of csrc/mesh_normals.hip in
+    torch.  Per mesh the fp32 cross products (meshes.cross) of the faces whose three components are finite, clamped to +-2^16 and
+    rounded to int64 at 2^36 (torch.round: ties to even), are index_add_-ed at the faces' clamped vertices; a corner is
+    fl32(fl64(S) / sqrt((S_x^2 + S_y^2) + S_z^2)); a face with a corner whose sum is (0, 0, 0), or of a mesh without vertices, is nine
+    NaNs.  Unless fill_all, a face whose face_vn[f, 0, 0] is not NaN keeps its nine values."""
+    voff, foff = vert_off.tolist(), face_off.tolist()
+    out = torch.full((faces.shape[0], 3, 3), float("nan"), dtype=torch.float32)
+    for n in range(len(voff) - 1):
+        V, f = voff[n + 1] - voff[n], faces[foff[n]:foff[n + 1]]
+        if V <= 0 or f.shape[0] == 0:
+            continue
+        v, f = verts[voff[n]:voff[n + 1]], clamp_index(f, V)
+        c = torch.stack(cross(v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]), dim=1)
+        q = torch.round(c.clamp(-NORMAL_CLAMP, NORMAL_CLAMP).to(torch.float64) * NORMAL_SCALE)
+        q = torch.where(torch.isfinite(c).all(dim=1, keepdim=True), q, torch.zeros_like(q)).to(torch.int64)
+        acc = torch.zeros((V, 3), dtype=torch.int64)
+        for j in range(3):
+            acc.index_add_(0, f[:, j], q)
+        S = acc[f]                                                                  # [F, 3 corners, 3]
+        x, y, z = (S[:, :, k].to(torch.float64) for k in range(3))
+        some = (S != 0).any(dim=2)
+        length = torch.where(some, torch.sqrt((x * x + y * y) + z * z), torch.ones_like(x))
+        normal = torch.stack([x / length, y / length, z / length], dim=2).to(torch.float32)
+        out[foff[n]:foff[n + 1]] = torch.where(some.all(dim=1)[:, None, None], normal, torch.full_like(normal, float("nan")))
+    if face_vn is not None and not fill_all:
+        given = ~torch.isnan(face_vn[:, 0, 0])
+        out[given] = face_vn[given]
+    return out
+
+
+SHADING_MODES = ("flat", "smooth")
+
+
 # ------------------------------------------------------------------------------------------------ the convenient calls
-def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1):
+def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1, shading="flat"):
     """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
     [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
     ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures).
     textures="mip": render_views_textured with the mip pyramid of the batch's textures, built here (MeshBatch.with_texture_mips)
-    unless the batch carries one.  samples=4: four coverage samples per pixel (ops.render_views)."""
+    unless the batch carries one.  samples=4: four coverage samples per pixel (ops.render_views).  shading="smooth": the batch's
+    corner normals batch.face_vn (MeshBatch.pack(..., face_vn_list=) and / or MeshBatch.with_vertex_normals()) are interpolated
+    across every face that has them (normals= of the two calls); a batch without face_vn raises."""
     from .. import ops
     if not isinstance(textures, bool) and textures != "mip":
         raise ValueError(f"textures must be False, True or \"mip\", got {textures!r}")
+    if shading not in SHADING_MODES:
+        raise ValueError(f"shading must be one of {SHADING_MODES}, got {shading!r}")
+    if shading == "smooth" and batch.face_vn is None:
+        raise ValueError("render_batch: shading=\"smooth\" needs corner normals - MeshBatch.pack(..., face_vn_list=) or "
+                         "MeshBatch.with_vertex_normals()")
+    normals = batch.face_vn if shading == "smooth" else None
     cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
     H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
     if textures:
@@ -430,14 +526,18 @@ def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=F
                 raise ValueError("render_batch: the batch was packed without textures (MeshBatch.pack(..., face_uv_list=, mat_tex_list=, textures_list=))")
             mips = (batch if batch.mip_texels is not None else batch.with_texture_mips()).mip_tensors
         return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples,
-                                         mips=mips)
-    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples)
+                                         mips=mips, normals=normals)
+    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples, normals=normals)
 
 
 def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False,
-                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1):
+                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1, face_vn_list=None):
     """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None); textures=True
-    and textures="mip" need the three texture lists of MeshBatch.pack."""
+    and textures="mip" need the three texture lists of MeshBatch.pack.  face_vn_list (per mesh float32 [F, 3, 3], NaN rows for faces
+    without; data.materials.load_obj_normals) turns smooth shading on: the faces without normals take computed ones
+    (MeshBatch.with_vertex_normals(fill="missing")) and the batch is rendered with shading="smooth"."""
     batch = MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device, face_uv_list=face_uv_list, mat_tex_list=mat_tex_list,
-                           textures_list=textures_list)
-    return render_batch(batch, num_views, image_size, return_visibility, textures, samples)
+                           textures_list=textures_list, face_vn_list=face_vn_list)
+    if face_vn_list is None:
+        return render_batch(batch, num_views, image_size, return_visibility, textures, samples)
+    return render_batch(batch.with_vertex_normals(fill="missing"), num_views, image_size, return_visibility, textures, samples, shading="smooth")

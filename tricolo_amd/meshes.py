@@ -194,7 +194,8 @@ def host_boxes(verts_list):
 @dataclass
 class MeshBatch:
     """A packed batch on one device; the three material tensors are None for a batch packed without materials, the five texture
-    tensors for a batch packed without textures, the two pyramid tensors until with_texture_mips() has built them."""
+    tensors for a batch packed without textures, the two pyramid tensors until with_texture_mips() has built them, face_vn for a
+    batch packed without face_vn_list until with_vertex_normals() has computed it."""
     verts: torch.Tensor
     faces: torch.Tensor
     vert_off: torch.Tensor
@@ -211,13 +212,15 @@ class MeshBatch:
     tex_size: torch.Tensor | None = None
     mip_texels: torch.Tensor | None = None          # the mip pyramid of the textures (with_texture_mips); None without one
     mip_off: torch.Tensor | None = None
+    face_vn: torch.Tensor | None = None             # corner normals fp32 [sumF, 3, 3], a NaN row = a face without; None without any
 
     @classmethod
     def pack(cls, verts_list, faces_list, face_mat_list=None, kd_list=None, device=None, *, face_uv_list=None, mat_tex_list=None,
-             textures_list=None):
+             textures_list=None, face_vn_list=None):
         """pack_meshes, then pack_materials where face_mat_list and kd_list are given; device=None: where verts_list[0] lives.  With
         face_uv_list, mat_tex_list and textures_list (all three, beside the materials) pack_textures adds the texture fields,
-        validated by check_textures."""
+        validated by check_textures.  face_vn_list: per mesh the corner normals float32 [F, 3, 3] (data.materials.load_obj_normals;
+        all nine values NaN for a face without), concatenated into face_vn."""
         verts, faces, voff, foff, max_faces = pack_meshes(verts_list, faces_list, device)
         mats = (None, None, None)
         if face_mat_list is not None:
@@ -238,7 +241,15 @@ class MeshBatch:
                     raise ValueError(f"mesh {n}: {len(mt)} mat_tex entries for {kd.shape[0]} materials")
             tex = pack_textures(face_uv_list, mat_tex_list, textures_list, verts.device)
             check_textures(*tex, faces.shape[0], mats[1].shape[0])
-        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list), *tex)
+        face_vn = None
+        if face_vn_list is not None:
+            if len(face_vn_list) != len(faces_list):
+                raise ValueError("every mesh needs its face_vn")
+            for n, (vn, f) in enumerate(zip(face_vn_list, faces_list)):
+                if not torch.is_tensor(vn) or vn.dtype != torch.float32 or tuple(vn.shape) != (f.shape[0], 3, 3):
+                    raise ValueError(f"mesh {n}: face_vn must be a float32 tensor of shape [{f.shape[0]}, 3, 3]")
+            face_vn = torch.cat([vn.to(verts.device) for vn in face_vn_list]).contiguous()
+        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list), *tex, face_vn=face_vn)
 
     @property
     def tensors(self):                              # the first seven arguments of ops.render_views and ops.voxelize_meshes, in their order
@@ -264,9 +275,18 @@ class MeshBatch:
         check_texture_mips(mip_texels, mip_off, self.tex_size)
         return replace(self, mip_texels=mip_texels, mip_off=mip_off)
 
+    def with_vertex_normals(self, fill="missing"):
+        """The batch with computed corner normals (ops.mesh_vertex_normals: area-weighted, by vertex index; head of
+        csrc/mesh_normals.hip): what render_batch(..., shading="smooth") renders from.  fill="missing" keeps the normals the batch
+        was packed with and fills the faces without; fill="all" overwrites every face.  Everything else is shared, not copied."""
+        from dataclasses import replace
+
+        from . import ops
+        return replace(self, face_vn=ops.mesh_vertex_normals(self.verts, self.faces, self.vert_off, self.face_off, self.face_vn, fill))
+
     def with_face_colours(self, colours):
-        """The batch with one material per face, `colours` fp32 [sumF, 3] (ops.mesh_face_colours) as their Kd, and no textures: what
-        the voxeliser takes to colour its voxels from textures.  face_mat counts up within every mesh and mat_off = face_off."""
+        """The batch with one material per face, `colours` fp32 [sumF, 3] (ops.mesh_face_colours) as their Kd, and no textures or
+        normals: what the voxeliser takes to colour its voxels from textures.  face_mat counts up within every mesh and mat_off = face_off."""
         sumF = self.faces.shape[0]
         if not torch.is_tensor(colours) or colours.dtype != torch.float32 or tuple(colours.shape) != (sumF, 3) or colours.device != self.verts.device:
             raise ValueError(f"colours must be a float32 tensor of shape [{sumF}, 3] on the batch's device")

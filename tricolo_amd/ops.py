@@ -1686,10 +1686,11 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
 RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
 
 
-def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples):
+def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples, normals=None):
     """The body of render_views and render_views_textured, whose own arguments are checked (batch: the seven tensors of the packed
-    batch; textures: its five texture tensors, or None; mips: the checked pyramid pair, or None): the camera, the limits, then the one
-    entry point of csrc/raster.hip for the mode, or data.render.render_views_cpu on CPU tensors."""
+    batch; textures: its five texture tensors, or None; mips: the checked pyramid pair, or None; normals: the checked face_vn, or
+    None): the camera, the limits, then the one entry point of csrc/raster.hip for the mode - tri_raster_render_smooth for every mode
+    with normals - or data.render.render_views_cpu on CPU tensors."""
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
     views, sumF, dev = cam.shape[1], batch[1].shape[0], batch[0].device
@@ -1703,7 +1704,8 @@ def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visi
                          f"{N * views * H * W * samples * 8} bytes; one call takes fewer than 2^31 {unit} and at most 65535 views - split the batch")
     if not batch[0].is_cuda:
         from .data.render import render_views_cpu
-        return render_views_cpu(*batch, cam, H, W, yfov, znear, return_visibility, textures=textures, samples=samples, mips=mips)
+        return render_views_cpu(*batch, cam, H, W, yfov, znear, return_visibility, textures=textures, samples=samples, mips=mips,
+                                normals=normals)
     image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=dev)
     vis = torch.empty((N, views, H, W) + ((4,) if samples == 4 else ()), dtype=torch.int32, device=dev) if return_visibility else None
     size = (lib().tri_raster_workspace_aa if samples == 4 else lib().tri_raster_workspace)(sumF, N, views, H, W)
@@ -1712,7 +1714,10 @@ def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visi
     tex = [ptr(x) for x in (textures or (None,) * 5)] + [textures[4].shape[0] if textures else 0]
     view = [ptr(cam), N, sumF, views, H, W, float(yfov), float(znear)]
     out = [ptr(ws), ptr(image), ptr(vis), stream()]
-    if mips is not None:
+    if normals is not None:
+        pyramid = [ptr(mips[0]), ptr(mips[1])] if mips is not None else [None, None]
+        name, args = "tri_raster_render_smooth", mesh + tex + pyramid + [ptr(normals)] + view + [samples] + out
+    elif mips is not None:
         name, args = "tri_raster_render_mip", mesh + tex + [ptr(mips[0]), ptr(mips[1])] + view + [samples] + out
     elif samples == 4 or textures is not None:
         name, args = "tri_raster_render_aa" if samples == 4 else "tri_raster_render_tex", mesh + tex + view + out
@@ -1728,8 +1733,18 @@ def _render_samples(stage, samples):
     return int(samples)
 
 
+def _mesh_normals(stage, faces, normals):
+    """Checks the corner normals a call was given for its batch (csrc/mesh_batch.h face_vn; meshes.MeshBatch.face_vn) -> normals."""
+    if not torch.is_tensor(normals) or normals.device != faces.device:
+        raise ValueError(f"{stage}: normals must be a tensor on the batch's device, {faces.device}")
+    if normals.dtype != torch.float32 or tuple(normals.shape) != (faces.shape[0], 3, 3) or not normals.is_contiguous():
+        raise ValueError(f"{stage}: normals must be a contiguous float32 tensor of shape [{faces.shape[0]}, 3, 3], got {tuple(normals.shape)} "
+                         f"{normals.dtype}")
+    return normals
+
+
 def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=math.pi / 3, znear=0.05,
-                 return_visibility=False, samples=1):
+                 return_visibility=False, samples=1, normals=None):
     """Render every mesh of a packed batch (meshes.MeshBatch.pack) from every camera -> images uint8 [N, views, 3, H, W], with
     return_visibility also int32 [N, views, H, W]: the face seen at each pixel centre, local to its mesh, -1 for background.
     face_mat int32 [sumF]: a material per face, local to the mesh; mat_kd fp32 [sumM, 3] diffuse colours with mat_off int64 [N + 1];
@@ -1742,12 +1757,20 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     samples=4 takes coverage and depth at four positions per pixel - (96, 32), (224, 96), (32, 160), (160, 224) in 1/256 pixel from the
     pixel's top-left corner, the 4x rotated grid - by the same rules, colours every sample as a pixel is coloured and writes their
     rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2; the visibility is then int32 [N, views, H, W, 4], and one call takes fewer than
-    2^31 samples.  samples=1, the default, is the pixel centre alone; anything else raises."""
+    2^31 samples.  samples=1, the default, is the pixel centre alone; anything else raises.
+    normals=face_vn fp32 [sumF, 3, 3] (meshes.MeshBatch.face_vn: one normal per face corner in the order of `faces`, any length; a
+    NaN in face_vn[f, 0, 0] = the face has none) turns smooth shading on: at the pixel centre - with samples=4 at each sample's own
+    position - the corner normals of the winning face are interpolated with the perspective-correct weights, the result is turned
+    toward the eye and lit as the flat normal is (head of csrc/raster.hip).  A face without normals, and a position where the
+    interpolated normal is not finite or has no length, is shaded flat, bit for bit; visibility never changes.  The turn toward the
+    eye at every position is this project's own rule.  normals=None, the default, is the call as it was."""
     H, W = int(H), int(W)
     samples = _render_samples("render_views", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views")
+    if normals is not None:
+        normals = _mesh_normals("render_views", faces, normals)
     return _render("render_views", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off), None, None, cam, H, W, yfov, znear,
-                   return_visibility, samples)
+                   return_visibility, samples, normals)
 
 
 def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size):
@@ -1821,7 +1844,7 @@ def _mesh_mips(stage, texels, tex_size, mips):
 
 
 def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size, cam, H, W,
-                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1, mips=None):
+                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1, mips=None, normals=None):
     """render_views with map_Kd textures: the packed batch and its five texture tensors (MeshBatch.tensors, MeshBatch.texture_tensors).
     face_uv fp32 [sumF, 3, 2]: one (u, v) per face corner, NaN in face_uv[f, 0, 0] = the face has none; mat_tex int32 [sumM]: a
     batch-global texture index per material, -1 = none; texels u8 [sumTexels, 4] RGBA; tex_off int64 [T + 1]; tex_size int32 [T, 2]
@@ -1835,15 +1858,59 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
     right and one whole pixel down, rho is the longer of the two steps in texels, and the colour blends the two pyramid levels around
     log2(rho) (head of csrc/raster.hip; no LOD bias, no anisotropy).  Where the texture is magnified (rho <= 1) the colour is the one
     without mips, bit for bit; visibility never changes.  The rule is this project's own definition: no pixel of it has been compared
-    with pyrender's mip-mapping.  mips=None, the default, is the call as it was."""
+    with pyrender's mip-mapping.  mips=None, the default, is the call as it was.
+    normals=face_vn: render_views' smooth shading, with or without mips and at either sample count; the texel is taken as before and
+    multiplies Kd, the smooth shade replaces the flat one.  normals=None, the default, is the call as it was."""
     H, W = int(H), int(W)
     samples = _render_samples("render_views_textured", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
     _mesh_textures("render_views_textured", faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size)
     if mips is not None:
         mips = _mesh_mips("render_views_textured", texels, tex_size, mips)
+    if normals is not None:
+        normals = _mesh_normals("render_views_textured", faces, normals)
     return _render("render_views_textured", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off),
-                   (face_uv, mat_tex, texels, tex_off, tex_size), mips, cam, H, W, yfov, znear, return_visibility, samples)
+                   (face_uv, mat_tex, texels, tex_off, tex_size), mips, cam, H, W, yfov, znear, return_visibility, samples, normals)
+
+
+VERTEX_NORMAL_FILL = {"missing": 0, "all": 1}
+
+
+def mesh_vertex_normals(verts, faces, vert_off, face_off, face_vn=None, fill="missing"):
+    """Vertex normals of a packed batch (meshes.MeshBatch.pack) as corner normals -> face_vn fp32 [sumF, 3, 3], what normals= of
+    render_views takes.  A definition of this project (head of csrc/mesh_normals.hip): per vertex INDEX of a mesh the fp32 cross
+    products of the faces that use it - area-weighted; clamped to +-2^16 per component and rounded to fixed point at 2^36 - are summed
+    with 64-bit integer atomics, so the result does not depend on the order of the faces and is bit-reproducible; a corner is that
+    sum normalised in float64 and rounded to fp32.  Vertices at one position are not merged.  fill="missing": a face whose incoming
+    face_vn[f, 0, 0] is not NaN keeps its nine values bit for bit, the others (all, when face_vn is None) are computed; fill="all":
+    every face is computed.  A face with a corner whose sum is (0, 0, 0) - two coincident faces of opposite winding, say - gets nine
+    NaNs and renders flat.  A vertex shared by more than 2^10 faces with components at the clamp would wrap its sum (modular, still
+    deterministic).  Three launches, no host synchronisation.  CPU tensors run data.render.mesh_vertex_normals_cpu, the same integers
+    and float64 in torch."""
+    if fill not in VERTEX_NORMAL_FILL:
+        raise ValueError(f"mesh_vertex_normals: fill must be one of {sorted(VERTEX_NORMAL_FILL)}, got {fill!r}")
+    if not all(torch.is_tensor(x) for x in (verts, faces, vert_off, face_off)) or len({x.device for x in (verts, faces, vert_off, face_off)}) != 1:
+        raise ValueError("mesh_vertex_normals: all tensors must live on one device")
+    _mesh_arg(verts, "verts", torch.float32, 3)
+    _mesh_arg(faces, "faces", torch.int32, 3)
+    N = vert_off.numel() - 1
+    if N < 0:
+        raise ValueError("vert_off must hold N + 1 offsets")
+    _mesh_arg(vert_off, "vert_off", torch.int64, numel=N + 1)
+    _mesh_arg(face_off, "face_off", torch.int64, numel=N + 1)
+    if face_vn is not None:
+        face_vn = _mesh_normals("mesh_vertex_normals", faces, face_vn)
+    sumV, sumF = verts.shape[0], faces.shape[0]
+    if sumV >= 2 ** 31 or sumF >= 2 ** 31:
+        raise ValueError("mesh_vertex_normals: 2^31 or more vertices or faces in one batch")
+    if not verts.is_cuda:
+        from .data.render import mesh_vertex_normals_cpu
+        return mesh_vertex_normals_cpu(verts, faces, vert_off, face_off, face_vn, fill == "all")
+    out = torch.empty((sumF, 3, 3), dtype=torch.float32, device=verts.device)
+    ws = torch.empty((max(16, lib().tri_mesh_vertex_normals_workspace(sumV)),), dtype=torch.uint8, device=verts.device)
+    check(lib().tri_mesh_vertex_normals(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), N, sumV, sumF, VERTEX_NORMAL_FILL[fill], ptr(ws),
+                                        ptr(face_vn), ptr(out), stream()), "tri_mesh_vertex_normals")
+    return out
 
 
 def mesh_face_colours(batch):
