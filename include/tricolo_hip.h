@@ -588,6 +588,24 @@ int tri_raster_render_smooth(const float* verts, const int* faces, const long* v
                              const float* face_vn, const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear,
                              int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
 
+/* The glTF 2.0 metallic-roughness BRDF in place of the Lambert shade: any of the six modes above, flat (face_vn null) or smooth, with
+ * the batch's mat_pbr fp32 [sumM][2] = (metallic, roughness) per material, indexed like mat_kd (csrc/mesh_batch.h; metallic clamped to
+ * [0, 1], roughness to [0.04, 1], a NaN takes the lower bound; a mesh without materials takes (0.2, 0.8)).  The other arguments are
+ * tri_raster_render_smooth's and the mode follows from them in the same way.  Visibility is tri_raster_render's
+ * (tri_raster_render_aa's with four samples), bit for bit: only the resolve pass differs.  At the pixel centre - with four samples at
+ * each sample's own position - the world position p on the winning face comes from the perspective-correct weights, v = (eye - p) /
+ * |eye - p|, l = (0, 1, 0), h = (l + v) / |l + v|, n is the unit shading normal of the Lambert modes, base = Kd (times the texel), and
+ *   colour = clamp(0.1 base + 3 NL ((1 - F) cdiff / pi + F G D / (4 NL NV)), 0, 1)
+ * with Schlick's Fresnel term, the Smith-GGX geometry term and the GGX distribution of the glTF specification and the cosine clamps of
+ * the Khronos reference shader; every sum, product and quotient is spelled out at the head of csrc/raster.hip.  A position where a
+ * weight, |eye - p| or |l + v| is not finite or zero, or the normal has no finite length, takes the Lambert colour of
+ * tri_raster_render_smooth, bit for bit.  The same workspace and limits.  A null mat_pbr is TRI_ERR_ARG. */
+int tri_raster_render_brdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                           const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                           const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
+                           const float* face_vn, const float* mat_pbr, const float* cam, int N, long sumF, int views, int H, int W,
+                           double yfov, double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
+
 /* Vertex normals of a packed batch, written as corner normals face_vn_out fp32 [sumF][3][3] for tri_raster_render_smooth.  A
  * definition of this project (head of csrc/mesh_normals.hip): area-weighted - the fp32 cross product of every face, clamped to
  * +-2^16 per component and rounded to fixed point with 36 fractional bits, is summed per VERTEX INDEX of its mesh with 64-bit integer

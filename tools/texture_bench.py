@@ -6,9 +6,10 @@ views at 224 x 224 - and ops.mesh_face_colours on the same batch.  Two of the th
 one process, and every window is reported, so the spread is on the page.  One JSON line per size.  --mip adds the mip-mapped call
 (ops.render_views_textured(..., mips=), with --samples 1 4 in both sample counts) and ops.texture_mips, the pyramid build for the
 batch's 256 x 256 textures, to the alternation.  --normals adds the smooth-shaded calls (normals= of both renderers, the batch's
-computed vertex normals, in every sample count asked for) and ops.mesh_vertex_normals itself.
+computed vertex normals, in every sample count asked for) and ops.mesh_vertex_normals itself.  --brdf adds the metallic-roughness
+partner (brdf= of both renderers; metallic 1 with two roughnesses, and the default (0.2, 0.8)) of every render call in the alternation.
 
-    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--mip] [--normals] [--trace-only RINGS]
+    python tools/texture_bench.py [--rings 100 317] [--batch 8] [--iters 20] [--windows 5] [--samples 1 4] [--mip] [--normals] [--brdf] [--trace-only RINGS]
     (--trace-only: three warmed calls of each for rocprofv3 --kernel-trace --stats, which gives the resolve kernels' own times)
 """
 import argparse
@@ -61,6 +62,7 @@ def main():
                     "(texture_mips) beside the others")
     ap.add_argument("--normals", action="store_true", help="time the smooth-shaded calls (render_views_smooth, render_views_textured_smooth and their "
                     "_4 partners) and the vertex normals (mesh_vertex_normals) beside the others")
+    ap.add_argument("--brdf", action="store_true", help="time the metallic-roughness partner (its name with _brdf) of every render call beside the others")
     ap.add_argument("--trace-only", type=int, default=None, metavar="RINGS")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -88,6 +90,21 @@ def main():
                 calls["render_views_smooth" + tag] = lambda smp=smp: ops.render_views(*packed.tensors, *tail, samples=smp, normals=vn)
                 calls["render_views_textured_smooth" + tag] = lambda smp=smp: ops.render_views_textured(*packed.tensors, *packed.texture_tensors, *tail,
                                                                                                          samples=smp, normals=vn)
+        if a.brdf:
+            pbr = torch.tensor([[0.2, 0.8], [1.0, 0.76], [1.0, 0.5]] * a.batch, device=dev)
+            renders = {"render_views": (False, None, None), "render_views_textured": (True, None, None)}
+            if a.mip:
+                renders["render_views_mip"] = (True, mips, None)
+            if a.normals:
+                renders["render_views_smooth"], renders["render_views_textured_smooth"] = (False, None, vn), (True, None, vn)
+            for name, (textured, pyramid, normals) in renders.items():
+                for smp in a.samples:
+                    if textured:
+                        fn = lambda smp=smp, pyramid=pyramid, normals=normals: ops.render_views_textured(    # noqa: E731
+                            *packed.tensors, *packed.texture_tensors, *tail, samples=smp, mips=pyramid, normals=normals, brdf=pbr)
+                    else:
+                        fn = lambda smp=smp, normals=normals: ops.render_views(*packed.tensors, *tail, samples=smp, normals=normals, brdf=pbr)  # noqa: E731
+                    calls[name + ("_4" if smp == 4 else "") + "_brdf"] = fn
         if 1 not in a.samples:
             calls.pop("render_views_mip", None)
             del calls["render_views"], calls["render_views_textured"]
@@ -117,7 +134,12 @@ def main():
                           **({"pixels_changed_by_mips": float((calls["render_views_mip"]() != tex).any(dim=2).float().mean())}
                              if "render_views_mip" in calls else {}),
                           **({"pixels_changed_by_normals": float((calls["render_views_smooth"]() != plain).any(dim=2).float().mean())}
-                             if "render_views_smooth" in calls else {})}), flush=True)
+                             if "render_views_smooth" in calls else {}),
+                          **{k + "_over_lambert": round(med[k] / med[k[:-5]], 4) for k in med if k.endswith("_brdf") and k[:-5] in med},
+                          **({"pixels_changed_by_brdf": float((calls["render_views_brdf"]() != plain).any(dim=2).float().mean()),
+                              "drawn_pixels_changed_by_brdf": float(((calls["render_views_brdf"]() != plain).any(dim=2) & (plain != 255).any(dim=2)).sum()
+                                                                    / (plain != 255).any(dim=2).sum())}
+                             if "render_views_brdf" in calls else {})}), flush=True)
 
 
 if __name__ == "__main__":

@@ -160,6 +160,7 @@ SIGNATURES = {
     "tri_texture_mips": (I, [P, P, P, I, L, P, L, P, P]),
     "tri_raster_render_mip": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
     "tri_raster_render_smooth": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
+    "tri_raster_render_brdf": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
     "tri_mesh_vertex_normals_workspace": (Z, [L]),
     "tri_mesh_vertex_normals": (I, [P, P, P, P, I, L, L, I, P, P, P, P]),
     "tri_mesh_face_colours": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, L, P, P]),

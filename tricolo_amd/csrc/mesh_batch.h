@@ -28,11 +28,16 @@
 // mb_mip_sample is mb_tex_sample's rule on one level, with that level's own (H_l, W_l).
 //
 // Corner normals (optional; null when an initialiser stops at mip_off, as the sampler's, the voxeliser's and every raster entry point's
-// but tri_raster_render_smooth's does).  face_vn fp32 [sumF][3][3] holds one normal per face corner in the order of `faces`, indexed by
-// global face like face_uv; a face whose face_vn[f][0][0] is NaN has no normals (the host writes NaN into all nine values) and is
-// shaded flat.  Normals need not be unit length.  They come from the `vn` lines of the OBJ file (data/materials.py load_obj_normals)
-// or from mesh_normals.hip (tri_mesh_vertex_normals: area-weighted, by vertex index); only the SMOOTH resolve kernels of raster.hip
-// read them.
+// but tri_raster_render_smooth's and tri_raster_render_brdf's does).  face_vn fp32 [sumF][3][3] holds one normal per face corner in
+// the order of `faces`, indexed by global face like face_uv; a face whose face_vn[f][0][0] is NaN has no normals (the host writes NaN
+// into all nine values) and is shaded flat.  Normals need not be unit length.  They come from the `vn` lines of the OBJ file
+// (data/materials.py load_obj_normals) or from mesh_normals.hip (tri_mesh_vertex_normals: area-weighted, by vertex index); only the
+// SMOOTH resolve kernels of raster.hip read them.
+//
+// PBR factors (optional; null when an initialiser stops at face_vn, as every entry point's but tri_raster_render_brdf's does).  mat_pbr
+// fp32 [sumM][2] holds (metallic, roughness) per material, indexed like mat_kd by mat_off and the face's clamped material.  mb_face_pbr
+// below reads them: metallic is clamped to [0, 1] and roughness to [0.04, 1], each as fminf(fmaxf(x, lo), hi), so a NaN takes the lower
+// bound; a mesh without materials takes (0.2, 0.8) beside its grey 0.4.  Only the BRDF resolve kernels of raster.hip read them.
 //
 // Contraction is switched off HERE, not only in the including files: `#pragma clang fp contract(off)` covers the code that follows it,
 // so a helper defined in a header ahead of the including file's own pragma would be compiled with contraction on - a * b + c became
@@ -63,6 +68,7 @@ struct MeshBatch {
     const unsigned* __restrict__ mip_texels;        // the mip pyramid: null when an initialiser stops at T
     const long* __restrict__ mip_off;
     const float* __restrict__ face_vn;              // the corner normals: null when an initialiser stops at mip_off
+    const float* __restrict__ mat_pbr;              // (metallic, roughness) per material: null when an initialiser stops at face_vn
 };
 
 // the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
@@ -86,6 +92,15 @@ __device__ __forceinline__ void mb_face_kd(const MeshBatch& m, int n, long gf, f
     const long j = min((long)(unsigned)m.face_mat[gf], M - 1);
 #pragma unroll
     for (int k = 0; k < 3; ++k) kd[k] = M > 0 ? m.mat_kd[(size_t)(m0 + j) * 3 + k] : 0.4f;
+}
+
+// the clamped (metallic, roughness) of global face gf of mesh n (m.mat_pbr is not null): a bad material index reads the mesh's own last
+// material; (0.2, 0.8) without materials.  fmaxf first, then fminf: a NaN takes the lower bound, 0 or 0.04.
+__device__ __forceinline__ void mb_face_pbr(const MeshBatch& m, int n, long gf, float& metal, float& rough) {
+    const long m0 = m.mat_off[n], M = m.mat_off[n + 1] - m0;
+    const long j = min((long)(unsigned)m.face_mat[gf], M - 1);
+    metal = fminf(fmaxf(M > 0 ? m.mat_pbr[(size_t)(m0 + j) * 2] : 0.2f, 0.f), 1.f);
+    rough = fminf(fmaxf(M > 0 ? m.mat_pbr[(size_t)(m0 + j) * 2 + 1] : 0.8f, 0.04f), 1.f);
 }
 
 // o = (b - a) x (c - a) in fp32, every operation rounded on its own

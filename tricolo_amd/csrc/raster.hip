@@ -78,14 +78,44 @@
 //     silhouette, where the interpolated normal already points away from the eye.  The turn is ours; so is the reading that the
 //     reference's pyrender meshes are smooth-shaded (data/render.py).  With four samples an untextured face WITH normals is coloured
 //     per sample - its shade varies across the pixel - and no longer once per face; a face without normals keeps that path.
+//   the glTF metallic-roughness BRDF (tri_raster_render_brdf only; the batch's PBR factors mat_pbr are laid out in mesh_batch.h;
+//     everything above is untouched by it, visibility included - the clear, faces and queue passes are the same kernels).  The formulas
+//     are the glTF 2.0 specification's, the clamps of the cosines the Khronos glTF-WebGL-PBR reference shader's; that pyrender shades
+//     this way is a reading from memory nobody has checked (data/render.py).  At a position P - the pixel centre, or a sample's own
+//     position with four samples - where face f of mesh n won, every operation fp32 and rounded on its own, sums in the order written:
+//     base_k per channel: what the modes above multiply the shade with - Kd, or Kd c with the texel c of the textured and mip-mapped
+//       modes, with their fallbacks to Kd;
+//     (m, r) = mb_face_pbr (mesh_batch.h): m = fminf(fmaxf(metallic, 0), 1), r = fminf(fmaxf(roughness, 0.04), 1) - a NaN takes the
+//       lower bound - and (0.2, 0.8) for a mesh without materials;  alpha = r r,  a2 = alpha alpha;
+//     n: the unit normal of the Lambert modes.  Flat: x = (b - a) x (c - a), len = sqrt((x_x^2 + x_y^2) + x_z^2), n_j = x_j / len, every
+//       n_j negated when side = (x_x e_x + x_y e_y) + x_z e_z < 0 with e = eye - a.  Smooth, for a face with corner normals whose
+//       interpolation at P is finite with len != 0 (the rule above): n_j = +-(interpolated n_j) / len by the sign of its own side.  The
+//       Lambert shade at P is s = 0.1 + fl32(3 / pi) max(n_y, 0) (n_y = 0 for a flat len of 0) - the bits of the modes above;
+//     b_k, d = rs_weights at P;  p_j = (b0 a_j + b1 b_j) + b2 c_j with the face's corners in the swapped order, as the UVs are;
+//     q = eye - p,  dist = sqrt((q_x^2 + q_y^2) + q_z^2),  v_j = q_j / dist;  l = (0, 1, 0);  g = (v_x, 1 + v_y, v_z),
+//     hl = sqrt((g_x^2 + g_y^2) + g_z^2),  h_j = g_j / hl;
+//     NL = clamp(n_y, 0.001, 1),  NV = clamp(|(n_x v_x + n_y v_y) + n_z v_z|, 0.001, 1),  NH = clamp((n_x h_x + n_y h_y) + n_z h_z, 0, 1),
+//     VH = clamp((v_x h_x + v_y h_y) + v_z h_z, 0, 1),  clamp(x, lo, hi) = fminf(fmaxf(x, lo), hi);
+//     w = 1 - VH,  w5 = (((w w) w) w) w  (four multiplications);
+//     g(x) = (2 x) / (x + sqrt(a2 + (1 - a2) (x x))),  G = g(NL) g(NV);   t = (NH NH) (a2 - 1) + 1,  D = a2 / ((pi t) t), pi = fl32(pi);
+//     S = (G D) / ((4 NL) NV)  - the specular term without its Fresnel factor, one quotient for the three channels;
+//     per channel  F0 = 0.04 + (base - 0.04) m,  cdiff = (0.96 base) (1 - m),  F = F0 + (1 - F0) w5,
+//       colour = clamp(0.1 base + (3 NL) (((1 - F) cdiff) / pi + F S), 0, 1),  u8 = floor(255 colour + 0.5);  background 255.
+//     No pow, exp or log; every root and quotient is the correctly rounded one (mb_sqrt, mb_div).
+//     Fallback: where a b_k is not finite, dist or hl is zero or not finite, or the len of the normal in use is zero or not finite (or
+//     the winner could not be set up again, which cannot happen), the position takes the Lambert colour u8(clamp(base s, 0, 1)) - what
+//     tri_raster_render_smooth (without normals: the plain, textured or mip-mapped call) writes there, bit for bit.
+//     With four samples every sample of every face is coloured at its own position - v varies across the pixel, so the once-per-face
+//     shortcut of untextured flat faces does not apply - and the pixel is still (c0 + c1 + c2 + c3 + 2) >> 2.
 //
 // Work: one lane per (view, face) sets the face up; a pixel box of at most RS_SMALL x RS_SMALL is rasterised by the lane itself, a
 // larger one is appended to a device queue (one atomic add per wave, slots by ballot), and a second kernel on a fixed grid walks the
 // queue - one workgroup per queued face, its lanes tiling the box - with the count it reads on the device.  No host synchronisation.
 // Every mode is that one sequence (rs_render: clear, faces, queue, resolve), its kernels templates on the keys per pixel S, 1 or 4, and
-// the resolve on the mode and on SMOOTH as well; the face set-up (rs_setup), a key (rs_pixel), the perspective-correct weights at a
+// the resolve on the mode, on SMOOTH and on BRDF as well; the face set-up (rs_setup), a key (rs_pixel), the perspective-correct weights at a
 // position (rs_weights) and (u, v, d) from them (rs_uvd), the texel of a face there (rs_texel, over mesh_batch.h's one bilinear tap),
-// the smooth shade there (rs_smooth_shade) and a colour (rs_colour_u8) are each stated once for all of them.  With four
+// the smooth shade there (rs_smooth_shade), the metallic-roughness colour there (rs_brdf_u8, with the unit normals of rs_flat_normal and
+// rs_smooth_normal) and a Lambert colour (rs_colour_u8) are each stated once for all of them.  With four
 // samples the split is by the samples' box, and the two inner walks differ on purpose: the one-sample lane visits every pixel of its
 // box; the four-sample lane moves a cursor over its box's samples to ITS next covered one with integer tests only - a pixel whose four
 // samples all lie outside one edge (the largest of that edge's four offsets is still negative) is stepped over whole - and only then
@@ -108,6 +138,7 @@
 #define RS_AA_LO 32                             // the leftmost / topmost and the rightmost / lowest of the four samples, in 1/256 pixel
 #define RS_AA_HI 224
 #define RS_KDIFF 0.95492965f                    // fl32(3 / pi): intensity 3, Lambert's 1 / pi
+#define RS_PI 3.14159274f                       // fl32(pi)
 #define RS_B13 0.33333334f                      // fl32(1 / 3), fl32(2 / 3), fl32(1 / 6): the sample positions of the face colours
 #define RS_B23 0.6666667f
 #define RS_B16 0.16666667f
@@ -421,6 +452,167 @@ __device__ __forceinline__ void rs_colour_u8(const float* kd, float shade, int* 
     }
 }
 
+// The unit flat normal n of the face (a, b, c), turned toward `eye`; n = 0 where the cross product has no length.  0.1 + RS_KDIFF
+// fmaxf(n[1], 0) is rs_shade's value, bit for bit.  True when the length is above 0 and finite: the BRDF may use n.
+__device__ __forceinline__ bool rs_flat_normal(const float* a, const float* b, const float* c, const float* eye, float* n) {
+    float x[3];
+    mb_cross(a, b, c, x);
+    const float len = mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
+    const float side = (x[0] * ex + x[1] * ey) + x[2] * ez;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float nj = len > 0.f ? mb_div(x[j], len) : 0.f;
+        n[j] = side < 0.f ? -nj : nj;
+    }
+    return len > 0.f && mb_finite(len);
+}
+
+// The unit smooth normal of face gf (with corner normals; a: its vertex 0) from the weights b0, b1, b2 of rs_weights, turned toward
+// `eye`: rs_smooth_shade's normal, so that 0.1 + RS_KDIFF fmaxf(n[1], 0) is its shade, bit for bit.  Leaves n and good - the caller's
+// flat ones - as they are where the interpolated normal is not finite or has no length; good: the length is finite as well.
+__device__ __forceinline__ void rs_smooth_normal(const MeshBatch& m, const RsFace& f, long gf, float b0, float b1, float b2, const float* a,
+                                                 const float* eye, float* n, bool& good) {
+    const float* vn = m.face_vn + (size_t)gf * 9;
+    const int i1 = f.swap ? 2 : 1, i2 = f.swap ? 1 : 2;
+    float x[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) x[j] = (b0 * vn[j] + b1 * vn[3 * i1 + j]) + b2 * vn[3 * i2 + j];
+    if (!(mb_finite(x[0]) && mb_finite(x[1]) && mb_finite(x[2]))) return;
+    const float len = mb_sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    if (len == 0.f) return;
+    const float ex = eye[0] - a[0], ey = eye[1] - a[1], ez = eye[2] - a[2];
+    const float side = (x[0] * ex + x[1] * ey) + x[2] * ez;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float nj = mb_div(x[j], len);
+        n[j] = side < 0.f ? -nj : nj;
+    }
+    good = mb_finite(len);
+}
+
+__device__ __forceinline__ float rs_clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+
+// Smith-GGX for one direction: (2 x) / (x + sqrt(a2 + (1 - a2) (x x)))
+__device__ __forceinline__ float rs_smith(float x, float a2) { return mb_div(2.f * x, x + mb_sqrt(a2 + (1.f - a2) * (x * x))); }
+
+// THE metallic-roughness colour (head of this file) of a position with the weights b0, b1, b2 on the face with corners pa, pb, pc (the
+// swap applied), the unit normal n, base colour `base` and the clamped factors (metal, rough), seen from `eye`: col[0..2] as u8 values.
+// False, with col untouched, where the position falls back to the Lambert colour.
+__device__ __forceinline__ bool rs_brdf_u8(const float* base, float metal, float rough, const float* n, const float* pa, const float* pb,
+                                           const float* pc, float b0, float b1, float b2, const float* eye, int* col) {
+    if (!(mb_finite(b0) && mb_finite(b1) && mb_finite(b2))) return false;
+    float q[3], v[3], h[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) q[j] = eye[j] - ((b0 * pa[j] + b1 * pb[j]) + b2 * pc[j]);
+    const float dist = mb_sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
+    if (!(dist > 0.f && mb_finite(dist))) return false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[j] = mb_div(q[j], dist);
+    const float gx = v[0], gy = 1.0f + v[1], gz = v[2];
+    const float hl = mb_sqrt((gx * gx + gy * gy) + gz * gz);
+    if (!(hl > 0.f && mb_finite(hl))) return false;
+    h[0] = mb_div(gx, hl); h[1] = mb_div(gy, hl); h[2] = mb_div(gz, hl);
+    const float NL = rs_clamp(n[1], 0.001f, 1.f);
+    const float NV = rs_clamp(fabsf((n[0] * v[0] + n[1] * v[1]) + n[2] * v[2]), 0.001f, 1.f);
+    const float NH = rs_clamp((n[0] * h[0] + n[1] * h[1]) + n[2] * h[2], 0.f, 1.f);
+    const float VH = rs_clamp((v[0] * h[0] + v[1] * h[1]) + v[2] * h[2], 0.f, 1.f);
+    const float w = 1.0f - VH, w5 = (((w * w) * w) * w) * w;
+    const float alpha = rough * rough, a2 = alpha * alpha;
+    const float G = rs_smith(NL, a2) * rs_smith(NV, a2);
+    const float t = (NH * NH) * (a2 - 1.0f) + 1.0f;
+    const float D = mb_div(a2, (RS_PI * t) * t);
+    const float S = mb_div(G * D, (4.f * NL) * NV);
+    const float light = 3.f * NL;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float F0 = 0.04f + (base[k] - 0.04f) * metal, cdiff = (0.96f * base[k]) * (1.0f - metal);
+        const float F = F0 + (1.0f - F0) * w5;
+        const float c = rs_clamp(0.1f * base[k] + light * (mb_div((1.0f - F) * cdiff, RS_PI) + F * S), 0.f, 1.f);
+        col[k] = (int)(uint8_t)(int)floorf(255.f * c + 0.5f);
+    }
+    return true;
+}
+
+// one thread per pixel of a BRDF call, S keys per pixel: every position - the pixel centre, or each of the four samples - is coloured
+// on its own by rs_brdf_u8, or where that falls back by rs_colour_u8 with the Lambert shade of the position; the pixel is the colour
+// of its one position or the rounded integer mean of four.  A face met in the sample before is not set up again.
+template <int S, bool TEX, bool MIP, bool SMOOTH>
+__device__ __forceinline__ void rs_resolve_brdf(const MeshBatch& m, const float* __restrict__ cam, int views, int H, int W, long npix, float fx,
+                                                float fy, float znear, const u64* __restrict__ keys, uint8_t* __restrict__ image,
+                                                int* __restrict__ visibility) {
+    const long i = (long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (i >= npix) return;
+    const int HW = H * W;
+    const long nv = i / HW;
+    const int pix = (int)(i - nv * HW), n = (int)(nv / views);
+    u64 key4[4] = {0, 0, 0, 0};
+    if (S == 4) {
+        const ulonglong2* kp = (const ulonglong2*)(keys + 4 * (size_t)i);           // the workspace is 16-byte aligned
+        const ulonglong2 ka = kp[0], kb = kp[1];
+        key4[0] = ka.x; key4[1] = ka.y; key4[2] = kb.x; key4[3] = kb.y;
+    } else {
+        key4[0] = keys[i];
+    }
+    const float* eye = cam + (size_t)nv * 12;
+    const long f0 = m.face_off[n], F = m.face_off[n + 1] - f0, v0 = m.vert_off[n], V = m.vert_off[n + 1] - v0;
+    int sum[3] = {S == 4 ? 2 : 0, S == 4 ? 2 : 0, S == 4 ? 2 : 0}, t = -1;
+    long prev = -1, centre[3] = {0, 0, 0};
+    float kd[3] = {0.f, 0.f, 0.f}, flat[3] = {0.f, 0.f, 0.f}, metal = 0.f, rough = 0.f;
+    bool set = false, vn = false, flat_good = false;
+    const float *pa = m.verts, *pb = m.verts, *pc = m.verts;
+    RsFace f;
+#pragma unroll 1
+    for (int s = 0; s < S; ++s) {
+        const u64 key = s == 0 ? key4[0] : s == 1 ? key4[1] : s == 2 ? key4[2] : key4[3];
+        const long lf = (long)(0xFFFFFFFFu - (unsigned)key);
+        const bool none = key == 0 || lf >= F || V <= 0;
+        if (visibility) visibility[(size_t)S * i + s] = none ? -1 : (int)lf;
+        if (none) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sum[k] += 255;
+            continue;
+        }
+        if (lf != prev) {
+            prev = lf;
+            const int* fi = m.faces + (size_t)(f0 + lf) * 3;
+            pa = mb_vertex(m, v0, V, fi[0]);
+            const float *p1 = mb_vertex(m, v0, V, fi[1]), *p2 = mb_vertex(m, v0, V, fi[2]);
+            flat_good = rs_flat_normal(pa, p1, p2, eye, flat);
+            mb_face_kd(m, n, f0 + lf, kd);
+            mb_face_pbr(m, n, f0 + lf, metal, rough);
+            if (SMOOTH) vn = rs_has_vn(m, f0 + lf);
+            if (TEX) t = mb_face_tex(m, n, f0 + lf);
+            set = rs_setup<RS_LO(S), RS_HI(S)>(m, cam, f0 + lf, n, nv, H, W, fx, fy, znear, f);       // the winner: true
+            if (set) rs_edges(f, pix % W, pix / W, centre);
+            pb = set && f.swap ? p2 : p1;
+            pc = set && f.swap ? p1 : p2;
+        }
+        float c[3], base[3] = {kd[0], kd[1], kd[2]}, nrm[3] = {flat[0], flat[1], flat[2]};
+        bool good = flat_good;
+        int col[3];
+        bool done = false;
+        if (set) {
+            const long e[3] = {centre[0] + (S == 1 ? 0 : rs_sample_step(f, 0, s)), centre[1] + (S == 1 ? 0 : rs_sample_step(f, 1, s)),
+                               centre[2] + (S == 1 ? 0 : rs_sample_step(f, 2, s))};
+            float b0, b1, b2, d;
+            rs_weights(f, (float)(double)f.A2, e, b0, b1, b2, d);
+            if (vn) rs_smooth_normal(m, f, f0 + lf, b0, b1, b2, pa, eye, nrm, good);
+            if (t >= 0 && rs_texel<MIP>(m, f, f0 + lf, t, e, c)) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) base[k] = kd[k] * c[k];
+            }
+            done = good && rs_brdf_u8(base, metal, rough, nrm, pa, pb, pc, b0, b1, b2, eye, col);
+        }
+        if (!done) rs_colour_u8(base, 0.1f + RS_KDIFF * fmaxf(nrm[1], 0.f), col);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sum[k] += col[k];
+    }
+    uint8_t* out = image + (size_t)nv * 3 * HW + pix;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)(S == 4 ? sum[k] >> 2 : sum[k]);
+}
+
 // one thread per pixel: the winning face's flat Lambert colour, 255 where nothing was drawn.  TEX: the textured resolve pass - the
 // lanes of a wave whose face has a texture set it up again and run rs_texel together, the others wait for them and keep their Kd.
 // SMOOTH: a face with corner normals is set up again as well and takes rs_smooth_shade at the pixel centre.
@@ -535,12 +727,14 @@ __device__ __forceinline__ void rs_resolve_aa(const MeshBatch& m, const float* _
     for (int k = 0; k < 3; ++k) out[(size_t)k * HW] = (uint8_t)(sum[k] >> 2);
 }
 
-// the resolve kernel of S keys per pixel; TEX, MIP: the mode of the call; SMOOTH: the batch carries corner normals (m.face_vn)
-template <int S, bool TEX, bool MIP, bool SMOOTH>
+// the resolve kernel of S keys per pixel; TEX, MIP: the mode of the call; SMOOTH: the batch carries corner normals (m.face_vn); BRDF:
+// it carries PBR factors (m.mat_pbr) and is coloured by the metallic-roughness BRDF
+template <int S, bool TEX, bool MIP, bool SMOOTH, bool BRDF>
 __global__ __launch_bounds__(RS_THREADS) void raster_resolve_kernel(MeshBatch m, const float* __restrict__ cam, int views, int H, int W, long npix,
                                                                     float fx, float fy, float znear, const u64* __restrict__ keys,
                                                                     uint8_t* __restrict__ image, int* __restrict__ visibility) {
-    if (S == 4) rs_resolve_aa<TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+    if (BRDF) rs_resolve_brdf<S, TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
+    else if (S == 4) rs_resolve_aa<TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
     else rs_resolve<TEX, MIP, SMOOTH>(m, cam, views, H, W, npix, fx, fy, znear, keys, image, visibility);
 }
 
@@ -705,14 +899,14 @@ typedef void (*RsResolve)(MeshBatch, const float*, int, int, int, long, float, f
 
 // THE launch sequence: clear, faces, queue, resolve, with `samples` keys per pixel (1 or 4).  A batch without textures (T == 0) takes
 // the plain resolve whatever the mode: mb_face_tex finds no texture in it.  A batch with corner normals (m.face_vn) takes the SMOOTH
-// resolve of its mode; the three passes before it are the same kernels either way.
+// resolve of its mode, one with PBR factors (m.mat_pbr) the BRDF resolve; the three passes before it are the same kernels either way.
 static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
                      void* workspace, uint8_t* image, int* visibility, void* stream, const char* who) {
-    static const RsResolve resolve[2][2][3] = {
-        {{raster_resolve_kernel<1, false, false, false>, raster_resolve_kernel<1, true, false, false>, raster_resolve_kernel<1, true, true, false>},
-         {raster_resolve_kernel<4, false, false, false>, raster_resolve_kernel<4, true, false, false>, raster_resolve_kernel<4, true, true, false>}},
-        {{raster_resolve_kernel<1, false, false, true>, raster_resolve_kernel<1, true, false, true>, raster_resolve_kernel<1, true, true, true>},
-         {raster_resolve_kernel<4, false, false, true>, raster_resolve_kernel<4, true, false, true>, raster_resolve_kernel<4, true, true, true>}}};
+#define RS_MODES(S, SMOOTH, BRDF) \
+    {raster_resolve_kernel<S, false, false, SMOOTH, BRDF>, raster_resolve_kernel<S, true, false, SMOOTH, BRDF>, raster_resolve_kernel<S, true, true, SMOOTH, BRDF>}
+    static const RsResolve resolve[2][2][2][3] = {{{RS_MODES(1, false, false), RS_MODES(4, false, false)}, {RS_MODES(1, true, false), RS_MODES(4, true, false)}},
+                                                  {{RS_MODES(1, false, true), RS_MODES(4, false, true)}, {RS_MODES(1, true, true), RS_MODES(4, true, true)}}};
+#undef RS_MODES
     const int N = m.N;
     const int bad = rs_check(N, sumF, views, H, W, yfov, znear, samples, who);
     if (bad != TRI_OK) return bad;
@@ -736,7 +930,7 @@ static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam
         (aa ? raster_queue_kernel<4> : raster_queue_kernel<1>)<<<RS_QUEUE_BLOCKS, RS_THREADS, 0, st>>>(m, cam, views, H, W, fx, fy, zn, keys, qcount,
                                                                                                        queue, qcap);
     }
-    resolve[m.face_vn != nullptr][aa][m.T > 0 ? mode : RS_PLAIN]<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy,
+    resolve[m.mat_pbr != nullptr][m.face_vn != nullptr][aa][m.T > 0 ? mode : RS_PLAIN]<<<(unsigned)((npix + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(m, cam, views, H, W, npix, fx, fy,
                                                                                                                     zn, keys, image, visibility);
     return tri_check_launch(who);
 }
@@ -821,6 +1015,26 @@ extern "C" int tri_raster_render_smooth(const float* verts, const int* faces, co
     if (bad != TRI_OK) return bad;
     const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
                       (const unsigned*)mip_texels, mip_off, face_vn};
+    return rs_render(m, pyramid ? RS_MIP : RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
+}
+
+extern "C" int tri_raster_render_brdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
+                                      const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
+                                      const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
+                                      const float* face_vn, const float* mat_pbr, const float* cam, int N, long sumF, int views, int H, int W,
+                                      double yfov, double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const char* who = "tri_raster_render_brdf";
+    if (!mat_pbr) { tri_set_error("tri_raster_render_brdf: mat_pbr must not be null"); return TRI_ERR_ARG; }
+    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_brdf: samples must be 1 or 4"); return TRI_ERR_ARG; }
+    if (T > 0 && (mip_texels != nullptr) != (mip_off != nullptr)) {         // T == 0: an empty pyramid may be null, nothing is textured
+        tri_set_error("tri_raster_render_brdf: the two pyramid fields come together or not at all");
+        return TRI_ERR_ARG;
+    }
+    const bool pyramid = mip_texels && mip_off;
+    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, pyramid);
+    if (bad != TRI_OK) return bad;
+    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
+                      (const unsigned*)mip_texels, mip_off, face_vn, mat_pbr};
     return rs_render(m, pyramid ? RS_MIP : RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 

@@ -1,7 +1,8 @@
 """Per-face diffuse colours of a Wavefront OBJ: the `usemtl` groups of the file and the `Kd` of the `mtllib` files next to it,
 as far as the renderer of data/render.py uses them.  load_obj_materials ignores map_Kd textures (and every other MTL statement);
 load_obj_textured also reads the `vt` texture coordinates and decodes the map_Kd images for ops.render_views_textured;
-load_obj_normals reads the `vn` normals of the face corners for the smooth shading of ops.render_views(..., normals=)."""
+load_obj_normals reads the `vn` normals of the face corners for the smooth shading of ops.render_views(..., normals=);
+load_obj_pbr reads the `Ns` of the materials for the metallic-roughness BRDF of ops.render_views(..., brdf=)."""
 from __future__ import annotations
 
 import math
@@ -13,6 +14,8 @@ import torch
 from ..meshes import load_obj
 
 DEFAULT_KD = (0.4, 0.4, 0.4)
+DEFAULT_PBR = (0.2, 0.8)                            # (metallic, roughness) of material 0, the default grey
+DEFAULT_NS = 1.0                                    # the specular exponent of a material without a usable Ns
 
 
 def load_mtl(path):
@@ -104,6 +107,55 @@ def load_obj_normals(path):
     if face_vn.shape[0] != faces.shape[0]:
         raise ValueError(f"{path}: {face_vn.shape[0]} normal rows for {faces.shape[0]} faces")
     return face_vn
+
+
+def load_mtl_ns(path):
+    """-> {name: Ns} in file order: the specular exponent of every material, DEFAULT_NS for one without a usable `Ns` line - absent,
+    unparsable, negative or not finite.  As for Kd, the lines of a material's first `newmtl` and of its later ones both count, the last
+    usable one wins."""
+    out = {}
+    name = None
+    with open(path, "rb") as f:
+        for ln in f.read().replace(b"\r", b"").split(b"\n"):
+            tok = ln.split()
+            if len(tok) >= 2 and tok[0] == b"newmtl":
+                name = b" ".join(tok[1:]).decode(errors="replace")
+                out.setdefault(name, DEFAULT_NS)
+            elif len(tok) >= 2 and tok[0] == b"Ns" and name is not None:
+                try:
+                    ns = float(tok[1])
+                except ValueError:
+                    continue
+                if math.isfinite(ns) and ns >= 0.0:
+                    out[name] = ns
+    return out
+
+
+def ns_to_roughness(ns):
+    """(2 / (Ns + 2)) ^ (1 / 4) in float64, as two square roots, rounded to fp32: the roughness a specular exponent stands for."""
+    return float(np.float32(math.sqrt(math.sqrt(2.0 / (float(ns) + 2.0)))))
+
+
+def load_obj_pbr(path, metallic=1.0):
+    """-> pbr float32 [M, 2] = (metallic, roughness) of the materials of load_obj_materials(path), in its order: what
+    MeshBatch.pack(..., pbr_list=) takes for the BRDF of ops.render_views(..., brdf=).  roughness = ns_to_roughness(Ns) with the Ns of
+    the material's MTL definition (the first mtllib file that defines the name counts, as for Kd), Ns = 1 without a usable one;
+    metallic is one number for all parsed materials.  Material 0, the default grey named None, is DEFAULT_PBR = (0.2, 0.8).  This is
+    what pyrender is believed - from memory, checked by nobody - to make of a trimesh SimpleMaterial (data/render.py)."""
+    names = load_obj_materials(path)[4]
+    with open(path, "rb") as f:
+        lines = [ln.strip() for ln in f.read().replace(b"\r", b"").split(b"\n")]
+    here = os.path.dirname(os.path.abspath(path))
+    ns = {}
+    for ln in lines:
+        if ln[:7] in (b"mtllib ", b"mtllib\t"):
+            for lib in ln.split()[1:]:
+                lib_path = os.path.join(here, lib.decode(errors="replace"))
+                if os.path.isfile(lib_path):
+                    for name, value in load_mtl_ns(lib_path).items():
+                        ns.setdefault(name, value)
+    rows = [DEFAULT_PBR] + [(float(metallic), ns_to_roughness(ns.get(name, DEFAULT_NS))) for name in names[1:]]
+    return torch.from_numpy(np.asarray(rows, dtype=np.float32).reshape(-1, 2))
 
 
 def load_mtl_textures(path):

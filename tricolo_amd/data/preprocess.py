@@ -3,7 +3,7 @@ splits, without pyrender, trimesh, pynrrd, Hydra or Lightning.
 
     python -m tricolo_amd.data.preprocess data=text2shape_chair_table data.dataset_root_path=/path/to/data \\
         [--batch-meshes 8] [--jpeg-roundtrip] [--device cuda] [--voxels nrrd|mesh|auto] [--textures off|on|mip] [--antialias off|4x] \\
-        [--shading flat|smooth]
+        [--shading flat|smooth] [--brdf lambert|gltf] [--metallic 1.0]
 
 It writes the files tricolo_amd.data.dataset.PackedDataset (and the reference's own loader) read: `{split}_map.json` at
 cfg.data.{split}_lang_data_path - the list of {model_id, category, caption, tokens} from processed_captions_{split}.p and
@@ -11,7 +11,7 @@ shapenet.json; for Text2ShapeC13 the existing map file is read instead - and `<e
 with voxel32 / voxel64 / voxel128 (uint8 [4, V, V, V]) and images (uint8 [cfg.data.num_views, 3, 224, 224]).  The images are rendered from
 `<dirname(dataset_path)>/ShapeNetCore.v2/<category>/<model_id>/models/model_normalized.obj` by ops.render_views (csrc/raster.hip), a
 batch of meshes per call.  data/render.py says what that renderer restates of the reference's pyrender scene, what it deliberately
-does differently (Lambert shading, flat normals unless asked otherwise, no culling, textures only on request) and that no pixel has
+does differently (Lambert shading and flat normals unless asked otherwise, no culling, textures only on request) and that no pixel has
 been compared with pyrender's.
 
 --textures on (the default is off: a textured material renders with its bare Kd) reads the `vt` coordinates and the map_Kd images
@@ -41,6 +41,14 @@ with vn and the faces that took computed normals.  It rests on our unverified re
 meshes smoothly by default and that trimesh keeps a file's vn; the area weighting (trimesh: angle weighting) and the turn toward
 the eye at every position are our own (data/render.py).
 
+--brdf gltf (the default is lambert: Kd (0.1 + 3/pi max(n . l, 0))) colours every pixel - with --antialias 4x, every sample - with
+the glTF 2.0 metallic-roughness BRDF, ops.render_views(..., brdf=): the materials' roughness comes from their `Ns`
+(data/materials.py load_obj_pbr: (2 / (Ns + 2))^(1/4), Ns = 1 without a usable one), their metallic factor is --metallic (default
+1.0; only meaningful with gltf), the default grey material takes (0.2, 0.8).  It works with every --textures, --antialias and
+--shading choice and with --device cpu, and leaves the voxels and the .npz layout alone.  It rests on our unverified readings, from
+memory, of how pyrender converts a trimesh SimpleMaterial and of its fragment shader (data/render.py); the metallic factor is the
+least certain part, hence --metallic.  No pixel has been compared with pyrender's.
+
 --voxels says where the grids come from.  nrrd (the default): Text2Shape's nrrd_256_filter_div_{V}_solid/<id>/<id>.nrrd downloads
 (data/nrrd.py), which exist for chairs and tables only.  mesh: ops.voxelize_meshes (csrc/voxelize.hip) voxelises the meshes already
 loaded for the renderer, one call per size for the whole batch, so that Text2ShapeC13 or one's own meshes get their grids too.
@@ -68,7 +76,7 @@ import torch
 from .. import config as tcfg
 from ..meshes import MeshBatch
 from . import render, voxelize
-from .materials import load_obj_materials, load_obj_normals, load_obj_textured
+from .materials import load_obj_materials, load_obj_normals, load_obj_pbr, load_obj_textured
 from .nrrd import read_nrrd
 
 VOXEL_SIZES = (32, 64, 128)
@@ -77,6 +85,7 @@ VOXEL_SOURCES = ("nrrd", "mesh", "auto")
 TEXTURE_MODES = ("off", "on", "mip")
 ANTIALIAS_MODES = {"off": 1, "4x": 4}                # --antialias -> samples per pixel
 SHADING_MODES = render.SHADING_MODES                 # ("flat", "smooth")
+BRDF_MODES = render.BRDF_MODES                       # ("lambert", "gltf")
 
 
 def create_model_id_caption_mapping(caption_file_path, id_word_file_path, output_json_path, ignored_models):
@@ -128,19 +137,21 @@ def nrrd_path(data_root, mid, v):
     return os.path.join(data_root, f"nrrd_256_filter_div_{v}_solid", mid, f"{mid}.nrrd")
 
 
-def pack_batch(meshes, device, textures=False, face_vn_list=None):
+def pack_batch(meshes, device, textures=False, face_vn_list=None, pbr_list=None):
     """MeshBatch.pack of load_obj_materials' (or, with textures, load_obj_textured's) tuples; with textures the voxeliser's batch too.
     textures="mip": the packed batch carries the mip pyramid of its textures, built here, once per batch.  face_vn_list
     (load_obj_normals of the same files): the renderer's batch carries them, completed by computed vertex normals once per batch; the
-    voxeliser's batch is what it is without them."""
+    voxeliser's batch is what it is without them.  pbr_list (load_obj_pbr of the same files): the renderer's batch carries the
+    materials' (metallic, roughness); the voxeliser does not read them."""
     from dataclasses import replace
     if not textures:
-        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_vn_list=face_vn_list)
+        packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_vn_list=face_vn_list, pbr_list=pbr_list)
         solid = packed if face_vn_list is None else replace(packed, face_vn=None)
     else:
         from .. import ops
         packed = MeshBatch.pack(*zip(*(m[:4] for m in meshes)), device=device, face_uv_list=[m[5] for m in meshes],
-                                mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes], face_vn_list=face_vn_list)
+                                mat_tex_list=[m[6] for m in meshes], textures_list=[m[7] for m in meshes], face_vn_list=face_vn_list,
+                                pbr_list=pbr_list)
         solid = packed.with_face_colours(ops.mesh_face_colours(packed))
         if textures == "mip":
             packed = packed.with_texture_mips()
@@ -150,16 +161,19 @@ def pack_batch(meshes, device, textures=False, face_vn_list=None):
 
 
 def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_meshes=8, roundtrip=False, log=print, voxels="nrrd",
-                textures=False, texture_stats=None, samples=1, shading="flat", normal_stats=None):
+                textures=False, texture_stats=None, samples=1, shading="flat", normal_stats=None, brdf="lambert", metallic=1.0):
     """Render and pack every (category, model_id) of `keys` that has no .npz yet -> (written, skipped).  voxels: where the grids
     come from - "nrrd" (the downloaded files), "mesh" (ops.voxelize_meshes) or "auto" (the files where all three exist).
     textures: read and render map_Kd textures, and colour mesh voxels from them ("mip": render them mip-mapped); texture_stats, a dict, then gains the number of
     "textured_models" (at least one texture loaded) and of "texture_failures" (map_Kd files that could not be loaded).
     samples: coverage samples per pixel, 1 or 4 (render.render_batch).  shading="smooth": read the `vn` normals, complete them with
     computed vertex normals and render smooth-shaded; normal_stats, a dict, then gains the number of "faces_with_vn" (rendered with
-    the file's normals) and of "faces_with_computed_normals"."""
+    the file's normals) and of "faces_with_computed_normals".  brdf="gltf": read the materials' Ns (load_obj_pbr, with `metallic` as
+    their metallic factor) and render with the metallic-roughness BRDF."""
     if shading not in SHADING_MODES:
         raise ValueError(f"shading must be one of {SHADING_MODES}, got {shading!r}")
+    if brdf not in BRDF_MODES:
+        raise ValueError(f"brdf must be one of {BRDF_MODES}, got {brdf!r}")
     todo = [k for k in keys if not os.path.exists(os.path.join(out_root, k[0], f"{k[1]}.npz"))]
     load = load_obj_textured if textures else load_obj_materials
     for i in range(0, len(todo), batch_meshes):
@@ -171,13 +185,17 @@ def pack_models(keys, obj_root, data_root, out_root, num_views, device, batch_me
         normals = None
         if shading == "smooth":
             normals = [load_obj_normals(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj")) for cat, mid in batch]
-        packed, solid = pack_batch(meshes, device, textures, normals)
+        pbr = None
+        if brdf == "gltf":
+            pbr = [load_obj_pbr(os.path.join(obj_root, cat, mid, "models", "model_normalized.obj"), metallic) for cat, mid in batch]
+        packed, solid = pack_batch(meshes, device, textures, normals, pbr)
         if normals is not None and normal_stats is not None:
             given = sum(int((~torch.isnan(vn[:, 0, 0])).sum()) for vn in normals)
             normal_stats["faces_with_vn"] = normal_stats.get("faces_with_vn", 0) + given
             normal_stats["faces_with_computed_normals"] = (normal_stats.get("faces_with_computed_normals", 0)
                                                            + int((~torch.isnan(packed.face_vn[:, 0, 0])).sum()) - given)
-        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures, samples=samples, shading=shading).cpu().numpy()
+        images = render.render_batch(packed, num_views, render.IMAGE_SIZE, textures=textures, samples=samples, shading=shading,
+                                     brdf=brdf).cpu().numpy()
         from_mesh = [k for k, (_, mid) in enumerate(batch) if voxels == "mesh" or
                      (voxels == "auto" and not all(os.path.exists(nrrd_path(data_root, mid, v)) for v in VOXEL_SIZES))]
         if 0 < len(from_mesh) < len(batch):                  # only some models lack their NRRD files: that subset, packed once for the three sizes
@@ -215,6 +233,9 @@ def main(argv=None, log=print):
                     "the pixel their rounded mean; off: visibility at the pixel centre alone")
     ap.add_argument("--shading", choices=SHADING_MODES, default="flat", help="smooth: interpolate the models' vn normals, and computed vertex "
                     "normals where a face has none (ops.mesh_vertex_normals), across every face; flat: the normal of the face")
+    ap.add_argument("--brdf", choices=BRDF_MODES, default="lambert", help="gltf: the glTF metallic-roughness BRDF, roughness from the materials' "
+                    "Ns (ops.render_views(..., brdf=)); lambert: Kd (0.1 + 3/pi max(n . l, 0))")
+    ap.add_argument("--metallic", type=float, default=1.0, help="the metallic factor of every parsed material under --brdf gltf")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.batch_meshes < 1:
         ap.error("--batch-meshes must be positive")
@@ -234,7 +255,7 @@ def main(argv=None, log=print):
         nrm = {"faces_with_vn": 0, "faces_with_computed_normals": 0} if args.shading == "smooth" else {}
         written, skipped = pack_models(keys, obj_root, data.dataset_path, data.exp_data_root_path, int(data.num_views), args.device,
                                        args.batch_meshes, args.jpeg_roundtrip, log, args.voxels, {"off": False, "on": True, "mip": "mip"}[args.textures], tex,
-                                       ANTIALIAS_MODES[args.antialias], args.shading, nrm)
+                                       ANTIALIAS_MODES[args.antialias], args.shading, nrm, args.brdf, args.metallic)
         stats[split] = {"models": len(keys), "written": written, "skipped": skipped, **tex, **nrm}
         log(f"  {len(keys)} models: {written} written, {skipped} already there")
         if tex:

@@ -9,7 +9,20 @@ Scene.centroid and scene.cameras.look_at (one point, a given distance) comes fro
 are not installed where this was written: NOBODY HAS COMPARED A PIXEL OF THIS RENDERER WITH PYRENDER'S OUTPUT.
 
 Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliberate differences:
-  * Lambert diffuse plus ambient, Kd (0.1 + 3/pi max(n . l, 0)), instead of pyrender's metallic-roughness BRDF;
+  * Lambert by default; the glTF BRDF on request.  The default is Lambert diffuse plus ambient, Kd (0.1 + 3/pi max(n . l, 0)).
+    brdf= of ops.render_views and ops.render_views_textured (brdf="gltf" below, --brdf gltf of data/preprocess.py) colours every
+    position - the pixel centre, with samples=4 each sample - with the glTF 2.0 metallic-roughness model instead: base = Kd (times
+    the texel), F0 = 0.04 + (base - 0.04) m, cdiff = 0.96 base (1 - m), Schlick's F, the Smith-GGX G and the GGX D with alpha = r^2,
+    colour = clamp(0.1 base + 3 NL ((1 - F) cdiff / pi + F G D / (4 NL NV)), 0, 1), the view vector from the world position on the
+    face, the normal flat or smooth as above (head of csrc/raster.hip).  The BRDF formulas are the glTF 2.0 specification's, which is
+    public.  What rests ON MEMORY and has been checked by nobody, neither trimesh nor pyrender being installed where this was
+    written: **material conversion** - that pyrender turns a trimesh SimpleMaterial into a MetallicRoughnessMaterial with
+    baseColorFactor = the diffuse colour, baseColorTexture = the image, roughnessFactor = (2 / (Ns + 2))^(1/4) with Ns defaulting to
+    1, and metallicFactor left at its default 1.0 (the least certain part, hence --metallic; with it the images carry almost no
+    diffuse term, a face turned away from the light shows only the ambient tenth of its colour and an upward face a broad
+    highlight); **default material** - that its default material is grey 0.4, metallic 0.2, roughness 0.8; **fragment shader** -
+    that it follows the Khronos glTF-WebGL-PBR reference shader with the clamps NL, NV in [0.001, 1] and NH, VH in [0, 1], radiance =
+    intensity times colour, ambient times base colour added, no gamma.  NOBODY HAS COMPARED A PIXEL WITH PYRENDER'S OUTPUT;
   * flat face normals by default, turned toward the eye.  Smooth shading is opt-in (normals= of ops.render_views and
     ops.render_views_textured, shading="smooth" below, --shading smooth of data/preprocess.py): the corner normals of the batch - the
     `vn` lines of the OBJ file (data/materials.py load_obj_normals) and, for faces without, vertex normals computed by
@@ -45,7 +58,8 @@ Geometry is what is pinned; colour fidelity to pyrender is not claimed.  Deliber
 
 On GPU tensors ops.render_views launches the HIP kernels; on CPU tensors the same call runs render_views_cpu below, a torch
 restatement of the kernel's arithmetic (spelled out at the head of csrc/raster.hip) that gives the same bits.  It exists for
-checking and for machines without a GPU and is not tuned.  ops.render_views_textured and ops.mesh_face_colours have theirs here too.
+checking and for machines without a GPU and is not tuned.  ops.render_views_textured and ops.mesh_face_colours have theirs here too,
+and so has the BRDF (_brdf_one).
 """
 from __future__ import annotations
 
@@ -398,14 +412,115 @@ def _shade_one(verts, faces, face_mat, kd, cam, vis, tex=None, smooth=None):
     return out
 
 
+PI32 = float(np.float32(math.pi))                                                  # csrc/raster.hip RS_PI
+DEFAULT_PBR = (0.2, 0.8)                                                            # (metallic, roughness) of a mesh without materials
+
+
+def _clamp(x, lo, hi):
+    """fminf(fmaxf(x, lo), hi): a NaN takes the lower bound (torch.clamp would keep it)."""
+    return torch.fmin(torch.fmax(x, _f32(lo)), _f32(hi))
+
+
+def face_pbr(face_mat, pbr):
+    """(metallic, roughness) fp32 [F] each: csrc/mesh_batch.h mb_face_pbr - the factors of every face's (clamped) material, clamped
+    to [0, 1] and [0.04, 1] with a NaN taking the lower bound; DEFAULT_PBR for a mesh without materials."""
+    if pbr.shape[0] > 0:
+        mr = pbr[clamp_index(face_mat, pbr.shape[0])]
+    else:
+        mr = torch.tensor(DEFAULT_PBR, dtype=torch.float32).expand(face_mat.shape[0], 2)
+    return _clamp(mr[:, 0], 0.0, 1.0), _clamp(mr[:, 1], 0.04, 1.0)
+
+
+def _brdf_one(verts, faces, face_mat, kd, pbr, cam, H, W, yfov, znear, vis, tex=None, face_vn=None, offsets=CENTRE):
+    """u8 [3, HW S] of one mesh and one view from its visibility buffer vis int64 [HW S] under the metallic-roughness BRDF (head of
+    csrc/raster.hip, rs_resolve_brdf): every entry coloured at its own position.  pbr: the mesh's rows of mat_pbr; tex: _texels_one's
+    pair; face_vn: the mesh's corner normals for the smooth normal, or None.  Where the BRDF falls back the entry takes the Lambert
+    colour of _shade_one."""
+    out = torch.full((3, vis.numel()), 255, dtype=torch.uint8)
+    pix = torch.nonzero(vis >= 0).reshape(-1)
+    if pix.numel() == 0:
+        return out
+    f = vis[pix]
+    eye = cam[:3]
+    corner = verts[faces[f]]                                                        # [P, 3, 3]
+    a = corner[:, 0]
+    e = eye - a
+
+    def turned(x, length, has_length):
+        side = (x[0] * e[:, 0] + x[1] * e[:, 1]) + x[2] * e[:, 2]
+        safe = torch.where(has_length, length, torch.ones_like(length))
+        unit = [torch.where(has_length, xj / safe, torch.zeros_like(xj)) for xj in x]
+        return torch.stack([torch.where(side < 0, -u, u) for u in unit], dim=1)
+
+    x = cross(a, corner[:, 1], corner[:, 2])
+    length = torch.sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])
+    n = turned(x, length, length > 0)
+    good = (length > 0) & torch.isfinite(length)
+
+    keep, X, Y, d, A2, order = project_faces(verts, faces, cam, H, W, yfov, znear, with_order=True)
+    S, off = len(offsets), torch.tensor(offsets, dtype=torch.int64)
+    pixel, s = torch.div(pix, S, rounding_mode="floor"), pix % S
+    Px, Py = 256 * (pixel % W) + off[s, 0], 256 * torch.div(pixel, W, rounding_mode="floor") + off[s, 1]
+    bw, _ = _weights(X, Y, d, A2[f].to(torch.float32), f, Px, Py)
+    if face_vn is not None:
+        vn = face_vn[f].gather(1, order[f][:, :, None].expand(-1, 3, 3))
+        y = [(bw[0] * vn[:, 0, j] + bw[1] * vn[:, 1, j]) + bw[2] * vn[:, 2, j] for j in range(3)]
+        ylen = torch.sqrt((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2])
+        has = keep[f] & ~torch.isnan(face_vn[f, 0, 0]) & torch.isfinite(y[0]) & torch.isfinite(y[1]) & torch.isfinite(y[2]) & (ylen != 0)
+        n = torch.where(has[:, None], turned(y, ylen, has), n)
+        good = torch.where(has, torch.isfinite(ylen), good)
+
+    base = face_kd(face_mat[f], kd)
+    if tex is not None:
+        base = torch.where(tex[0][pix][:, None], base * tex[1][pix], base)
+    shade = 0.1 + _f32(KDIFF) * torch.fmax(n[:, 1], _f32(0.0))
+    lambert = _clamp(base * shade[:, None], 0.0, 1.0)
+
+    P = corner.gather(1, order[f][:, :, None].expand(-1, 3, 3))                     # the corners in the swapped order
+    q = [eye[j] - ((bw[0] * P[:, 0, j] + bw[1] * P[:, 1, j]) + bw[2] * P[:, 2, j]) for j in range(3)]
+    dist = torch.sqrt((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2])
+    ok = keep[f] & good & torch.isfinite(bw[0]) & torch.isfinite(bw[1]) & torch.isfinite(bw[2]) & (dist > 0) & torch.isfinite(dist)
+    v = [qj / torch.where(ok, dist, torch.ones_like(dist)) for qj in q]
+    g = [v[0], 1.0 + v[1], v[2]]
+    hl = torch.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+    ok = ok & (hl > 0) & torch.isfinite(hl)
+    h = [gj / torch.where(ok, hl, torch.ones_like(hl)) for gj in g]
+    NL = _clamp(n[:, 1], 0.001, 1.0)
+    NV = _clamp(((n[:, 0] * v[0] + n[:, 1] * v[1]) + n[:, 2] * v[2]).abs(), 0.001, 1.0)
+    NH = _clamp((n[:, 0] * h[0] + n[:, 1] * h[1]) + n[:, 2] * h[2], 0.0, 1.0)
+    VH = _clamp((v[0] * h[0] + v[1] * h[1]) + v[2] * h[2], 0.0, 1.0)
+    w = 1.0 - VH
+    w5 = (((w * w) * w) * w) * w
+    metal, rough = face_pbr(face_mat[f], pbr)
+    alpha = rough * rough
+    a2 = alpha * alpha
+
+    def smith(c):
+        return (2.0 * c) / (c + torch.sqrt(a2 + (1.0 - a2) * (c * c)))
+
+    G = smith(NL) * smith(NV)
+    t = (NH * NH) * (a2 - 1.0) + 1.0
+    D = a2 / ((_f32(PI32) * t) * t)
+    spec = ((G * D) / ((4.0 * NL) * NV))[:, None]
+    light = (3.0 * NL)[:, None]
+    F0 = 0.04 + (base - 0.04) * metal[:, None]
+    cdiff = (0.96 * base) * (1.0 - metal)[:, None]
+    F = F0 + (1.0 - F0) * w5[:, None]
+    colour = _clamp(0.1 * base + light * (((1.0 - F) * cdiff) / _f32(PI32) + F * spec), 0.0, 1.0)
+    rgb = torch.floor(255.0 * torch.where(ok[:, None], colour, lambert) + 0.5).to(torch.uint8)
+    out[:, pix] = rgb.t()
+    return out
+
+
 def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=YFOV, znear=ZNEAR,
-                     return_visibility=False, textures=None, samples=1, mips=None, normals=None):
+                     return_visibility=False, textures=None, samples=1, mips=None, normals=None, brdf=None):
     """ops.render_views on CPU tensors: one mesh and one view after the other, the kernel's arithmetic in torch.  textures: the five
     texture tensors of the batch (face_uv, mat_tex, texels, tex_off, tex_size) for ops.render_views_textured.  samples=4: coverage,
     depth and colour at the four SAMPLE_OFFSETS of every pixel, the pixel their rounded integer mean (c0 + c1 + c2 + c3 + 2) >> 2 per
     channel, the visibility int32 [N, views, H, W, 4].  mips: the pyramid pair (texture_mips_cpu) for the mip-mapped colours of
     ops.render_views_textured(..., mips=).  normals: the batch's corner normals face_vn fp32 [sumF, 3, 3] for the smooth shade of
-    ops.render_views(..., normals=) - interpolated at every sample's own position - in any of those modes."""
+    ops.render_views(..., normals=) - interpolated at every sample's own position - in any of those modes.  brdf: the batch's PBR
+    factors mat_pbr fp32 [sumM, 2] for the metallic-roughness colours of ops.render_views(..., brdf=), in any of those modes."""
     if samples not in (1, 4):
         raise ValueError(f"render_views_cpu: samples must be 1 or 4, got {samples!r}")
     offsets = SAMPLE_OFFSETS if samples == 4 else CENTRE
@@ -430,10 +545,12 @@ def render_views_cpu(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off
                 uv = face_uv[foff[n]:foff[n + 1]]
                 face_t = face_textures(fm, mat_tex[moff[n]:moff[n + 1]], uv, tex_size.shape[0])
                 tex = _texels_one(v, f, cam[n, k], H, W, yfov, znear, face, face_t, uv, texels, tex_off, tex_size, offsets, mips)
-            smooth = None
-            if normals is not None:
-                smooth = _smooth_one(v, f, cam[n, k], H, W, yfov, znear, face, normals[foff[n]:foff[n + 1]], offsets)
-            colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex, smooth)
+            vn = None if normals is None else normals[foff[n]:foff[n + 1]]
+            if brdf is not None:
+                colour = _brdf_one(v, f, fm, kd, brdf[moff[n]:moff[n + 1]], cam[n, k], H, W, yfov, znear, face, tex, vn, offsets)
+            else:
+                smooth = None if vn is None else _smooth_one(v, f, cam[n, k], H, W, yfov, znear, face, vn, offsets)
+                colour = _shade_one(v, f, fm, kd, cam[n, k], face, tex, smooth)
             if samples == 4:
                 colour = ((colour.view(3, H * W, 4).to(torch.int32).sum(dim=2) + 2) >> 2).to(torch.uint8)
             image[n, k] = colour.view(3, H, W)
@@ -497,17 +614,21 @@ def mesh_vertex_normals_cpu(verts, faces, vert_off, face_off, face_vn=None, fill
 
 
 SHADING_MODES = ("flat", "smooth")
+BRDF_MODES = ("lambert", "gltf")
 
 
 # ------------------------------------------------------------------------------------------------ the convenient calls
-def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1, shading="flat"):
+def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=False, textures=False, samples=1, shading="flat",
+                 brdf="lambert"):
     """The reference's num_views renderings of every mesh of a meshes.MeshBatch packed with materials -> uint8
     [N, num_views, 3, S, S] on the batch's device: places the cameras around every mesh's bounding-box centre and calls
     ops.render_views, or with textures=True ops.render_views_textured (the batch must have been packed with textures).
     textures="mip": render_views_textured with the mip pyramid of the batch's textures, built here (MeshBatch.with_texture_mips)
     unless the batch carries one.  samples=4: four coverage samples per pixel (ops.render_views).  shading="smooth": the batch's
     corner normals batch.face_vn (MeshBatch.pack(..., face_vn_list=) and / or MeshBatch.with_vertex_normals()) are interpolated
-    across every face that has them (normals= of the two calls); a batch without face_vn raises."""
+    across every face that has them (normals= of the two calls); a batch without face_vn raises.  brdf="gltf": the glTF
+    metallic-roughness BRDF with the batch's PBR factors batch.mat_pbr (MeshBatch.pack(..., pbr_list=); brdf= of the two calls) in
+    place of the Lambert shade, in any of those modes; a batch without mat_pbr raises."""
     from .. import ops
     if not isinstance(textures, bool) and textures != "mip":
         raise ValueError(f"textures must be False, True or \"mip\", got {textures!r}")
@@ -516,7 +637,12 @@ def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=F
     if shading == "smooth" and batch.face_vn is None:
         raise ValueError("render_batch: shading=\"smooth\" needs corner normals - MeshBatch.pack(..., face_vn_list=) or "
                          "MeshBatch.with_vertex_normals()")
+    if brdf not in BRDF_MODES:
+        raise ValueError(f"brdf must be one of {BRDF_MODES}, got {brdf!r}")
+    if brdf == "gltf" and batch.mat_pbr is None:
+        raise ValueError("render_batch: brdf=\"gltf\" needs the materials' PBR factors - MeshBatch.pack(..., pbr_list=)")
     normals = batch.face_vn if shading == "smooth" else None
+    pbr = batch.pbr_tensor if brdf == "gltf" else None
     cam = pack_cameras(box_centers(batch.boxes), num_views, batch.verts.device)
     H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
     if textures:
@@ -526,18 +652,21 @@ def render_batch(batch, num_views=12, image_size=IMAGE_SIZE, return_visibility=F
                 raise ValueError("render_batch: the batch was packed without textures (MeshBatch.pack(..., face_uv_list=, mat_tex_list=, textures_list=))")
             mips = (batch if batch.mip_texels is not None else batch.with_texture_mips()).mip_tensors
         return ops.render_views_textured(*batch.tensors, *batch.texture_tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples,
-                                         mips=mips, normals=normals)
-    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples, normals=normals)
+                                         mips=mips, normals=normals, brdf=pbr)
+    return ops.render_views(*batch.tensors, cam, H, W, YFOV, ZNEAR, return_visibility, samples=samples, normals=normals, brdf=pbr)
 
 
 def render_meshes(verts_list, faces_list, face_mat_list, kd_list, num_views=12, image_size=IMAGE_SIZE, device=None, return_visibility=False,
-                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1, face_vn_list=None):
+                  textures=False, face_uv_list=None, mat_tex_list=None, textures_list=None, samples=1, face_vn_list=None, brdf="lambert",
+                  pbr_list=None):
     """render_batch of the lists, packed (meshes.MeshBatch.pack) on `device` (where verts_list[0] lives when None); textures=True
     and textures="mip" need the three texture lists of MeshBatch.pack.  face_vn_list (per mesh float32 [F, 3, 3], NaN rows for faces
     without; data.materials.load_obj_normals) turns smooth shading on: the faces without normals take computed ones
-    (MeshBatch.with_vertex_normals(fill="missing")) and the batch is rendered with shading="smooth"."""
+    (MeshBatch.with_vertex_normals(fill="missing")) and the batch is rendered with shading="smooth".  brdf="gltf" with pbr_list (per
+    mesh float32 [M, 2]; data.materials.load_obj_pbr) renders with the metallic-roughness BRDF."""
     batch = MeshBatch.pack(verts_list, faces_list, face_mat_list, kd_list, device, face_uv_list=face_uv_list, mat_tex_list=mat_tex_list,
-                           textures_list=textures_list, face_vn_list=face_vn_list)
+                           textures_list=textures_list, face_vn_list=face_vn_list, pbr_list=pbr_list)
     if face_vn_list is None:
-        return render_batch(batch, num_views, image_size, return_visibility, textures, samples)
-    return render_batch(batch.with_vertex_normals(fill="missing"), num_views, image_size, return_visibility, textures, samples, shading="smooth")
+        return render_batch(batch, num_views, image_size, return_visibility, textures, samples, brdf=brdf)
+    return render_batch(batch.with_vertex_normals(fill="missing"), num_views, image_size, return_visibility, textures, samples, shading="smooth",
+                        brdf=brdf)

@@ -195,7 +195,7 @@ def host_boxes(verts_list):
 class MeshBatch:
     """A packed batch on one device; the three material tensors are None for a batch packed without materials, the five texture
     tensors for a batch packed without textures, the two pyramid tensors until with_texture_mips() has built them, face_vn for a
-    batch packed without face_vn_list until with_vertex_normals() has computed it."""
+    batch packed without face_vn_list until with_vertex_normals() has computed it, mat_pbr for a batch packed without pbr_list."""
     verts: torch.Tensor
     faces: torch.Tensor
     vert_off: torch.Tensor
@@ -213,14 +213,17 @@ class MeshBatch:
     mip_texels: torch.Tensor | None = None          # the mip pyramid of the textures (with_texture_mips); None without one
     mip_off: torch.Tensor | None = None
     face_vn: torch.Tensor | None = None             # corner normals fp32 [sumF, 3, 3], a NaN row = a face without; None without any
+    mat_pbr: torch.Tensor | None = None             # (metallic, roughness) fp32 [sumM, 2] per material, indexed like mat_kd; None without
 
     @classmethod
     def pack(cls, verts_list, faces_list, face_mat_list=None, kd_list=None, device=None, *, face_uv_list=None, mat_tex_list=None,
-             textures_list=None, face_vn_list=None):
+             textures_list=None, face_vn_list=None, pbr_list=None):
         """pack_meshes, then pack_materials where face_mat_list and kd_list are given; device=None: where verts_list[0] lives.  With
         face_uv_list, mat_tex_list and textures_list (all three, beside the materials) pack_textures adds the texture fields,
         validated by check_textures.  face_vn_list: per mesh the corner normals float32 [F, 3, 3] (data.materials.load_obj_normals;
-        all nine values NaN for a face without), concatenated into face_vn."""
+        all nine values NaN for a face without), concatenated into face_vn.  pbr_list: per mesh the (metallic, roughness) of its
+        materials, float32 [M, 2] beside its Kd [M, 3] (data.materials.load_obj_pbr), concatenated into mat_pbr; the values are not
+        range-checked - the renderer clamps them."""
         verts, faces, voff, foff, max_faces = pack_meshes(verts_list, faces_list, device)
         mats = (None, None, None)
         if face_mat_list is not None:
@@ -249,7 +252,15 @@ class MeshBatch:
                 if not torch.is_tensor(vn) or vn.dtype != torch.float32 or tuple(vn.shape) != (f.shape[0], 3, 3):
                     raise ValueError(f"mesh {n}: face_vn must be a float32 tensor of shape [{f.shape[0]}, 3, 3]")
             face_vn = torch.cat([vn.to(verts.device) for vn in face_vn_list]).contiguous()
-        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list), *tex, face_vn=face_vn)
+        mat_pbr = None
+        if pbr_list is not None:
+            if face_mat_list is None or len(pbr_list) != len(faces_list):
+                raise ValueError("every mesh needs its pbr factors, and the materials they belong to")
+            for n, (pbr, kd) in enumerate(zip(pbr_list, kd_list)):
+                if not torch.is_tensor(pbr) or pbr.dtype != torch.float32 or tuple(pbr.shape) != (kd.shape[0], 2):
+                    raise ValueError(f"mesh {n}: pbr must be a float32 tensor of shape [{kd.shape[0]}, 2] = (metallic, roughness) per material")
+            mat_pbr = torch.cat([pbr.to(verts.device) for pbr in pbr_list]).contiguous()
+        return cls(verts, faces, voff, foff, *mats, max_faces, host_boxes(verts_list), *tex, face_vn=face_vn, mat_pbr=mat_pbr)
 
     @property
     def tensors(self):                              # the first seven arguments of ops.render_views and ops.voxelize_meshes, in their order
@@ -262,6 +273,10 @@ class MeshBatch:
     @property
     def mip_tensors(self):                          # the mips= pair of ops.render_views_textured, None for a batch without a pyramid
         return None if self.mip_texels is None else (self.mip_texels, self.mip_off)
+
+    @property
+    def pbr_tensor(self):                           # the brdf= argument of ops.render_views and ops.render_views_textured, None without pbr_list
+        return self.mat_pbr
 
     def with_texture_mips(self):
         """The batch with the mip pyramid of its textures (ops.texture_mips, built once on the batch's device; validated by
@@ -286,14 +301,22 @@ class MeshBatch:
 
     def with_face_colours(self, colours):
         """The batch with one material per face, `colours` fp32 [sumF, 3] (ops.mesh_face_colours) as their Kd, and no textures or
-        normals: what the voxeliser takes to colour its voxels from textures.  face_mat counts up within every mesh and mat_off = face_off."""
+        normals: what the voxeliser takes to colour its voxels from textures.  face_mat counts up within every mesh and mat_off = face_off;
+        mat_pbr, where the batch has it, becomes one row per face, that of the face's (clamped) material."""
         sumF = self.faces.shape[0]
         if not torch.is_tensor(colours) or colours.dtype != torch.float32 or tuple(colours.shape) != (sumF, 3) or colours.device != self.verts.device:
             raise ValueError(f"colours must be a float32 tensor of shape [{sumF}, 3] on the batch's device")
         counts = self.face_off[1:] - self.face_off[:-1]
         local = torch.arange(sumF, dtype=torch.int64, device=self.verts.device) - torch.repeat_interleave(self.face_off[:-1], counts)
+        mat_pbr = None
+        if self.mat_pbr is not None:
+            count = torch.repeat_interleave(self.mat_off[1:] - self.mat_off[:-1], counts)                 # the materials of every face's mesh
+            j = torch.minimum(self.face_mat.to(torch.int64) & 0xFFFFFFFF, (count - 1).clamp(min=0))      # the kernels' unsigned clamp
+            default = self.mat_pbr.new_tensor([[0.2, 0.8]])                                               # a mesh without materials
+            rows = torch.cat([self.mat_pbr, default])[(torch.repeat_interleave(self.mat_off[:-1], counts) + j).clamp(max=self.mat_pbr.shape[0])]
+            mat_pbr = torch.where((count > 0)[:, None], rows, default).contiguous()
         return MeshBatch(self.verts, self.faces, self.vert_off, self.face_off, local.to(torch.int32), colours.contiguous(), self.face_off.clone(),
-                         self.max_faces, self.boxes)
+                         self.max_faces, self.boxes, mat_pbr=mat_pbr)
 
 
 # ------------------------------------------------------------------------------------------------ shared by the torch restatements

@@ -1686,11 +1686,12 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
 RENDER_MAX_PIXELS = 2 ** 31                                                      # csrc/raster.hip RS_MAX_PIXELS: 16 GiB of visibility keys
 
 
-def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples, normals=None):
+def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples, normals=None, brdf=None):
     """The body of render_views and render_views_textured, whose own arguments are checked (batch: the seven tensors of the packed
     batch; textures: its five texture tensors, or None; mips: the checked pyramid pair, or None; normals: the checked face_vn, or
-    None): the camera, the limits, then the one entry point of csrc/raster.hip for the mode - tri_raster_render_smooth for every mode
-    with normals - or data.render.render_views_cpu on CPU tensors."""
+    None; brdf: the checked mat_pbr, or None): the camera, the limits, then the one entry point of csrc/raster.hip for the mode -
+    tri_raster_render_brdf for every mode with brdf, tri_raster_render_smooth for every other mode with normals - or
+    data.render.render_views_cpu on CPU tensors."""
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
     views, sumF, dev = cam.shape[1], batch[1].shape[0], batch[0].device
@@ -1705,7 +1706,7 @@ def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visi
     if not batch[0].is_cuda:
         from .data.render import render_views_cpu
         return render_views_cpu(*batch, cam, H, W, yfov, znear, return_visibility, textures=textures, samples=samples, mips=mips,
-                                normals=normals)
+                                normals=normals, brdf=brdf)
     image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=dev)
     vis = torch.empty((N, views, H, W) + ((4,) if samples == 4 else ()), dtype=torch.int32, device=dev) if return_visibility else None
     size = (lib().tri_raster_workspace_aa if samples == 4 else lib().tri_raster_workspace)(sumF, N, views, H, W)
@@ -1714,8 +1715,12 @@ def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visi
     tex = [ptr(x) for x in (textures or (None,) * 5)] + [textures[4].shape[0] if textures else 0]
     view = [ptr(cam), N, sumF, views, H, W, float(yfov), float(znear)]
     out = [ptr(ws), ptr(image), ptr(vis), stream()]
-    if normals is not None:
-        pyramid = [ptr(mips[0]), ptr(mips[1])] if mips is not None else [None, None]
+    pyramid = [ptr(mips[0]), ptr(mips[1])] if mips is not None else [None, None]
+    if brdf is not None:
+        if brdf.shape[0] == 0:                                                      # a batch without a material: no row is ever read, but the
+            brdf = brdf.new_zeros((1, 2))                                           # entry point takes a null mat_pbr for "no BRDF"
+        name, args = "tri_raster_render_brdf", mesh + tex + pyramid + [ptr(normals), ptr(brdf)] + view + [samples] + out
+    elif normals is not None:
         name, args = "tri_raster_render_smooth", mesh + tex + pyramid + [ptr(normals)] + view + [samples] + out
     elif mips is not None:
         name, args = "tri_raster_render_mip", mesh + tex + [ptr(mips[0]), ptr(mips[1])] + view + [samples] + out
@@ -1743,8 +1748,18 @@ def _mesh_normals(stage, faces, normals):
     return normals
 
 
+def _mesh_pbr(stage, mat_kd, brdf):
+    """Checks the PBR factors a call was given for its batch (csrc/mesh_batch.h mat_pbr; meshes.MeshBatch.mat_pbr) -> brdf."""
+    if not torch.is_tensor(brdf) or brdf.device != mat_kd.device:
+        raise ValueError(f"{stage}: brdf must be a tensor on the batch's device, {mat_kd.device}")
+    if brdf.dtype != torch.float32 or tuple(brdf.shape) != (mat_kd.shape[0], 2) or not brdf.is_contiguous():
+        raise ValueError(f"{stage}: brdf must be a contiguous float32 tensor of shape [{mat_kd.shape[0]}, 2] = (metallic, roughness) per "
+                         f"material, got {tuple(brdf.shape)} {brdf.dtype}" + ("" if brdf.is_contiguous() else " (not contiguous)"))
+    return brdf
+
+
 def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, cam, H, W, yfov=math.pi / 3, znear=0.05,
-                 return_visibility=False, samples=1, normals=None):
+                 return_visibility=False, samples=1, normals=None, brdf=None):
     """Render every mesh of a packed batch (meshes.MeshBatch.pack) from every camera -> images uint8 [N, views, 3, H, W], with
     return_visibility also int32 [N, views, H, W]: the face seen at each pixel centre, local to its mesh, -1 for background.
     face_mat int32 [sumF]: a material per face, local to the mesh; mat_kd fp32 [sumM, 3] diffuse colours with mat_off int64 [N + 1];
@@ -1763,14 +1778,22 @@ def render_views(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, ca
     position - the corner normals of the winning face are interpolated with the perspective-correct weights, the result is turned
     toward the eye and lit as the flat normal is (head of csrc/raster.hip).  A face without normals, and a position where the
     interpolated normal is not finite or has no length, is shaded flat, bit for bit; visibility never changes.  The turn toward the
-    eye at every position is this project's own rule.  normals=None, the default, is the call as it was."""
+    eye at every position is this project's own rule.  normals=None, the default, is the call as it was.
+    brdf=mat_pbr fp32 [sumM, 2] (meshes.MeshBatch.mat_pbr: metallic and roughness per material, indexed like mat_kd) replaces the
+    Lambert shade by the glTF 2.0 metallic-roughness BRDF: at every position the view vector comes from the world position on the
+    winning face, the normal is the flat or (with normals=) the smooth one, and the colour is clamp(0.1 base + 3 NL ((1 - F) cdiff /
+    pi + F G D / (4 NL NV)), 0, 1) with base = Kd (head of csrc/raster.hip).  Metallic is clamped to [0, 1] and roughness to [0.04, 1],
+    a NaN takes the lower bound, a mesh without materials takes (0.2, 0.8).  A position where the view or half vector has no length
+    takes the Lambert colour, bit for bit; visibility never changes.  brdf=None, the default, is the call as it was."""
     H, W = int(H), int(W)
     samples = _render_samples("render_views", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views")
     if normals is not None:
         normals = _mesh_normals("render_views", faces, normals)
+    if brdf is not None:
+        brdf = _mesh_pbr("render_views", mat_kd, brdf)
     return _render("render_views", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off), None, None, cam, H, W, yfov, znear,
-                   return_visibility, samples, normals)
+                   return_visibility, samples, normals, brdf)
 
 
 def _mesh_textures(stage, faces, mat_kd, face_uv, mat_tex, texels, tex_off, tex_size):
@@ -1844,7 +1867,7 @@ def _mesh_mips(stage, texels, tex_size, mips):
 
 
 def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off, tex_size, cam, H, W,
-                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1, mips=None, normals=None):
+                          yfov=math.pi / 3, znear=0.05, return_visibility=False, samples=1, mips=None, normals=None, brdf=None):
     """render_views with map_Kd textures: the packed batch and its five texture tensors (MeshBatch.tensors, MeshBatch.texture_tensors).
     face_uv fp32 [sumF, 3, 2]: one (u, v) per face corner, NaN in face_uv[f, 0, 0] = the face has none; mat_tex int32 [sumM]: a
     batch-global texture index per material, -1 = none; texels u8 [sumTexels, 4] RGBA; tex_off int64 [T + 1]; tex_size int32 [T, 2]
@@ -1860,7 +1883,9 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
     without mips, bit for bit; visibility never changes.  The rule is this project's own definition: no pixel of it has been compared
     with pyrender's mip-mapping.  mips=None, the default, is the call as it was.
     normals=face_vn: render_views' smooth shading, with or without mips and at either sample count; the texel is taken as before and
-    multiplies Kd, the smooth shade replaces the flat one.  normals=None, the default, is the call as it was."""
+    multiplies Kd, the smooth shade replaces the flat one.  normals=None, the default, is the call as it was.
+    brdf=mat_pbr: render_views' metallic-roughness BRDF in any of those modes; the base colour is Kd times the texel where the face is
+    textured.  brdf=None, the default, is the call as it was."""
     H, W = int(H), int(W)
     samples = _render_samples("render_views_textured", samples)
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, cam, stage="render_views_textured")
@@ -1869,8 +1894,10 @@ def render_views_textured(verts, faces, vert_off, face_off, face_mat, mat_kd, ma
         mips = _mesh_mips("render_views_textured", texels, tex_size, mips)
     if normals is not None:
         normals = _mesh_normals("render_views_textured", faces, normals)
+    if brdf is not None:
+        brdf = _mesh_pbr("render_views_textured", mat_kd, brdf)
     return _render("render_views_textured", N, (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off),
-                   (face_uv, mat_tex, texels, tex_off, tex_size), mips, cam, H, W, yfov, znear, return_visibility, samples, normals)
+                   (face_uv, mat_tex, texels, tex_off, tex_size), mips, cam, H, W, yfov, znear, return_visibility, samples, normals, brdf)
 
 
 VERTEX_NORMAL_FILL = {"missing": 0, "all": 1}
