@@ -136,6 +136,28 @@ def test_conv_fwd_mask_bias_act_stats():
     np.testing.assert_allclose(out3.numpy(), torch.tanh(cl3(F.conv3d(x, w, padding=1)).reshape(M, -1) + bias).numpy(), atol=2e-6)
 
 
+@pytest.mark.parametrize("precision,mode", [("bf16", 0), ("bf16x3", 1)])
+def test_conv_fwd_stats_from_the_unsplit_generic_kernel(precision, mode):
+    """The BatchNorm records conv_igemm_kernel's own epilogue writes (fp32 storage, no split-K: the small layers above are split over K
+    and get their records from conv_splitk_finish_kernel).  A 1x1x1 layer with two k-steps is never split (plan_generic asks for eight);
+    300 rows = two full 128-row tiles and a partial one, 192 channels = three 64-wide channel tiles.  |x| <= 2, |w| <= 1 over 64 inputs:
+    |out| <= 128, so a record's sum of squares is at most 128 * 128^2 = 2^21 - every fp32 sum is exact and the records must add up to the
+    float64 column sums exactly."""
+    M, cin, cout = 300, 64, 192
+    g = ops.ConvGeom(M, (1, 1, 1), cin, cin, cout, (1, 1, 1), 1, (0, 0, 0), (cin, 1, 1))
+    assert (g.kernel_family[(False, mode)] & 255) == 0 and not g.splitk(False, mode)
+    x = ints((M, cin), -2, 2, 91)
+    w = ints((cout, cin), -1, 1, 92)
+    ref = x @ w.t()
+    assert float(ref.abs().max()) <= 128
+    packed = ops.pack_weight(w.view(cout, cin, 1, 1, 1).to(DEV), g, precision, storage=torch.float32)
+    out, stats = ops.conv_fwd(x.view(M, 1, 1, 1, cin).to(DEV), g, packed, want_stats=True)
+    assert stats.shape == (g.num_mtiles[mode], 2, cout) and g.num_mtiles[mode] == 3
+    assert torch.equal(out.cpu().view(M, cout), ref)
+    st = stats.cpu().double().sum(0)
+    assert torch.equal(st[0], ref.double().sum(0)) and torch.equal(st[1], (ref.double() ** 2).sum(0))
+
+
 DGRAD_CASES = [c for c in CONV_CASES if c[3] != 3]
 
 

@@ -112,10 +112,6 @@ __global__ void bn_act_kernel(const T* __restrict__ y, const float4* __restrict_
         Act<T>::st4(out + i * 4, v);
     }
 }
-static inline int ew_grid(long total) {
-    long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
 extern "C" int tri_bn_act(const void* y, const float* scale, const float* shift, const void* res, const float* rscale,
                           const float* rshift, void* out, long M, int C, int relu, int act_fmt, void* stream) {
     if (C % 4) { tri_set_error("tri_bn_act: C must be a multiple of 4"); return TRI_ERR_ARG; }
@@ -1174,12 +1170,8 @@ __device__ __forceinline__ void stem_route_2x2(const uchar4* __restrict__ arg, c
 template <typename T>
 __device__ __forceinline__ float4 rnd4(float4 v) { return make_float4(Act<T>::rnd(v.x), Act<T>::rnd(v.y), Act<T>::rnd(v.z), Act<T>::rnd(v.w)); }
 
-// 2x2 blocks (4 positions each) per workgroup: 64 as bnb_rows of large tensors; tuning aid TRICOLO_STEM_BLOCKS
-static int stem_blocks_per_wg() {
-    static int v = -1;
-    if (v < 0) v = 64;
-    return v;
-}
+// 2x2 blocks (4 positions each) per workgroup: 64 as bnb_rows of large tensors
+static const int STEM_BLOCKS = 64;
 // 16-bit storage, C % 8 == 0: one thread = one 2x2 block of positions x EIGHT channels - 16-byte loads of y and the pooled gradient,
 // 8-byte loads of the tap map (the 4-channel form below moves 8 / 4 bytes per load and ran at 2.1 TB/s on the stem's 100 MB tensor).
 // Same routing, rounding, mask and summation order per channel as the 4-channel form.
@@ -1344,7 +1336,7 @@ __global__ void stem_bwd_apply_kernel(const T* __restrict__ y, const uchar4* __r
     }
 }
 extern "C" int tri_maxpool_bn_bwd_num_blocks(int N, int H, int W) {
-    const int per = stem_blocks_per_wg();
+    const int per = STEM_BLOCKS;
     return (int)(((long)N * (H / 2) * (W / 2) + per - 1) / per);
 }
 static int stem_args_ok(int H, int W, int C, const void* rs, const void* rb) {
@@ -1363,17 +1355,17 @@ extern "C" int tri_maxpool_bn_bwd_reduce(const void* y, const uint8_t* arg, cons
         const size_t smem8 = (size_t)rpp8 * tpr8 * 16 * sizeof(float);
         if (act_fmt == TRI_FMT_F16)
             stem_bwd_reduce8_kernel<f16_t><<<nblk, 256, smem8, (hipStream_t)stream>>>((const f16_t*)y, arg, (const f16_t*)dpool, N, H, W, C, partial,
-                                                                                     relu_scale, relu_shift, stem_blocks_per_wg());
+                                                                                     relu_scale, relu_shift, STEM_BLOCKS);
         else
             stem_bwd_reduce8_kernel<bf16_t><<<nblk, 256, smem8, (hipStream_t)stream>>>((const bf16_t*)y, arg, (const bf16_t*)dpool, N, H, W, C, partial,
-                                                                                      relu_scale, relu_shift, stem_blocks_per_wg());
+                                                                                      relu_scale, relu_shift, STEM_BLOCKS);
         return tri_check_launch("tri_maxpool_bn_bwd_reduce");
     }
     const int C4 = C / 4, tpr = C4 < 256 ? C4 : 256, rpp = 256 / tpr;
     const size_t smem = (size_t)rpp * tpr * 8 * sizeof(float);
     TRI_ACT_DISPATCH(act_fmt, stem_bwd_reduce_kernel<T><<<nblk, 256, smem, (hipStream_t)stream>>>(
         (const T*)y, (const uchar4*)arg, (const T*)dpool, N, H, W, C, partial, (const float4*)relu_scale, (const float4*)relu_shift,
-        stem_blocks_per_wg()));
+        STEM_BLOCKS));
     return tri_check_launch("tri_maxpool_bn_bwd_reduce");
 }
 // ---- the same two sums from the POOLED tensors (round 4) -----------------------------------------------------------------------

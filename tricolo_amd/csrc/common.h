@@ -39,6 +39,20 @@ static inline bool tri_env_read_is(const char* name, char c) { const char* e = g
 #define tri_env_int(name, dflt) ([]() -> int { static const int v = tri_env_read_int(name, dflt); return v; }())
 #define tri_env_is(name, c) ([]() -> bool { static const bool v = tri_env_read_is(name, c); return v; }())
 
+// ---- small host helpers -----------------------------------------------------------------------------------------
+// log2 of a power of two, -1 for anything else
+static inline int ilog2_exact(int v) {
+    for (int s = 0; s < 31; ++s) if ((1 << s) == v) return s;
+    return -1;
+}
+// workspace carving: sizes rounded up to 256 bytes
+static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+// grid of a grid-stride elementwise kernel of 256 threads: one thread per element up to 4096 workgroups
+static inline int ew_grid(long total) {
+    long b = (total + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
 // Unsigned division by a runtime constant (Granlund-Montgomery round-up form), valid for n < 2^31.
 struct FastDiv {
     uint32_t mul, shift, d;

@@ -17,13 +17,9 @@
 #include <stdlib.h>
 #include "../../include/tricolo_hip.h"
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 int tri_internal_num_cus();                                                   // conv_igemm.hip
-
-template <int N>
-__device__ __forceinline__ float c64_row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
 
 struct ConvC64Args {
     const void* in;            // [N, H, W, 64] 16-bit
@@ -235,10 +231,7 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const ConvC64Args p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float s_ = cs[ct][r], q_ = cq[ct][r];
-                s_ += c64_row_ror<8>(s_); q_ += c64_row_ror<8>(q_);
-                s_ += c64_row_ror<4>(s_); q_ += c64_row_ror<4>(q_);
-                s_ += c64_row_ror<2>(s_); q_ += c64_row_ror<2>(q_);
-                s_ += c64_row_ror<1>(s_); q_ += c64_row_ror<1>(q_);
+                stat_row_sum(s_, q_);
                 if (fr == 0) {
                     red[(wave * 32 + 16 * ct + 4 * fq + r) * 2 + 0] = s_;
                     red[(wave * 32 + 16 * ct + 4 * fq + r) * 2 + 1] = q_;
@@ -249,8 +242,7 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const ConvC64Args p) {
             const int cw = t >> 5, i = t & 31;
             const float s_ = red[(cw * 32 + i) * 2] + red[((cw + 2) * 32 + i) * 2];
             const float q_ = red[(cw * 32 + i) * 2 + 1] + red[((cw + 2) * 32 + i) * 2 + 1];
-            p.stats[(size_t)blockIdx.x * 128 + t] = s_;
-            p.stats[(size_t)blockIdx.x * 128 + 64 + t] = q_;
+            stat_store(p.stats, blockIdx.x, 64, 0, t, s_, q_);
         }
     }
 }

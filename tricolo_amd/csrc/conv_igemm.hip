@@ -18,6 +18,7 @@
 #include <mutex>
 #include "../../include/tricolo_hip.h"
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 struct ConvArgs {
     const void* in;            // activations: fp32 or bf16 (kernel template parameter AT)
@@ -47,12 +48,6 @@ struct ConvArgs {
 #endif
     FastDiv dOW, dOH, dOD, dCin, dP, dH2;
 };
-
-// v rotated right by N lanes inside its row of 16 lanes (DPP row_ror)
-template <int N>
-__device__ __forceinline__ float row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
 
 // Shared epilogue: acc[a][b][r] = out[m = a-tile row (lane & 15)][n = b-tile col 4 * (lane >> 4) + r].
 template <typename AT, int BN, int TM, int TN, int WAVES_M, int WM, int WN>
@@ -116,25 +111,14 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[TM
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float s = cs[b][r], q = cq[b][r];
-                // the 16 rows of a fragment are the 16 lanes of one DPP row: rotate-and-add on the VALU instead of 8
-                // ds_bpermute round trips per column (measured: statistics were 3,300 of a tile's ~31,000 cycles)
-                s += row_ror<8>(s); q += row_ror<8>(q);
-                s += row_ror<4>(s); q += row_ror<4>(q);
-                s += row_ror<2>(s); q += row_ror<2>(q);
-                s += row_ror<1>(s); q += row_ror<1>(q);
-                if (fr == 0) {
-                    int col = wn * WN + b * 16 + fq * 4 + r;
-                    red[(wm * BN + col) * 2 + 0] = s;
-                    red[(wm * BN + col) * 2 + 1] = q;
-                }
+                stat_row_sum(s, q);
+                stat_stage(red, wm, BN, wn * WN + b * 16 + fq * 4 + r, fr, s, q);
             }
         __syncthreads();
         if (t < BN) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int w = 0; w < WAVES_M; ++w) { s += red[(w * BN + t) * 2]; q += red[(w * BN + t) * 2 + 1]; }
-            p.stats[((size_t)mtile * 2 + 0) * p.Cout + n0 + t] = s;
-            p.stats[((size_t)mtile * 2 + 1) * p.Cout + n0 + t] = q;
+            float s, q;
+            stat_wave_sum<WAVES_M>(red, 0, BN, t, s, q);
+            stat_store(p.stats, mtile, p.Cout, n0, t, s, q);
         }
     }
 }
@@ -661,15 +645,8 @@ __device__ __forceinline__ void halo_store_stats(const f32x4* cs, const f32x4* c
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float s_ = cs[b][r], q_ = cq[b][r];
-            s_ += row_ror<8>(s_); q_ += row_ror<8>(q_);
-            s_ += row_ror<4>(s_); q_ += row_ror<4>(q_);
-            s_ += row_ror<2>(s_); q_ += row_ror<2>(q_);
-            s_ += row_ror<1>(s_); q_ += row_ror<1>(q_);
-            if (fr == 0) {
-                const int col = b * 16 + fq * 4 + r;
-                red[(wave * BN + col) * 2 + 0] = s_;
-                red[(wave * BN + col) * 2 + 1] = q_;
-            }
+            stat_row_sum(s_, q_);
+            stat_stage(red, wave, BN, b * 16 + fq * 4 + r, fr, s_, q_);
         }
     if (raw_barrier) {                          // inside the tile loop: LDS-DMA in flight must not be waited for (no vmcnt wait)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -679,10 +656,9 @@ __device__ __forceinline__ void halo_store_stats(const f32x4* cs, const f32x4* c
         __syncthreads();
     }
     if (t < BN) {
-        float s_ = 0.f, q_ = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { s_ += red[(w * BN + t) * 2]; q_ += red[(w * BN + t) * 2 + 1]; }
-        stats[((size_t)rec * 2 + 0) * Cout + ntile * BN + t] = s_;
+        float s_, q_;
+        stat_wave_sum<4>(red, 0, BN, t, s_, q_);
+        stats[((size_t)rec * 2 + 0) * Cout + ntile * BN + t] = s_;        // (stat_store written out: conv_frag.h)
         stats[((size_t)rec * 2 + 1) * Cout + ntile * BN + t] = q_;
         // (per-tile use: the next write to `red` comes after at least nine more barriers)
     }
@@ -1689,23 +1665,14 @@ __global__ __launch_bounds__(256, NPT == 2 ? 2 : 1) void conv_stem_kernel(const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float s_ = cs[ct][r], q_ = cq[ct][r];
-                s_ += row_ror<8>(s_); q_ += row_ror<8>(q_);
-                s_ += row_ror<4>(s_); q_ += row_ror<4>(q_);
-                s_ += row_ror<2>(s_); q_ += row_ror<2>(q_);
-                s_ += row_ror<1>(s_); q_ += row_ror<1>(q_);
-                if (fr == 0) {
-                    const int col = ct * 16 + fq * 4 + r;
-                    red[(wave * 64 + col) * 2 + 0] = s_;
-                    red[(wave * 64 + col) * 2 + 1] = q_;
-                }
+                stat_row_sum(s_, q_);
+                stat_stage(red, wave, 64, ct * 16 + fq * 4 + r, fr, s_, q_);
             }
         __syncthreads();
         if (t < 64) {
-            float s_ = 0.f, q_ = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s_ += red[(w * 64 + t) * 2]; q_ += red[(w * 64 + t) * 2 + 1]; }
-            p.stats[((size_t)blockIdx.x * 2 + 0) * p.Cout + t] = s_;
-            p.stats[((size_t)blockIdx.x * 2 + 1) * p.Cout + t] = q_;
+            float s_, q_;
+            stat_wave_sum<4>(red, 0, 64, t, s_, q_);
+            stat_store(p.stats, blockIdx.x, p.Cout, 0, t, s_, q_);
         }
     }
 }
@@ -1953,11 +1920,6 @@ extern "C" int tri_weight_prep(const float* w, long s_row, long s_tap, long s_in
 }
 
 // ------------------------------------------------------------------------------------------------------ launcher
-
-static int ilog2_exact(int v) {
-    for (int s = 0; s < 31; ++s) if ((1 << s) == v) return s;
-    return -1;
-}
 
 template <int BN, int NSPLIT, typename AT>
 static int launch_conv(const ConvArgs& a, hipStream_t stream) {

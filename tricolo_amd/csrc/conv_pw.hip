@@ -11,6 +11,7 @@
 #include "common.h"
 #include "../../include/tricolo_hip.h"
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 struct PwArgs {
     const void* in;
@@ -21,11 +22,6 @@ struct PwArgs {
     int GH, GW;                // the small grid; the large one is 2 GH x 2 GW
     int transposed;
 };
-
-template <int N>
-static __device__ __forceinline__ float pw_row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
 
 template <typename AT, int BN>
 __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs p) {
@@ -130,23 +126,14 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float s_ = cs[b][r], q_ = cq[b][r];
-            s_ += pw_row_ror<8>(s_); q_ += pw_row_ror<8>(q_);
-            s_ += pw_row_ror<4>(s_); q_ += pw_row_ror<4>(q_);
-            s_ += pw_row_ror<2>(s_); q_ += pw_row_ror<2>(q_);
-            s_ += pw_row_ror<1>(s_); q_ += pw_row_ror<1>(q_);
-            if (fr == 0) {
-                const int col = b * 16 + fq * 4 + r;
-                red[(wave * BN + col) * 2 + 0] = s_;
-                red[(wave * BN + col) * 2 + 1] = q_;
-            }
+            stat_row_sum(s_, q_);
+            stat_stage(red, wave, BN, b * 16 + fq * 4 + r, fr, s_, q_);
         }
     __syncthreads();
     if (t < BN) {
-        float s_ = 0.f, q_ = 0.f;
-#pragma unroll
-        for (int w2 = 0; w2 < 4; ++w2) { s_ += red[(w2 * BN + t) * 2]; q_ += red[(w2 * BN + t) * 2 + 1]; }
-        p.stats[((size_t)mtile * 2 + 0) * p.N + ntile * BN + t] = s_;
-        p.stats[((size_t)mtile * 2 + 1) * p.N + ntile * BN + t] = q_;
+        float s_, q_;
+        stat_wave_sum<4>(red, 0, BN, t, s_, q_);
+        stat_store(p.stats, mtile, p.N, ntile * BN, t, s_, q_);
     }
 }
 

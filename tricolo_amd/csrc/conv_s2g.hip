@@ -22,6 +22,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 int tri_internal_num_cus();                                                   // conv_igemm.hip
 
@@ -60,11 +61,6 @@ __device__ __forceinline__ void s2g_wait(v4i& f, const int n) {
         case 10: asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(f)); break;
         default: asm volatile("s_waitcnt lgkmcnt(11)" : "+v"(f)); break;
     }
-}
-
-template <int N>
-__device__ __forceinline__ float s2g_row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
 }
 
 
@@ -273,10 +269,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2g_kernel(const S2gArgs p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float s_ = cs[tn][q], q_ = cq[tn][q];
-                    s_ += s2g_row_ror<8>(s_); q_ += s2g_row_ror<8>(q_);
-                    s_ += s2g_row_ror<4>(s_); q_ += s2g_row_ror<4>(q_);
-                    s_ += s2g_row_ror<2>(s_); q_ += s2g_row_ror<2>(q_);
-                    s_ += s2g_row_ror<1>(s_); q_ += s2g_row_ror<1>(q_);
+                    stat_row_sum(s_, q_);
                     if (fr == 0) {
                         sred[((wave * TN + tn) * 16 + fq * 4 + q) * 2 + 0] = s_;
                         sred[((wave * TN + tn) * 16 + fq * 4 + q) * 2 + 1] = q_;
@@ -292,8 +285,7 @@ __global__ __launch_bounds__(256, 1) void conv_s2g_kernel(const S2gArgs p) {
                 s_ += sred[(((cw * WK + w) * TN) * 16 + rem) * 2 + 0];
                 q_ += sred[(((cw * WK + w) * TN) * 16 + rem) * 2 + 1];
             }
-            p.stats[((size_t)unit * 2 + 0) * p.Cout + n0 + t] = s_;
-            p.stats[((size_t)unit * 2 + 1) * p.Cout + n0 + t] = q_;
+            stat_store(p.stats, unit, p.Cout, n0, t, s_, q_);
         }
     }
 }

@@ -25,13 +25,9 @@
 #include "common.h"
 #include <stdlib.h>
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 int tri_internal_num_cus();                                                   // conv_igemm.hip
-
-template <int N>
-__device__ __forceinline__ float vox_row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
 
 struct Vox0Args {
     const void* in;            // [B, V, V, V, 4] 16-bit, zeros at inactive sites
@@ -257,10 +253,7 @@ __global__ __launch_bounds__(256, 4) void conv_vox0_kernel(const Vox0Args p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float s_ = ct ? cs1[r] : cs0[r], q_ = ct ? cq1[r] : cq0[r];
-                s_ += vox_row_ror<8>(s_); q_ += vox_row_ror<8>(q_);
-                s_ += vox_row_ror<4>(s_); q_ += vox_row_ror<4>(q_);
-                s_ += vox_row_ror<2>(s_); q_ += vox_row_ror<2>(q_);
-                s_ += vox_row_ror<1>(s_); q_ += vox_row_ror<1>(q_);
+                stat_row_sum(s_, q_);
                 if (fr == 0) {
                     const int ch = 8 * fq + 4 * ct + r;
                     red[(wave * 32 + ch) * 2 + 0] = s_;

@@ -33,6 +33,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "conv_vox.h"
+#include "conv_frag.h"
 
 int tri_internal_num_cus();                                                   // conv_igemm.hip
 
@@ -57,11 +58,6 @@ struct VoxgArgs {
 #define VOXG_STAMP(i)
 #define VOXG_STAMPV(i, v)
 #endif
-
-template <int N>
-__device__ __forceinline__ float voxg_row_ror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
 
 #define VOXG_MAXROWS 512                                                      // active sites of a unit (8^3 sample, all active)
 
@@ -375,10 +371,10 @@ __global__ __launch_bounds__(256, 1) void conv_voxg_kernel(const VoxgArgs p) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float s_ = cs[tn][q], q_ = cq[tn][q];
-                s_ += voxg_row_ror<8>(s_); q_ += voxg_row_ror<8>(q_);
-                s_ += voxg_row_ror<4>(s_); q_ += voxg_row_ror<4>(q_);
-                s_ += voxg_row_ror<2>(s_); q_ += voxg_row_ror<2>(q_);
-                s_ += voxg_row_ror<1>(s_); q_ += voxg_row_ror<1>(q_);
+                s_ += row_ror<8>(s_); q_ += row_ror<8>(q_);
+                s_ += row_ror<4>(s_); q_ += row_ror<4>(q_);
+                s_ += row_ror<2>(s_); q_ += row_ror<2>(q_);
+                s_ += row_ror<1>(s_); q_ += row_ror<1>(q_);
                 if (fr == 0) {
                     sred[((wave * TN + tn) * 16 + fq * 4 + q) * 2 + 0] = s_;
                     sred[((wave * TN + tn) * 16 + fq * 4 + q) * 2 + 1] = q_;
@@ -747,10 +743,7 @@ __global__ __launch_bounds__(256, 2) void conv_voxb_kernel(const VoxbArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float s_ = cs[r], q_ = cq[r];
-            s_ += voxg_row_ror<8>(s_); q_ += voxg_row_ror<8>(q_);
-            s_ += voxg_row_ror<4>(s_); q_ += voxg_row_ror<4>(q_);
-            s_ += voxg_row_ror<2>(s_); q_ += voxg_row_ror<2>(q_);
-            s_ += voxg_row_ror<1>(s_); q_ += voxg_row_ror<1>(q_);
+            stat_row_sum(s_, q_);
             if (fr == 0) {
                 p.stats[(size_t)blockIdx.x * 128 + wave * 16 + fq * 4 + r] = s_;
                 p.stats[(size_t)blockIdx.x * 128 + 64 + wave * 16 + fq * 4 + r] = q_;

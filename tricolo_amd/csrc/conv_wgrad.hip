@@ -1370,11 +1370,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const WgradGr
     wgrad_note_bad(bad, g.note);
 }
 
-static int ilog2_exact(int v) {
-    for (int s = 0; s < 31; ++s) if ((1 << s) == v) return s;
-    return -1;
-}
-
 
 // ---------------------------------------------------------------------------------------------------- gather plan
 // Per output position: element offset of the origin input voxel (o*stride - pad) and per-axis tap validity bits

@@ -18,11 +18,6 @@ int tri_check_launch(const char* what) {
 }
 extern "C" int tri_version() { return 1; }
 
-static inline int ew_grid(long total) {
-    long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 // ------------------------------------------------------------------------------------------------ voxel scatter
 // COO batch of data_module.py:52-64 (locs [n,4] = (b,i0,i1,i2), feats [n,3] in [0,1]) -> dense channels-last grid
 // [B,V,V,V,4] = (r,g,b,0) and site mask [B,V,V,V].  Both outputs must be zero-filled first (tri_fill_zero).

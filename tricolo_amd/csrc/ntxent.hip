@@ -179,8 +179,6 @@ __global__ void l2norm_rows_kernel(const float* __restrict__ x, int rows, int D,
     if (lane == 0) norm[row] = nrm;
 }
 
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 extern "C" size_t tri_ntxent_workspace(int B, int D) {
     return 2 * al256((size_t)B * D * 4) + 5 * al256((size_t)B * 4) + al256((size_t)B * B * 4);
 }

@@ -248,8 +248,6 @@ __global__ __launch_bounds__(256) void trp_grad_kernel(const TrpMulti p) {
     }
 }
 
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 static size_t trp_workspace(int M, int B) {
     const int P = M * (M - 1) / 2;
     return (size_t)M * al256((size_t)B * 8) + (size_t)P * (al256((size_t)B * B * 8) + al256((size_t)B * 16) + al256((size_t)B * 8) + 256);
