@@ -405,7 +405,12 @@ int tri_cast_to_f32(const void* src, float* dst, long n, int act_fmt, void* stre
  * pre-activation gradients dgi [L][B][768], dgh [2][L][B][384] and h_{t-1} rows hprev [2][L][B][128]; the weight
  * gradients are then plain GEMMs (tri_conv_wgrad with 1x1 geometry).
  * split3: MFMA operand mode of the recurrence - 0 single bf16 products, 1 the 3-product bf16 hi/lo split (fp32-grade), 2 single f16
- * products (the f16 mode; the backward carries its gate gradients through LDS times 2^12). */
+ * products (the f16 mode; the backward carries its gate gradients through LDS times 2^12).
+ * Input range of tri_gru_bwd in the f16 mode: every gate gradient must satisfy |dgate| < 65504 / 4096 (~16), or f16(4096 dgate)
+ * overflows to inf; with unit-size dhfinal the largest |dgate| is ~2.2, a real NT-Xent step is 2^-7 of that.  Resolution: 2^-24 / 4096
+ * (f16 subnormals survive the conversion, the LDS round trip and the f16 MFMA on gfx950 - measured: at 2^-20 of unit scale the backward
+ * is 1.4e-4 in relative L2 from float64, where flushing them would cost 2.7e-2; tests/test_gpu_text_tower.py,
+ * profiles/r17/NOTES_text_tower.md).  The bf16 modes have fp32's range and scale exactly with powers of two. */
 int tri_gru_fwd(const float* xproj, const float* w_hh, const float* b_hh, int B, int L, float* hs, float* gates, float* hfinal,
                 int split3, void* stream);
 int tri_gru_bwd(const float* dhfinal, const float* w_hh, const float* hs, const float* gates, int B, int L, float* dgi, float* dgh,

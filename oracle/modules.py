@@ -70,7 +70,7 @@ class BiGRURef(nn.Module):
 
     def forward(self, x, data_dict=None):
         emb = torch.transpose(self.embedding_layer(x), 0, 1)
-        h0 = torch.zeros((2, emb.shape[1], 128), dtype=torch.float32, device=emb.device)
+        h0 = torch.zeros((2, emb.shape[1], 128), dtype=emb.dtype, device=emb.device)
         _, hidden = self.gru(emb, h0)
         return F.normalize(torch.tanh(self.fc(torch.cat((hidden[-2], hidden[-1]), dim=1))), dim=1)
 
