@@ -488,25 +488,45 @@ int tri_f1_finalize(const int* count_p, const int* count_q, const float* sum_p, 
  * as fl32(v * scale[n]) before anything else, as the reference scales its meshes before it samples them.  A vertex index outside the
  * mesh is clamped to the mesh's own vertices (callers validate on the host; the kernels never read beyond the mesh).
  *
- * tri_mesh_bbox replaces gt_meshes.get_bounding_boxes() (calculate_f1.py:90): bbox [N][3][2] fp32 = per-axis (min, max) over ALL
- * vertices of the mesh, referenced by a face or not; a mesh without vertices gives zeros.  Not scaled. */
-int tri_mesh_bbox(const float* verts, const long* vert_off, int N, float* bbox, void* stream);
+ * Every mesh call takes the batch as one descriptor (csrc/mesh_batch.h lays the arrays out).  The first eight members are every
+ * call's; the sampler's calls and tri_mesh_bbox read no material and take null in those three.  The groups after them are optional
+ * and DECLARED, not inferred from null: `fields` names the groups the caller says are there.  A group that `fields` does not name
+ * is never read, whatever its members hold.  What every call refuses with TRI_ERR_ARG before anything runs: a null descriptor, a
+ * negative N or T, a bit in `fields` that the call does not take, TRI_MESH_MIPS without TRI_MESH_TEXTURES, T > 0 with a null
+ * member in a declared texture or pyramid group (T == 0: both groups may be null), a null face_vn / mat_pbr in a declared group. */
+#define TRI_MESH_TEXTURES 1u
+#define TRI_MESH_MIPS 2u
+#define TRI_MESH_NORMALS 4u
+#define TRI_MESH_PBR 8u
+typedef struct TriMeshBatch {       /* the members of csrc/mesh_batch.h's MeshBatch, in its order, then `fields` */
+    const float* verts; const int* faces; const long* vert_off; const long* face_off;
+    const int* face_mat; const float* mat_kd; const long* mat_off;
+    int N;
+    const float* face_uv; const int* mat_tex; const uint8_t* texels; const long* tex_off; const int* tex_size; int T;   /* TRI_MESH_TEXTURES */
+    const uint8_t* mip_texels; const long* mip_off;                                                                     /* TRI_MESH_MIPS */
+    const float* face_vn;                                                                                               /* TRI_MESH_NORMALS */
+    const float* mat_pbr;                                                                                               /* TRI_MESH_PBR */
+    unsigned fields;                /* the TRI_MESH_* groups that are there */
+} TriMeshBatch;
+size_t tri_mesh_batch_size(void);   /* sizeof(TriMeshBatch), for bindings that mirror the struct */
+
+/* tri_mesh_bbox replaces gt_meshes.get_bounding_boxes() (calculate_f1.py:90): bbox [N][3][2] fp32 = per-axis (min, max) over ALL
+ * vertices of the mesh, referenced by a face or not; a mesh without vertices gives zeros.  Not scaled.  Reads verts and vert_off. */
+int tri_mesh_bbox(const TriMeshBatch* batch, float* bbox, void* stream);
 /* The face-area CDF that sample_points_from_meshes (calculate_f1.py:125) draws its faces from: area = 0.5 * |(b - a) x (c - a)| in fp32
  * on the scaled vertices, cdf [sumF] float64 = the inclusive prefix sum of the areas per mesh, total [N] float64 = its last entry (0
  * for a mesh without faces).  Summed in float64 in 2,048-face chunks counted from the mesh's first face (chunk sums, a serial chain
  * over the sums, apply): the bits depend on the mesh alone, the CDF never decreases and a face of area 0 repeats the entry before it
  * exactly.  max_faces: at least the largest face count of the batch (it sizes the grid), below 2^31.  No atomics; bit-reproducible. */
-int tri_mesh_face_cdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale, int N,
-                      long max_faces, double* cdf, double* total, void* stream);
+int tri_mesh_face_cdf(const TriMeshBatch* batch, const float* scale, long max_faces, double* cdf, double* total, void* stream);
 /* Replaces sample_points_from_meshes(meshes, S) (calculate_f1.py:125; normals are not produced).  For mesh n and sample s:
  * Philox4x32-10, key = (low, high 32 bits of seed), counter = (s, n, 0, 0) -> x0..x3; u_f = (x0 >> 8) * 2^-24, u1, u2 likewise from x1,
  * x2; the face is the smallest f with cdf[f] > u_f * total[n] (float64; a face of area 0 is never chosen); with r = sqrtf(u1) the point is
  * (1 - r) a + r (1 - u2) b + r u2 c in fp32 on the scaled vertices.  points [N][S][3] fp32, face_idx (optional) int64 [N][S], local
  * to the mesh.  A mesh without faces or with total area 0 gives zero rows and -1.  Row (n, s) depends on (seed, n, s) and the mesh
  * only - not on S, the launch shape or the other meshes.  Large batches are split over launches. */
-int tri_mesh_sample_points(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale,
-                           const double* cdf, const double* total, int N, int S, unsigned long long seed, float* points, long* face_idx,
-                           void* stream);
+int tri_mesh_sample_points(const TriMeshBatch* batch, const float* scale, const double* cdf, const double* total, int S,
+                           unsigned long long seed, float* points, long* face_idx, void* stream);
 
 /* ---- Multi-view rendering (data/preprocess_all_data.py:44-82: the pyrender scene, restated as a rasteriser) -------------------- */
 /* The packed batch of the mesh sampler plus: face_mat int32 [sumF], the material of every face, local to its mesh; mat_kd fp32
@@ -517,42 +537,35 @@ int tri_mesh_sample_points(const float* verts, const int* faces, const long* ver
  * coverage by int64 edge functions at the pixel centres with the top-left rule, both sides visible, depth 1 / z interpolated in
  * fp32, the nearest face per pixel by a 64-bit atomic max (at bit-equal depth the lower face index): independent of the order in
  * which faces arrive, bit-reproducible.  Flat Lambert shading, Kd (0.1 + 3 / pi max(n . (0, 1, 0), 0)), white background.  The
- * arithmetic is spelled out at the head of csrc/raster.hip.  workspace: tri_raster_workspace(...) bytes of device memory, 16-byte
- * aligned (0 for sizes tri_raster_render refuses).  Limits of one call: fewer than 2^31 faces, fewer than 2^31 pixels over all meshes
- * and views, at most 65535 views: TRI_ERR_UNSUPPORTED before anything is launched.  Indices outside a mesh are clamped to it. */
-size_t tri_raster_workspace(long sumF, int N, int views, int H, int W);
-int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                      const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
-                      double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
+ * arithmetic is spelled out at the head of csrc/raster.hip.  samples is 1 or 4 (below; anything else is TRI_ERR_ARG, and a
+ * workspace of 0).  workspace: tri_raster_workspace(...) bytes of device memory, 16-byte aligned (0 for sizes tri_raster_render
+ * refuses).  Limits of one call: fewer than 2^31 faces, fewer than 2^31 pixels over all meshes and views, at most 65535 views:
+ * TRI_ERR_UNSUPPORTED before anything is launched.  Indices outside a mesh are clamped to it.
+ *
+ * ONE entry point renders every mode; the mode follows from batch->fields and samples, as the paragraphs below say: textured with
+ * TRI_MESH_TEXTURES, mip-mapped with TRI_MESH_MIPS beside it, smooth with TRI_MESH_NORMALS, the metallic-roughness BRDF with
+ * TRI_MESH_PBR, in any combination and at either sample count. */
+size_t tri_raster_workspace(long sumF, int N, int views, int H, int W, int samples);
+int tri_raster_render(const TriMeshBatch* batch, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+                      int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
 
-/* tri_raster_render with map_Kd textures.  The batch's five texture fields (csrc/mesh_batch.h): face_uv fp32 [sumF][3][2], one (u, v)
+/* TRI_MESH_TEXTURES: map_Kd textures.  The batch's five texture fields (csrc/mesh_batch.h): face_uv fp32 [sumF][3][2], one (u, v)
  * per face corner, a NaN in face_uv[f][0][0] marks a face without texture coordinates; mat_tex int32 [sumM], a batch-global texture
  * index per material, -1 = none, anything else clamped to T - 1 (T == 0: nothing is textured); texels u8 [sumTexels][4] RGBA (alpha
  * ignored); tex_off int64 [T + 1] texel offsets; tex_size int32 [T][2] = (height, width); row 0 is the top of the image, v = 0 its
- * bottom.  Visibility is tri_raster_render's, bit for bit; the colour of a textured face is clamp((Kd c) shade, 0, 1) with c the
+ * bottom.  Visibility is the untextured call's, bit for bit; the colour of a textured face is clamp((Kd c) shade, 0, 1) with c the
  * texture at the perspective-correct (u, v) of the pixel centre: repeat wrap, bilinear over the texel centres, NO mip-maps, every
  * operation in fp32 rounded on its own (spelled out at the head of csrc/raster.hip).  An untextured face - by its material, by the NaN
- * marker, or where (u, v) is not finite - is coloured exactly as by tri_raster_render.  Same workspace, same limits. */
-int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                          const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
-                          double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
-
-/* Four coverage samples per pixel, for batches with and without textures (the texture fields null and T == 0: every face is
- * untextured).  The sample positions, in 1/256 pixel from the pixel's top-left corner: (96, 32), (224, 96), (32, 160), (160, 224) - the
- * 4x rotated grid, the centre is not among them.  Coverage, depth and the 64-bit key of a sample are tri_raster_render's rules at the
- * sample's position instead of the pixel centre (same face set-up, top-left rule, atomic max).  Every sample is coloured as
- * tri_raster_render_tex colours a pixel - a textured face from the perspective-correct (u, v) at the sample's own position - and the
- * pixel is (c0 + c1 + c2 + c3 + 2) >> 2 per channel of the four u8 colours: a multisample resolve for untextured faces, 4x
- * supersampling for textured ones.  image u8 [N][views][3][H][W]; visibility (optional) int32 [N][views][H][W][4]: the face at each
- * sample, -1 for none.  workspace: tri_raster_workspace_aa(...) bytes, 16-byte aligned (0 for sizes the call refuses).  Limits of
- * one call: those of tri_raster_render, with fewer than 2^31 SAMPLES (N views H W 4) in place of pixels.  The arithmetic is spelled
- * out at the head of csrc/raster.hip. */
-size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W);
-int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                         const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                         const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H, int W,
-                         double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream);
+ * marker, or where (u, v) is not finite - is coloured exactly as without textures.  Same workspace, same limits.
+ *
+ * samples == 4: four coverage samples per pixel, for batches with and without textures.  The sample positions, in 1/256 pixel from
+ * the pixel's top-left corner: (96, 32), (224, 96), (32, 160), (160, 224) - the 4x rotated grid, the centre is not among them.
+ * Coverage, depth and the 64-bit key of a sample are the one-sample rules at the sample's position instead of the pixel centre (same
+ * face set-up, top-left rule, atomic max).  Every sample is coloured as a pixel is with one sample - a textured face from the
+ * perspective-correct (u, v) at the sample's own position - and the pixel is (c0 + c1 + c2 + c3 + 2) >> 2 per channel of the four u8
+ * colours: a multisample resolve for untextured faces, 4x supersampling for textured ones.  image u8 [N][views][3][H][W];
+ * visibility (optional) int32 [N][views][H][W][4]: the face at each sample, -1 for none.  Limits of one call: those of one sample,
+ * with fewer than 2^31 SAMPLES (N views H W 4) in place of pixels.  The arithmetic is spelled out at the head of csrc/raster.hip. */
 
 /* The mip pyramid of every texture of a batch (csrc/mesh_batch.h lays it out).  Texture t of size (H0, W0) has
  * L = floor(log2(max(H0, W0))) + 1 levels of size (max(1, H0 >> l), max(1, W0 >> l)); its chain starts at mip_off[t] (int64 [T + 1], the
@@ -564,71 +577,52 @@ int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_
 int tri_texture_mips(const uint8_t* texels, const long* tex_off, const int* tex_size, int T, long sum_texels, const long* mip_off,
                      long sum_mip, uint8_t* mip_texels, void* stream);
 
-/* tri_raster_render_tex (samples == 1) or tri_raster_render_aa (samples == 4) with mip-mapped textures: the same visibility, bit for
- * bit, the same workspace (tri_raster_workspace / tri_raster_workspace_aa) and limits.  mip_texels, mip_off: the pyramid of
- * tri_texture_mips for this batch's textures.  A textured face is coloured clamp((Kd c) shade, 0, 1) with c blended from two levels
- * of the pyramid; the level of detail comes from (u, v) at the position itself, one whole pixel to the right and one whole pixel
- * down (the face's plane extended; with four samples the step is still one pixel, no LOD bias).  Where the texture is magnified
- * (rho <= 1) the colour is tri_raster_render_tex's, bit for bit.  The rule is spelled out at the head of csrc/raster.hip; it is a
- * definition of this project, not compared with any other renderer.  T == 0: every face is untextured and the pyramid may be null. */
-int tri_raster_render_mip(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                          const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off, const float* cam,
-                          int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, void* workspace,
-                          uint8_t* image, int* visibility, void* stream);
-
-/* Smooth shading: any of the six modes above with the batch's corner normals face_vn fp32 [sumF][3][3] (csrc/mesh_batch.h: one normal
- * per face corner in the order of `faces`, not necessarily of unit length; a NaN in face_vn[f][0][0] marks a face without normals,
- * which is shaded flat exactly as before).  The mode follows from the arguments: the five texture fields may be null with T == 0 (no
- * face is textured), the two pyramid fields may be null (no mip-mapping; they come together or not at all), samples is 1 or 4.
- * Visibility is tri_raster_render's (tri_raster_render_aa's with four samples), bit for bit: only the resolve pass differs.  At the
- * pixel centre - with four samples at each sample's own position - the normal is interpolated with the perspective-correct weights
- * of the textured modes, turned toward the eye by the sign of its dot product with eye - vertex 0, and lit as the flat one is:
- * Kd (0.1 + 3 / pi max(n_y / |n|, 0)); where the interpolated normal is not finite or has no length the position takes the flat
- * shade.  The arithmetic is spelled out at the head of csrc/raster.hip.  workspace: tri_raster_workspace(...) bytes for samples == 1,
- * tri_raster_workspace_aa(...) for samples == 4; the same limits.  A null face_vn is TRI_ERR_ARG. */
-int tri_raster_render_smooth(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                             const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                             const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
-                             const float* face_vn, const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear,
-                             int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
-
-/* The glTF 2.0 metallic-roughness BRDF in place of the Lambert shade: any of the six modes above, flat (face_vn null) or smooth, with
- * the batch's mat_pbr fp32 [sumM][2] = (metallic, roughness) per material, indexed like mat_kd (csrc/mesh_batch.h; metallic clamped to
- * [0, 1], roughness to [0.04, 1], a NaN takes the lower bound; a mesh without materials takes (0.2, 0.8)).  The other arguments are
- * tri_raster_render_smooth's and the mode follows from them in the same way.  Visibility is tri_raster_render's
- * (tri_raster_render_aa's with four samples), bit for bit: only the resolve pass differs.  At the pixel centre - with four samples at
- * each sample's own position - the world position p on the winning face comes from the perspective-correct weights, v = (eye - p) /
- * |eye - p|, l = (0, 1, 0), h = (l + v) / |l + v|, n is the unit shading normal of the Lambert modes, base = Kd (times the texel), and
+/* TRI_MESH_MIPS (beside TRI_MESH_TEXTURES): tri_raster_render with mip-mapped textures, at either sample count: the same visibility,
+ * bit for bit, the same workspace and limits.  mip_texels, mip_off: the pyramid of tri_texture_mips for this batch's textures.  A
+ * textured face is coloured clamp((Kd c) shade, 0, 1) with c blended from two levels of the pyramid; the level of detail comes from
+ * (u, v) at the position itself, one whole pixel to the right and one whole pixel down (the face's plane extended; with four samples
+ * the step is still one pixel, no LOD bias).  Where the texture is magnified (rho <= 1) the colour is the one without the pyramid,
+ * bit for bit.  The rule is spelled out at the head of csrc/raster.hip; it is a definition of this project, not compared with any
+ * other renderer.  T == 0: every face is untextured and the pyramid may be null.
+ *
+ * TRI_MESH_NORMALS: smooth shading, in any of the six modes above, with the batch's corner normals face_vn fp32 [sumF][3][3]
+ * (csrc/mesh_batch.h: one normal per face corner in the order of `faces`, not necessarily of unit length; a NaN in face_vn[f][0][0]
+ * marks a face without normals, which is shaded flat exactly as before).  Visibility does not change, bit for bit: only the resolve
+ * pass differs.  At the pixel centre - with four samples at each sample's own position - the normal is interpolated with the
+ * perspective-correct weights of the textured modes, turned toward the eye by the sign of its dot product with eye - vertex 0, and
+ * lit as the flat one is: Kd (0.1 + 3 / pi max(n_y / |n|, 0)); where the interpolated normal is not finite or has no length the
+ * position takes the flat shade.  The arithmetic is spelled out at the head of csrc/raster.hip.
+ *
+ * TRI_MESH_PBR: the glTF 2.0 metallic-roughness BRDF in place of the Lambert shade, in any of the six modes above, flat or smooth,
+ * with the batch's mat_pbr fp32 [sumM][2] = (metallic, roughness) per material, indexed like mat_kd (csrc/mesh_batch.h; metallic
+ * clamped to [0, 1], roughness to [0.04, 1], a NaN takes the lower bound; a mesh without materials takes (0.2, 0.8)).  Visibility
+ * does not change, bit for bit: only the resolve pass differs.  At the pixel centre - with four samples at each sample's own
+ * position - the world position p on the winning face comes from the perspective-correct weights, v = (eye - p) / |eye - p|,
+ * l = (0, 1, 0), h = (l + v) / |l + v|, n is the unit shading normal of the Lambert modes, base = Kd (times the texel), and
  *   colour = clamp(0.1 base + 3 NL ((1 - F) cdiff / pi + F G D / (4 NL NV)), 0, 1)
  * with Schlick's Fresnel term, the Smith-GGX geometry term and the GGX distribution of the glTF specification and the cosine clamps of
  * the Khronos reference shader; every sum, product and quotient is spelled out at the head of csrc/raster.hip.  A position where a
- * weight, |eye - p| or |l + v| is not finite or zero, or the normal has no finite length, takes the Lambert colour of
- * tri_raster_render_smooth, bit for bit.  The same workspace and limits.  A null mat_pbr is TRI_ERR_ARG. */
-int tri_raster_render_brdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                           const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                           const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
-                           const float* face_vn, const float* mat_pbr, const float* cam, int N, long sumF, int views, int H, int W,
-                           double yfov, double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream);
+ * weight, |eye - p| or |l + v| is not finite or zero, or the normal has no finite length, takes the Lambert colour of the same
+ * batch without TRI_MESH_PBR, bit for bit. */
 
-/* Vertex normals of a packed batch, written as corner normals face_vn_out fp32 [sumF][3][3] for tri_raster_render_smooth.  A
+/* Vertex normals of a packed batch, written as corner normals face_vn_out fp32 [sumF][3][3] for TRI_MESH_NORMALS.  A
  * definition of this project (head of csrc/mesh_normals.hip): area-weighted - the fp32 cross product of every face, clamped to
  * +-2^16 per component and rounded to fixed point with 36 fractional bits, is summed per VERTEX INDEX of its mesh with 64-bit integer
  * atomics, so the result does not depend on the order of the faces and is bit-reproducible - then normalised in float64 and rounded
  * to fp32.  fill 0: a face whose face_vn_in[f][0][0] is not NaN keeps its nine incoming values bit for bit and only the others are
  * computed (face_vn_in may be null: all are computed); fill 1: every face is computed.  A face with a corner whose sum is (0, 0, 0) is
  * written as nine NaNs.  workspace: tri_mesh_vertex_normals_workspace(sumV) bytes of device memory (24 per vertex), 8-byte aligned.
- * Three launches on the stream, no host synchronisation.  Fewer than 2^31 faces and vertices. */
+ * Three launches on the stream, no host synchronisation.  Fewer than 2^31 faces and vertices.  Takes no optional group: the
+ * incoming normals are face_vn_in, not the batch's face_vn. */
 size_t tri_mesh_vertex_normals_workspace(long sumV);
-int tri_mesh_vertex_normals(const float* verts, const int* faces, const long* vert_off, const long* face_off, int N, long sumV, long sumF,
-                            int fill, void* workspace, const float* face_vn_in, float* face_vn_out, void* stream);
+int tri_mesh_vertex_normals(const TriMeshBatch* batch, long sumV, long sumF, int fill, void* workspace, const float* face_vn_in,
+                            float* face_vn_out, void* stream);
 
 /* One colour per face for the voxeliser: colours fp32 [sumF][3] = Kd for an untextured face, else Kd times the mean of four bilinear
  * samples of its texture, at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) of the face's UVs (used
- * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped. */
-int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                          const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                          const long* tex_off, const int* tex_size, int T, int N, long sumF, float* colours, void* stream);
+ * affinely; summed in this order, times 0.25f).  A face with a sample at a non-finite (u, v) is untextured.  Not clamped.
+ * Takes TRI_MESH_TEXTURES and no other group. */
+int tri_mesh_face_colours(const TriMeshBatch* batch, long sumF, float* colours, void* stream);
 
 /* ---- Coloured solid voxel grids from meshes (no counterpart in the reference, which reads downloaded NRRD grids) --------------- */
 /* The packed batch of tri_raster_render plus frame fp32 [N][4] = (origin x, y, z, cell size) per mesh.  grid u8 [N][4][V][V][V],
@@ -641,11 +635,11 @@ int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert
  * the order -x, +x, -y, +y, -z, +z).  Alpha 255 on surface and interior voxels; everything 0 elsewhere.  A mesh with cell <= 0 or a
  * non-finite frame gives an all-zero grid.  The arithmetic is spelled out at the head of csrc/voxelize.hip.  workspace:
  * tri_voxelize_workspace(...) bytes of device memory, 16-byte aligned (0 for sizes tri_voxelize_meshes refuses).  V must be 32, 64
- * or 128; fewer than 2^24 faces and fewer than 2^31 voxels in one call: TRI_ERR_UNSUPPORTED before anything is launched. */
+ * or 128; fewer than 2^24 faces and fewer than 2^31 voxels in one call: TRI_ERR_UNSUPPORTED before anything is launched.  Takes no
+ * optional group. */
 size_t tri_voxelize_workspace(long sumF, int N, int V);
-int tri_voxelize_meshes(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                        const float* mat_kd, const long* mat_off, const float* frame, int N, long sumF, int V, int fill, void* workspace,
-                        uint8_t* grid, uint8_t* labels, void* stream);
+int tri_voxelize_meshes(const TriMeshBatch* batch, const float* frame, long sumF, int V, int fill, void* workspace, uint8_t* grid,
+                        uint8_t* labels, void* stream);
 
 /* ---- Bicubic antialiased resize of u8 renderings (general_dataset.py:63-65: Resize(image_size, BICUBIC, antialias=True)) ------- */
 /* in [planes][Hin][Win] u8 -> out [planes][Hout][Wout] u8, both contiguous: cast to fp32, the separable bicubic (a = -0.5) antialias

@@ -99,10 +99,12 @@ def stream_entry_points():
 
 class RecordingLib:
     """Stands in for the ctypes library handle (tricolo_amd._C._lib, as _C._TimedLib does): notes every tri_* entry point that takes
-    arguments - launches and size / plan queries alike; `launches()` keeps the ones declared with a stream (stream_entry_points)."""
+    arguments - launches and size / plan queries alike; `launches()` keeps the ones declared with a stream (stream_entry_points).
+    The one render entry point serves every mode, so of each tri_raster_render call `raster_calls` keeps (fields, samples): the groups
+    its descriptor declared (_C.TRI_MESH_*) and its sample count."""
 
     def __init__(self, real, signatures):
-        self._real, self._sig, self.calls = real, signatures, []
+        self._real, self._sig, self.calls, self.raster_calls = real, signatures, [], []
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
@@ -112,6 +114,8 @@ class RecordingLib:
 
         def recorded(*a):
             self.calls.append(name)
+            if name == "tri_raster_render":                # (batch, cam, sumF, views, H, W, yfov, znear, samples, ...)
+                self.raster_calls.append((int(a[0].fields), int(a[8])))
             return fn(*a)
         return recorded
 
@@ -217,6 +221,11 @@ class Guard:
     @property
     def launched(self):
         return self.lib.launches() if self.lib is not None else []
+
+    @property
+    def raster_calls(self):
+        """[(fields, samples)] of the tri_raster_render calls made so far (RecordingLib)."""
+        return list(self.lib.raster_calls) if self.lib is not None else []
 
     def check(self):
         bad = []

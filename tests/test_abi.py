@@ -26,6 +26,8 @@ def test_header_symbols_are_exported_and_bound():
         assert hasattr(lib, s), f"{s} declared in tricolo_hip.h but not exported"
         assert s in _C.SIGNATURES, f"{s} has no ctypes signature"
     assert sorted(_C.SIGNATURES) == syms
+    import ctypes
+    assert ctypes.sizeof(_C.TriMeshBatch) == lib.tri_mesh_batch_size()            # the ctypes mirror of the batch descriptor
     assert lib.tri_version() >= 1
     assert lib.tri_conv_kpad(27, 4) == 128 and lib.tri_conv_kpad(49, 4) == 224
 

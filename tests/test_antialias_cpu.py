@@ -245,18 +245,22 @@ def test_refusals_before_anything_runs():
         ops.render_views_textured(*batch.tensors, *batch.texture_tensors, s["cam"][None].expand(1, 3, 12).contiguous(), 13378, 13378, samples=4)
     # the C entry point itself: sizes are checked before any pointer is touched, so null pointers and no GPU will do
     lib = _C.lib()
-    null = [None] * 12
     tail = [None, None, None, None]                                                      # workspace, image, visibility, stream
-    assert lib.tri_raster_workspace_aa(200, 1, 3, 13378, 13378) == 0
-    assert lib.tri_raster_workspace_aa(200, 1, 3, 32, 48) == 3 * 32 * 48 * 32 + 16 + 200 * 3 * 8
-    assert lib.tri_raster_workspace(200, 1, 3, 32, 48) == 3 * 32 * 48 * 8 + 16 + 200 * 3 * 8
-    rc = lib.tri_raster_render_aa(*null, 0, None, 1, 200, 3, 13378, 13378, R.YFOV, R.ZNEAR, *tail)
+
+    def null(N, T):                                                                      # every pointer null, the texture group declared
+        return _C.TriMeshBatch(N=N, T=T, fields=_C.TRI_MESH_TEXTURES)
+
+    assert lib.tri_raster_workspace(200, 1, 3, 13378, 13378, 4) == 0
+    assert lib.tri_raster_workspace(200, 1, 3, 32, 48, 4) == 3 * 32 * 48 * 32 + 16 + 200 * 3 * 8
+    assert lib.tri_raster_workspace(200, 1, 3, 32, 48, 1) == 3 * 32 * 48 * 8 + 16 + 200 * 3 * 8
+    assert [lib.tri_raster_workspace(200, 1, 3, 32, 48, bad) for bad in (0, 2, 3, 8, -1)] == [0] * 5
+    rc = lib.tri_raster_render(null(1, 0), None, 200, 3, 13378, 13378, R.YFOV, R.ZNEAR, 4, *tail)
     assert rc == _C.TRI_ERR_UNSUPPORTED
     message = lib.tri_last_error().decode()
-    assert "tri_raster_render_aa" in message and "2^31 or more samples" in message and "split the batch" in message
-    assert lib.tri_raster_render_aa(*null, -1, None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR, *tail) != 0          # a negative texture count
-    assert lib.tri_raster_render_aa(*null, 0, None, 1, 200, 3, 8, 8, 4.0, R.ZNEAR, *tail) != 0             # yfov beyond pi
-    assert lib.tri_raster_render_aa(*null, 0, None, 0, 0, 3, 8, 8, R.YFOV, R.ZNEAR, *tail) == 0            # nothing to draw: nothing runs
+    assert "tri_raster_render" in message and "2^31 or more samples" in message and "split the batch" in message
+    assert lib.tri_raster_render(null(1, -1), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 4, *tail) != 0          # a negative texture count
+    assert lib.tri_raster_render(null(1, 0), None, 200, 3, 8, 8, 4.0, R.ZNEAR, 4, *tail) != 0             # yfov beyond pi
+    assert lib.tri_raster_render(null(0, 0), None, 0, 3, 8, 8, R.YFOV, R.ZNEAR, 4, *tail) == 0            # nothing to draw: nothing runs
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the command line

@@ -357,16 +357,22 @@ def test_refusals_and_the_packed_batch():
 
 def test_the_entry_point_refuses_bad_arguments_before_anything_runs():
     lib = _C.lib()
-    mesh_and_textures, pyramid, tail, some = (None,) * 12, (None, None), (None, None, None, None), 64         # `some`: not null, never read
-    view = (None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR)
-    assert lib.tri_raster_render_brdf(*mesh_and_textures, 0, *pyramid, None, None, *view, 1, *tail) == _C.TRI_ERR_ARG
+    tail, some = (None, None, None, None), 64                                                                 # `some`: not null, never read
+    TEX, VN, PBR = _C.TRI_MESH_TEXTURES, _C.TRI_MESH_NORMALS, _C.TRI_MESH_PBR
+
+    def null(N, T, mat_pbr, fields=PBR, face_vn=None):                                                        # every other pointer null
+        return _C.TriMeshBatch(N=N, T=T, face_vn=face_vn, mat_pbr=mat_pbr, fields=fields)
+
+    view = (None, 200, 3, 8, 8, R.YFOV, R.ZNEAR)
+    assert lib.tri_raster_render(null(1, 0, None), *view, 1, *tail) == _C.TRI_ERR_ARG
     assert "mat_pbr" in lib.tri_last_error().decode()
-    assert lib.tri_raster_render_brdf(*mesh_and_textures, 0, *pyramid, some, None, *view, 4, *tail) == _C.TRI_ERR_ARG
-    assert lib.tri_raster_render_brdf(*mesh_and_textures, 0, *pyramid, None, some, *view, 2, *tail) == _C.TRI_ERR_ARG              # samples
-    assert lib.tri_raster_render_brdf(*mesh_and_textures, 3, *pyramid, None, some, *view, 1, *tail) == _C.TRI_ERR_ARG              # textures without fields
-    assert lib.tri_raster_render_brdf(*mesh_and_textures, 0, *pyramid, None, some, None, 1, 200, 3, 8, 8, 4.0, R.ZNEAR, 1, *tail) != 0      # yfov beyond pi
+    assert lib.tri_raster_render(null(1, 0, None, VN | PBR, some), *view, 4, *tail) == _C.TRI_ERR_ARG
+    assert "mat_pbr" in lib.tri_last_error().decode()
+    assert lib.tri_raster_render(null(1, 0, some), *view, 2, *tail) == _C.TRI_ERR_ARG                         # samples
+    assert lib.tri_raster_render(null(1, 3, some, TEX | PBR), *view, 1, *tail) == _C.TRI_ERR_ARG             # textures without fields
+    assert lib.tri_raster_render(null(1, 0, some), None, 200, 3, 8, 8, 4.0, R.ZNEAR, 1, *tail) != 0           # yfov beyond pi
     for samples in (1, 4):
-        assert lib.tri_raster_render_brdf(*mesh_and_textures, 0, *pyramid, None, some, None, 0, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0  # nothing to draw
+        assert lib.tri_raster_render(null(0, 0, some), None, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0     # nothing to draw
 
 
 # ---------------------------------------------------------------------------------------------------- the parser

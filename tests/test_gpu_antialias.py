@@ -1,4 +1,4 @@
-"""GPU: the four-sample kernels of csrc/raster.hip (tri_raster_render_aa) through ops.render_views and ops.render_views_textured with
+"""GPU: the four-sample kernels of csrc/raster.hip (tri_raster_render with samples == 4) through ops.render_views and ops.render_views_textured with
 samples=4 against their torch restatement (the same call on CPU tensors, compared with a float64 brute force at the sample positions
 in tests/test_antialias_cpu.py): the visibility equal on every sample, the colours equal or within 1 LSB on every pixel - the bound
 tests/test_gpu_raster.py uses for this renderer; batching, order independence, textures, the real resolution, and the guard bands
@@ -197,7 +197,7 @@ def test_guard_bands():
             img, vis = ops.render_views_textured(*t, *x, c, 32, 48, return_visibility=True, samples=4)
             pimg, pvis = ops.render_views(*t, c, 32, 48, return_visibility=True, samples=4)
             assert all(hasattr(o, "_band") for o in (img, vis, pimg, pvis))               # the outputs are banded too
-        assert "tri_raster_render_aa" in g.launched and not {"tri_raster_render", "tri_raster_render_tex"} & set(g.launched)
+        assert "tri_raster_render" in g.launched and len(g.raster_calls) == 2 and all(n == 4 for _, n in g.raster_calls)      # four samples, both
         out.append((img.clone(), vis.clone(), pimg.clone(), pvis.clone()))
     for a, b in zip(*out):
         assert same_bytes(a, b)

@@ -1,4 +1,4 @@
-"""GPU: the metallic-roughness BRDF on the device - tri_raster_render_brdf (the BRDF resolve kernels of csrc/raster.hip) against its
+"""GPU: the metallic-roughness BRDF on the device - tri_raster_render with TRI_MESH_PBR (the BRDF resolve kernels of csrc/raster.hip) against its
 torch restatement, which tests/test_brdf_cpu.py ties to float64 and to closed forms.  The scenes are that file's.  Visibility must be
 equal; colours may differ by 1 LSB, the allowance of tests/test_gpu_raster.py (the device's fp32 operations are the restatement's,
 each rounded on its own, so in practice they are equal; the count of differing values is printed and 0 is expected).  The same
@@ -111,7 +111,8 @@ def test_guard_bands_around_the_brdf_render(samples):
             mip = ops.render_views_textured(*mesh, *tex, c, 32, 48, return_visibility=True, samples=samples, mips=mips, normals=vn, brdf=pbr)
             assert all(hasattr(y, "_band") for y in flat + smooth + tx + mip)
             results.append([t.cpu() for t in flat + smooth + tx + mip])
-        assert set(g.launched) == {"tri_raster_render_brdf"}
+        assert set(g.launched) == {"tri_raster_render"} and len(g.raster_calls) == 4
+        assert all(fields & _C.TRI_MESH_PBR and n == samples for fields, n in g.raster_calls)     # every call declared mat_pbr: the BRDF resolve
     assert all(gb.same_bytes(a, b) for a, b in zip(*results))
     for k, (mode, smooth) in enumerate((("plain", False), ("plain", True), ("textured", False), ("mip", True))):
         want = tb.render(host, cam, 32, 48, mode=mode, samples=samples, smooth=smooth)
@@ -123,13 +124,44 @@ def test_a_null_mat_pbr_is_refused_and_nothing_is_launched():
     batch = tb.pack([s], DEV)
     cam = s["cam"][None].to(DEV)
     image = torch.full((1, 1, 3, 16, 16), 77, dtype=torch.uint8, device=DEV)
-    ws = torch.zeros((max(16, _C.lib().tri_raster_workspace(1, 1, 1, 16, 16)),), dtype=torch.uint8, device=DEV)
+    ws = torch.zeros((max(16, _C.lib().tri_raster_workspace(1, 1, 1, 16, 16, 1)),), dtype=torch.uint8, device=DEV)
     ptr = _C.ptr
-    args = [ptr(t) for t in batch.tensors] + [None] * 5 + [0, None, None, None]
-    tail = [ptr(cam), 1, 1, 1, 16, 16, R.YFOV, R.ZNEAR, 1, ptr(ws), ptr(image), None, None]
-    assert _C.lib().tri_raster_render_brdf(*args, None, *tail) == _C.TRI_ERR_ARG
+    desc = _C.TriMeshBatch(*(ptr(t) for t in batch.tensors), 1, fields=_C.TRI_MESH_PBR)          # mat_pbr declared, and null
+    tail = [ptr(cam), 1, 1, 16, 16, R.YFOV, R.ZNEAR, 1, ptr(ws), ptr(image), None, None]
+    assert _C.lib().tri_raster_render(desc, *tail) == _C.TRI_ERR_ARG
+    assert "mat_pbr" in _C.lib().tri_last_error().decode()
     torch.cuda.synchronize()
     assert bool((image == 77).all()) and bool((ws == 0).all())
-    assert _C.lib().tri_raster_render_brdf(*args, ptr(batch.mat_pbr), *tail) == 0       # the same call with it runs
+    desc.mat_pbr = ptr(batch.mat_pbr)
+    assert _C.lib().tri_raster_render(desc, *tail) == 0                                 # the same call with it runs
     torch.cuda.synchronize()
     assert torch.equal(image.cpu(), ops.render_views(*batch.tensors, cam, 16, 16, brdf=batch.mat_pbr).cpu())
+
+
+@pytest.mark.parametrize("samples", [1, 4])
+def test_an_undeclared_group_is_not_read(samples):
+    """One triangle, one view, 16 x 16 (an edge pixel is partly covered, so four samples differ from one).  The descriptor carries
+    valid face_vn and mat_pbr pointers - banded allocations of their own - in its slots: with fields = 0 the call is the plain one,
+    byte for byte; with TRI_MESH_PBR declared it is brdf='s; with both groups declared it is normals= with brdf=."""
+    s = tn.scene("triangle")
+    batch = tb.pack([s], DEV)
+    cam = s["cam"][None].to(DEV)
+    vn, pbr = gb.banded(batch.face_vn, gb.POISON), gb.banded(batch.mat_pbr, gb.POISON)
+    lib, ptr = _C.lib(), _C.ptr
+    desc = _C.TriMeshBatch(*(ptr(t) for t in batch.tensors), 1, face_vn=ptr(vn), mat_pbr=ptr(pbr), fields=0)
+    want = {0: ops.render_views(*batch.tensors, cam, 16, 16, return_visibility=True, samples=samples),
+            _C.TRI_MESH_PBR: ops.render_views(*batch.tensors, cam, 16, 16, return_visibility=True, samples=samples, brdf=batch.mat_pbr),
+            _C.TRI_MESH_NORMALS | _C.TRI_MESH_PBR: ops.render_views(*batch.tensors, cam, 16, 16, return_visibility=True, samples=samples,
+                                                                    normals=batch.face_vn, brdf=batch.mat_pbr)}
+    assert not torch.equal(want[0][0], want[_C.TRI_MESH_PBR][0])
+    ws = torch.empty((max(16, lib.tri_raster_workspace(1, 1, 1, 16, 16, samples)),), dtype=torch.uint8, device=DEV)
+    for fields, (image, vis) in want.items():
+        desc.fields = fields
+        got, seen = torch.full_like(image, 77), torch.full_like(vis, -7)
+        assert lib.tri_raster_render(desc, ptr(cam), 1, 1, 16, 16, R.YFOV, R.ZNEAR, samples, ptr(ws), ptr(got), ptr(seen), _C.stream()) == 0
+        torch.cuda.synchronize()
+        assert gb.same_bytes(got, image) and gb.same_bytes(seen, vis), fields
+    assert not vn._band.damage() and not pbr._band.damage()
+    if samples == 4:
+        one = ops.render_views(*batch.tensors, cam, 16, 16)
+        assert want[0][1].shape == (1, 1, 16, 16, 4) and not torch.equal(one, want[0][0])        # the four-sample path is another picture

@@ -10,7 +10,7 @@ import torch
 from tests import test_mip_cpu as tm
 from tests import test_texture_cpu as tc
 from tests.guard_bands import POISON, ZERO, guarded_ops, same_bytes
-from tricolo_amd import ops
+from tricolo_amd import _C, ops
 from tricolo_amd.data import render as R
 from tricolo_amd.meshes import MeshBatch
 
@@ -143,7 +143,8 @@ def test_guard_bands():
             one = ops.render_views_textured(*t, *x, c, 32, 48, return_visibility=True, mips=mips)
             four = ops.render_views_textured(*t, *x, c, 32, 48, return_visibility=True, samples=4, mips=mips)
             assert all(hasattr(y, "_band") for y in one + four)
-        assert {"tri_texture_mips", "tri_raster_render_mip"} <= set(g.launched)
+        assert {"tri_texture_mips", "tri_raster_render"} <= set(g.launched)
+        assert [n for _, n in g.raster_calls] == [1, 4] and all(fields & _C.TRI_MESH_MIPS for fields, _ in g.raster_calls)      # the pyramid declared
         out.append((mip_texels.clone(), one[0].clone(), one[1].clone(), four[0].clone(), four[1].clone()))
     for a, b in zip(*out):
         assert same_bytes(a, b)

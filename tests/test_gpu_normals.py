@@ -1,4 +1,4 @@
-"""GPU: smooth shading on the device - tri_raster_render_smooth (the SMOOTH resolve kernels of csrc/raster.hip) and
+"""GPU: smooth shading on the device - tri_raster_render with TRI_MESH_NORMALS (the SMOOTH resolve kernels of csrc/raster.hip) and
 tri_mesh_vertex_normals (csrc/mesh_normals.hip) against their torch restatements, which tests/test_normals_cpu.py ties to float64.
 The scenes are that file's.  Visibility must be equal; colours may differ by 1 LSB, the allowance of tests/test_gpu_raster.py (the
 device's fp32 operations are the restatement's, so in practice they are equal; the count is printed).  Computed normals must carry
@@ -13,7 +13,7 @@ from tests import guard_bands as gb
 from tests import normals_reference as nr
 from tests import test_normals_cpu as tn
 from tests.test_gpu_mip import three_meshes
-from tricolo_amd import ops
+from tricolo_amd import _C, ops
 from tricolo_amd.data import render as R
 
 pytestmark = pytest.mark.gpu
@@ -130,7 +130,8 @@ def test_guard_bands_around_the_smooth_render(samples):
             plain = ops.render_views(*mesh, c, 32, 48, return_visibility=True, samples=samples, normals=vn)
             mip = ops.render_views_textured(*mesh, *tex, c, 32, 48, return_visibility=True, samples=samples, mips=mips, normals=vn)
             results.append([t.cpu() for t in plain + mip])
-        assert "tri_raster_render_smooth" in g.launched and "tri_raster_render" not in g.launched
+        assert "tri_raster_render" in g.launched and len(g.raster_calls) == 2                    # normals declared, mat_pbr not: the SMOOTH resolve
+        assert all(fields & _C.TRI_MESH_NORMALS and not fields & _C.TRI_MESH_PBR and n == samples for fields, n in g.raster_calls)
     assert all(gb.same_bytes(a, b) for a, b in zip(*results))
     want = tn.render(host, cam, 32, 48, mode="plain", samples=samples, normals=host.face_vn)
     assert torch.equal(results[0][1], want[1]) and int((results[0][0].to(torch.int32) - want[0].to(torch.int32)).abs().max()) <= 1

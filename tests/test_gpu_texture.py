@@ -9,7 +9,7 @@ import torch
 
 from tests import test_texture_cpu as tc
 from tests.guard_bands import POISON, ZERO, guarded_ops, same_bytes
-from tricolo_amd import ops
+from tricolo_amd import _C, ops
 from tricolo_amd.data import render as R
 from tricolo_amd.meshes import MeshBatch
 
@@ -141,7 +141,8 @@ def test_guard_bands():
             img, vis = ops.render_views_textured(*t, *x, g.put(cam), 32, 48, return_visibility=True)
             colours = ops.mesh_face_colours(banded)
             assert hasattr(img, "_band") and hasattr(vis, "_band") and hasattr(colours, "_band")              # the outputs are banded too
-        assert {"tri_raster_render_tex", "tri_mesh_face_colours"} <= set(g.launched)
+        assert {"tri_raster_render", "tri_mesh_face_colours"} <= set(g.launched)
+        assert g.raster_calls == [(_C.TRI_MESH_TEXTURES, 1)]                                 # textures and no pyramid declared, one sample
         out.append((img.clone(), vis.clone(), colours.clone()))
     for a, b in zip(*out):
         assert same_bytes(a, b)

@@ -289,24 +289,57 @@ def test_refusals_before_anything_runs():
     check_refusals()
     # the C entry points themselves: sizes and counts are checked before any pointer is touched, so null pointers and no GPU will do
     lib = _C.lib()
-    null, pyramid, tail = [None] * 12, [None, None], [None, None, None, None]            # ... | workspace, image, visibility, stream
-    rc = lib.tri_raster_render_mip(*null, 0, *pyramid, None, 1, 200, 3, 13378, 13378, R.YFOV, R.ZNEAR, 4, *tail)
+    tail = [None, None, None, None]                                                      # workspace, image, visibility, stream
+
+    def null(N, T, fields=_C.TRI_MESH_TEXTURES | _C.TRI_MESH_MIPS):                      # every pointer null, textures and pyramid declared
+        return _C.TriMeshBatch(N=N, T=T, fields=fields)
+
+    rc = lib.tri_raster_render(null(1, 0), None, 200, 3, 13378, 13378, R.YFOV, R.ZNEAR, 4, *tail)
     assert rc == _C.TRI_ERR_UNSUPPORTED
     message = lib.tri_last_error().decode()
-    assert "tri_raster_render_mip" in message and "2^31 or more samples" in message and "split the batch" in message
-    assert lib.tri_raster_render_mip(*null, -1, *pyramid, None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG       # a negative texture count
-    assert lib.tri_raster_render_mip(*null, 0, *pyramid, None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 2, *tail) == _C.TRI_ERR_ARG        # two samples
+    assert "tri_raster_render" in message and "2^31 or more samples" in message and "split the batch" in message
+    assert lib.tri_raster_render(null(1, -1), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG       # a negative texture count
+    assert lib.tri_raster_render(null(1, 0), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 2, *tail) == _C.TRI_ERR_ARG        # two samples
     assert "samples must be 1 or 4" in lib.tri_last_error().decode()
-    assert lib.tri_raster_render_mip(*null, 3, *pyramid, None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG        # textures without their fields
+    assert lib.tri_raster_render(null(1, 3), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG        # textures without their fields
     assert "both pyramid fields" in lib.tri_last_error().decode()
-    assert lib.tri_raster_render_mip(*null, 0, *pyramid, None, 1, 200, 3, 8, 8, 4.0, R.ZNEAR, 4, *tail) != 0                       # yfov beyond pi
+    assert lib.tri_raster_render(null(1, 0), None, 200, 3, 8, 8, 4.0, R.ZNEAR, 4, *tail) != 0                       # yfov beyond pi
     for samples in (1, 4):
-        assert lib.tri_raster_render_mip(*null, 0, *pyramid, None, 0, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0            # nothing to draw: nothing runs
+        assert lib.tri_raster_render(null(0, 0), None, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0            # nothing to draw: nothing runs
     assert lib.tri_texture_mips(None, None, None, -1, 0, None, 0, None, None) == _C.TRI_ERR_ARG
     assert lib.tri_texture_mips(None, None, None, 2, -1, None, 3, None, None) == _C.TRI_ERR_ARG
     assert lib.tri_texture_mips(None, None, None, 2, 5, None, 7, None, None) == _C.TRI_ERR_ARG                                    # sizes without arrays
     assert "tri_texture_mips" in lib.tri_last_error().decode()
     assert lib.tri_texture_mips(None, None, None, 0, 0, None, 0, None, None) == 0                                                 # an empty pyramid: nothing runs
+
+
+def test_the_batch_descriptor_is_checked_by_one_rule_set_for_every_mesh_call():
+    """csrc/mesh_batch.h mb_from_abi: a null descriptor, a negative N, a group the callee does not take and a pyramid without textures are
+    TRI_ERR_ARG before anything runs (null pointers and no GPU will do), and the message begins with the callee's name."""
+    lib = _C.lib()
+    tail = [None, None, None, None]                                                      # workspace, image / grid, visibility / labels, stream
+
+    def null(N, T, fields):
+        return _C.TriMeshBatch(N=N, T=T, fields=fields)
+
+    assert lib.tri_raster_render(null(1, 0, _C.TRI_MESH_MIPS), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG     # a pyramid without textures
+    assert lib.tri_last_error().decode().startswith("tri_raster_render: ") and "TRI_MESH_TEXTURES" in lib.tri_last_error().decode()
+    assert lib.tri_raster_render(None, None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG                             # no descriptor
+    assert lib.tri_last_error().decode().startswith("tri_raster_render: ")
+    assert lib.tri_raster_render(null(1, 0, 16), None, 200, 3, 8, 8, R.YFOV, R.ZNEAR, 1, *tail) == _C.TRI_ERR_ARG                   # a bit no call takes
+    assert lib.tri_voxelize_meshes(null(1, 0, _C.TRI_MESH_PBR), None, 5, 32, 1, *tail) == _C.TRI_ERR_ARG                             # a group this call does not take
+    assert lib.tri_last_error().decode().startswith("tri_voxelize_meshes: ")
+    assert lib.tri_voxelize_meshes(None, None, 5, 32, 1, *tail) == _C.TRI_ERR_ARG
+    assert lib.tri_last_error().decode().startswith("tri_voxelize_meshes: ")
+    assert lib.tri_mesh_face_colours(null(1, 0, _C.TRI_MESH_TEXTURES | _C.TRI_MESH_MIPS), 5, None, None) == _C.TRI_ERR_ARG           # colours take textures, no pyramid
+    assert lib.tri_last_error().decode().startswith("tri_mesh_face_colours: ")
+    assert lib.tri_mesh_face_colours(null(1, 3, _C.TRI_MESH_TEXTURES), 5, None, None) == _C.TRI_ERR_ARG
+    assert "T > 0 needs all five texture fields" in lib.tri_last_error().decode() and "pyramid" not in lib.tri_last_error().decode()
+    for call in (lambda b: lib.tri_mesh_bbox(b, None, None), lambda b: lib.tri_mesh_face_cdf(b, None, 5, None, None, None),
+                 lambda b: lib.tri_mesh_sample_points(b, None, None, None, 5, 0, None, None, None),
+                 lambda b: lib.tri_mesh_vertex_normals(b, 5, 5, 0, None, None, None, None)):
+        assert call(None) == _C.TRI_ERR_ARG and call(null(1, 0, _C.TRI_MESH_NORMALS)) == _C.TRI_ERR_ARG
+        assert call(null(-1, 0, 0)) == _C.TRI_ERR_ARG and "negative size" in lib.tri_last_error().decode()
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the command line

@@ -369,23 +369,29 @@ def test_refusals():
 
 def test_entry_points_refuse_bad_arguments_before_anything_runs():
     lib = _C.lib()
-    mesh_and_textures, pyramid, tail, some = (None,) * 12, (None, None), (None, None, None, None), 64         # `some`: not null, never read
-    view = (None, 1, 200, 3, 8, 8, R.YFOV, R.ZNEAR)
-    assert lib.tri_raster_render_smooth(*mesh_and_textures, 0, *pyramid, None, *view, 1, *tail) == _C.TRI_ERR_ARG
+    tail, some = (None, None, None, None), 64                                                                 # `some`: not null, never read
+    TEX, VN = _C.TRI_MESH_TEXTURES, _C.TRI_MESH_NORMALS
+
+    def null(N, T, face_vn, fields=VN):                                                                       # every other pointer null
+        return _C.TriMeshBatch(N=N, T=T, face_vn=face_vn, fields=fields)
+
+    view = (None, 200, 3, 8, 8, R.YFOV, R.ZNEAR)
+    assert lib.tri_raster_render(null(1, 0, None), *view, 1, *tail) == _C.TRI_ERR_ARG
     assert "face_vn" in lib.tri_last_error().decode()
-    assert lib.tri_raster_render_smooth(*mesh_and_textures, 0, *pyramid, some, *view, 2, *tail) == _C.TRI_ERR_ARG                 # samples
-    assert lib.tri_raster_render_smooth(*mesh_and_textures, 3, *pyramid, some, *view, 1, *tail) == _C.TRI_ERR_ARG                 # textures without fields
-    assert lib.tri_raster_render_smooth(*mesh_and_textures, -1, *pyramid, some, *view, 4, *tail) == _C.TRI_ERR_ARG
-    assert lib.tri_raster_render_smooth(*mesh_and_textures, 0, *pyramid, some, None, 1, 200, 3, 8, 8, 4.0, R.ZNEAR, 1, *tail) != 0   # yfov beyond pi
+    assert lib.tri_raster_render(null(1, 0, some), *view, 2, *tail) == _C.TRI_ERR_ARG                         # samples
+    assert lib.tri_raster_render(null(1, 3, some, TEX | VN), *view, 1, *tail) == _C.TRI_ERR_ARG              # textures without fields
+    assert lib.tri_raster_render(null(1, -1, some), *view, 4, *tail) == _C.TRI_ERR_ARG
+    assert lib.tri_raster_render(null(1, 0, some), None, 200, 3, 8, 8, 4.0, R.ZNEAR, 1, *tail) != 0           # yfov beyond pi
     for samples in (1, 4):
-        assert lib.tri_raster_render_smooth(*mesh_and_textures, 0, *pyramid, some, None, 0, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0     # nothing to draw
+        assert lib.tri_raster_render(null(0, 0, some), None, 0, 3, 8, 8, R.YFOV, R.ZNEAR, samples, *tail) == 0     # nothing to draw
     assert lib.tri_mesh_vertex_normals_workspace(10) == 240 and lib.tri_mesh_vertex_normals_workspace(0) == 0 and lib.tri_mesh_vertex_normals_workspace(-5) == 0
-    assert lib.tri_mesh_vertex_normals(None, None, None, None, 1, -1, 5, 0, None, None, None, None) == _C.TRI_ERR_ARG
-    assert lib.tri_mesh_vertex_normals(None, None, None, None, 1, 5, 5, 2, None, None, None, None) == _C.TRI_ERR_ARG               # fill
-    assert lib.tri_mesh_vertex_normals(None, None, None, None, 1, 5, 5, 0, None, None, None, None) == _C.TRI_ERR_ARG               # faces without arrays
+    one, three = _C.TriMeshBatch(N=1), _C.TriMeshBatch(N=3)                                                   # null arrays, no optional group
+    assert lib.tri_mesh_vertex_normals(one, -1, 5, 0, None, None, None, None) == _C.TRI_ERR_ARG
+    assert lib.tri_mesh_vertex_normals(one, 5, 5, 2, None, None, None, None) == _C.TRI_ERR_ARG               # fill
+    assert lib.tri_mesh_vertex_normals(one, 5, 5, 0, None, None, None, None) == _C.TRI_ERR_ARG               # faces without arrays
     assert "tri_mesh_vertex_normals" in lib.tri_last_error().decode()
-    assert lib.tri_mesh_vertex_normals(None, None, None, None, 1, 5, 2 ** 31, 0, None, None, None, None) == _C.TRI_ERR_UNSUPPORTED
-    assert lib.tri_mesh_vertex_normals(None, None, None, None, 3, 5, 0, 1, None, None, None, None) == 0                            # no faces: nothing runs
+    assert lib.tri_mesh_vertex_normals(one, 5, 2 ** 31, 0, None, None, None, None) == _C.TRI_ERR_UNSUPPORTED
+    assert lib.tri_mesh_vertex_normals(three, 5, 0, 1, None, None, None, None) == 0                            # no faces: nothing runs
 
 
 # ---------------------------------------------------------------------------------------------------- the command line

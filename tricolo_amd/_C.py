@@ -41,11 +41,19 @@ class TriConvBnSums(C.Structure):
     _fields_ = [("y", C.c_void_p), ("relu_scale", C.c_void_p), ("relu_shift", C.c_void_p), ("relu_out", C.c_void_p), ("partial", C.c_void_p)]
 
 
+class TriMeshBatch(C.Structure):
+    """The packed mesh batch of include/tricolo_hip.h; `fields` declares which of the optional groups are there (TRI_MESH_*)."""
+    _fields_ = [(n, C.c_void_p) for n in ("verts", "faces", "vert_off", "face_off", "face_mat", "mat_kd", "mat_off")] + [("N", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("face_uv", "mat_tex", "texels", "tex_off", "tex_size")] + [("T", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("mip_texels", "mip_off", "face_vn", "mat_pbr")] + [("fields", C.c_uint)]
+
+
+TRI_MESH_TEXTURES, TRI_MESH_MIPS, TRI_MESH_NORMALS, TRI_MESH_PBR = 1, 2, 4, 8
 TRI_WGRAD_JOBS_MAX = 12
 TRI_ERR_ARG, TRI_ERR_UNSUPPORTED = -1, -2                   # common.h
 
 P, I, L, F, Z, DBL = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
-DP = C.POINTER(TriConvDesc)
+DP, MB = C.POINTER(TriConvDesc), C.POINTER(TriMeshBatch)
 
 # name -> (restype, argtypes); must list every symbol of include/tricolo_hip.h (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -149,23 +157,18 @@ SIGNATURES = {
     "tri_nn_dist2": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
     "tri_f1_counts": (I, [P, P, I, I, C.POINTER(F), I, P, P, P]),
     "tri_f1_finalize": (I, [P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
-    "tri_mesh_bbox": (I, [P, P, I, P, P]),
-    "tri_mesh_face_cdf": (I, [P, P, P, P, P, I, L, P, P, P]),
-    "tri_mesh_sample_points": (I, [P, P, P, P, P, P, P, I, I, C.c_ulonglong, P, P, P]),
-    "tri_raster_workspace": (Z, [L, I, I, I, I]),
-    "tri_raster_render": (I, [P, P, P, P, P, P, P, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
-    "tri_raster_render_tex": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
-    "tri_raster_workspace_aa": (Z, [L, I, I, I, I]),
-    "tri_raster_render_aa": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, L, I, I, I, DBL, DBL, P, P, P, P]),
+    "tri_mesh_batch_size": (Z, []),
+    "tri_mesh_bbox": (I, [MB, P, P]),
+    "tri_mesh_face_cdf": (I, [MB, P, L, P, P, P]),
+    "tri_mesh_sample_points": (I, [MB, P, P, P, I, C.c_ulonglong, P, P, P]),
+    "tri_raster_workspace": (Z, [L, I, I, I, I, I]),
+    "tri_raster_render": (I, [MB, P, L, I, I, I, DBL, DBL, I, P, P, P, P]),
     "tri_texture_mips": (I, [P, P, P, I, L, P, L, P, P]),
-    "tri_raster_render_mip": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
-    "tri_raster_render_smooth": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
-    "tri_raster_render_brdf": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, I, L, I, I, I, DBL, DBL, I, P, P, P, P]),
     "tri_mesh_vertex_normals_workspace": (Z, [L]),
-    "tri_mesh_vertex_normals": (I, [P, P, P, P, I, L, L, I, P, P, P, P]),
-    "tri_mesh_face_colours": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, L, P, P]),
+    "tri_mesh_vertex_normals": (I, [MB, L, L, I, P, P, P, P]),
+    "tri_mesh_face_colours": (I, [MB, L, P, P]),
     "tri_voxelize_workspace": (Z, [L, I, I]),
-    "tri_voxelize_meshes": (I, [P, P, P, P, P, P, P, P, I, L, I, I, P, P, P, P]),
+    "tri_voxelize_meshes": (I, [MB, P, L, I, I, P, P, P, P]),
     "tri_resize_bicubic_aa_workspace": (Z, [I, I, I, I]),
     "tri_resize_bicubic_aa_u8": (I, [P, I, I, I, P, I, I, P, P]),
     "tri_copy_segments": (I, [P, P, P, I, P]),

@@ -7,7 +7,11 @@
 // never reads beyond the mesh.  A mesh without vertices has nothing to clamp to - every kernel checks V > 0 first - and a mesh without
 // materials is grey 0.4.  The sampler has no use for materials and leaves the three material fields null.
 //
-// Textures (optional; the five fields are null and T is 0 in a batch packed without them).  face_uv fp32 [sumF][3][2] holds one (u, v)
+// The four groups after N are optional.  A caller hands the batch over as the TriMeshBatch of include/tricolo_hip.h, whose `fields`
+// DECLARES the groups that are there; mb_from_abi below is the only place a MeshBatch is filled from one, and a group that is not
+// declared reaches the kernels as null / T = 0, whatever its slots held.
+//
+// Textures (TRI_MESH_TEXTURES: the five fields and T).  face_uv fp32 [sumF][3][2] holds one (u, v)
 // per face corner in the order of `faces`; a face whose face_uv[f][0][0] is NaN has no texture coordinates (the host writes NaN into
 // all six values).  mat_tex int32 [sumM] names a material's texture by a BATCH-GLOBAL index, -1 = none; any other value is read as
 // unsigned and clamped to T - 1, and with T == 0 every material is untextured.  Texture t is the tex_size[t] = (height, width) texels
@@ -15,8 +19,8 @@
 // 0 is the top row of the image and v = 0 its bottom (the OBJ convention).  mb_tex_sample below is THE sampling rule - repeat wrap,
 // bilinear (mb_bilinear), no mip-maps - of the textured resolve pass of raster.hip and of its face colours.
 //
-// The mip pyramid (optional; the two fields are null in a batch without one; raster.hip's tri_texture_mips builds it and only its mip
-// resolve kernels read it).  Texture t of size (H0, W0) has L = floor(log2(max(H0, W0))) + 1 levels, level l of size
+// The mip pyramid (TRI_MESH_MIPS: the two fields; raster.hip's tri_texture_mips builds it and only its mip resolve kernels read it;
+// with T == 0 it may be null).  Texture t of size (H0, W0) has L = floor(log2(max(H0, W0))) + 1 levels, level l of size
 // (H_l, W_l) = (max(1, H0 >> l), max(1, W0 >> l)); level 0 is a copy of the texture.  mip_texels u8 [sumMipTexels][4] holds the chain
 // of texture t from mip_off[t] (int64 [T + 1]): its levels one after the other from level 0, each row major, RGBA with alpha 255.
 // There is NO table of level offsets: a kernel walks them from tex_size - level l starts sum_{k < l} H_k W_k texels into the chain, at
@@ -27,15 +31,12 @@
 // half rounded up; int64 holds it (2 * 255 * 2^48 < 2^63).  For power-of-two sizes that is the rounded mean of the 2^l x 2^l block.
 // mb_mip_sample is mb_tex_sample's rule on one level, with that level's own (H_l, W_l).
 //
-// Corner normals (optional; null when an initialiser stops at mip_off, as the sampler's, the voxeliser's and every raster entry point's
-// but tri_raster_render_smooth's and tri_raster_render_brdf's does).  face_vn fp32 [sumF][3][3] holds one normal per face corner in
-// the order of `faces`, indexed by global face like face_uv; a face whose face_vn[f][0][0] is NaN has no normals (the host writes NaN
+// Corner normals (TRI_MESH_NORMALS).  face_vn fp32 [sumF][3][3] holds one normal per face corner in the order of `faces`, indexed by global face like face_uv; a face whose face_vn[f][0][0] is NaN has no normals (the host writes NaN
 // into all nine values) and is shaded flat.  Normals need not be unit length.  They come from the `vn` lines of the OBJ file
 // (data/materials.py load_obj_normals) or from mesh_normals.hip (tri_mesh_vertex_normals: area-weighted, by vertex index); only the
 // SMOOTH resolve kernels of raster.hip read them.
 //
-// PBR factors (optional; null when an initialiser stops at face_vn, as every entry point's but tri_raster_render_brdf's does).  mat_pbr
-// fp32 [sumM][2] holds (metallic, roughness) per material, indexed like mat_kd by mat_off and the face's clamped material.  mb_face_pbr
+// PBR factors (TRI_MESH_PBR).  mat_pbr fp32 [sumM][2] holds (metallic, roughness) per material, indexed like mat_kd by mat_off and the face's clamped material.  mb_face_pbr
 // below reads them: metallic is clamped to [0, 1] and roughness to [0.04, 1], each as fminf(fmaxf(x, lo), hi), so a NaN takes the lower
 // bound; a mesh without materials takes (0.2, 0.8) beside its grey 0.4.  Only the BRDF resolve kernels of raster.hip read them.
 //
@@ -44,7 +45,9 @@
 // v_fmac_f32 in such a helper while the same expression in a kernel body stayed a multiply and an add.  With an fma the cross product
 // of a face with b == c is a rounding error instead of exactly 0, and the torch restatements could not form the same bits.
 #pragma once
+#include <stdio.h>
 #include "common.h"
+#include "../../include/tricolo_hip.h"
 
 #pragma clang fp contract(off)
 
@@ -59,17 +62,48 @@ struct MeshBatch {
     const float* __restrict__ mat_kd;
     const long* __restrict__ mat_off;
     int N;
-    const float* __restrict__ face_uv;              // the texture fields: null / 0 when an initialiser stops at N
+    const float* __restrict__ face_uv;              // the texture fields
     const int* __restrict__ mat_tex;
     const unsigned* __restrict__ texels;            // one RGBA texel per dword, R in the low byte
     const long* __restrict__ tex_off;
     const int* __restrict__ tex_size;
     int T;
-    const unsigned* __restrict__ mip_texels;        // the mip pyramid: null when an initialiser stops at T
+    const unsigned* __restrict__ mip_texels;        // the mip pyramid
     const long* __restrict__ mip_off;
-    const float* __restrict__ face_vn;              // the corner normals: null when an initialiser stops at mip_off
-    const float* __restrict__ mat_pbr;              // (metallic, roughness) per material: null when an initialiser stops at face_vn
+    const float* __restrict__ face_vn;              // the corner normals
+    const float* __restrict__ mat_pbr;              // (metallic, roughness) per material
 };
+
+static inline int mb_refuse(const char* who, const char* what) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    tri_set_error(msg);
+    return TRI_ERR_ARG;
+}
+
+// *out = the batch entry point `who` was handed, with the groups b->fields declares and every other group null / T = 0; allowed: the
+// TRI_MESH_* groups `who` takes.  THE rules of the descriptor (include/tricolo_hip.h states them for callers); TRI_ERR_ARG, with a
+// message that begins with `who`, for a descriptor that breaks one.
+static inline int mb_from_abi(const TriMeshBatch* b, const char* who, unsigned allowed, MeshBatch* out) {
+    if (!b) return mb_refuse(who, "the batch descriptor must not be null");
+    if (b->N < 0 || b->T < 0) return mb_refuse(who, "negative size");
+    if (b->fields & ~allowed) return mb_refuse(who, "the batch declares a field group that this call does not take");
+    const bool tex = b->fields & TRI_MESH_TEXTURES, mips = b->fields & TRI_MESH_MIPS;
+    if (mips && !tex) return mb_refuse(who, "TRI_MESH_MIPS needs TRI_MESH_TEXTURES");
+    if (tex && b->T > 0 && !(b->face_uv && b->mat_tex && b->texels && b->tex_off && b->tex_size && (!mips || (b->mip_texels && b->mip_off))))
+        return mb_refuse(who, mips ? "T > 0 needs all five texture fields and both pyramid fields" : "T > 0 needs all five texture fields");
+    if ((b->fields & TRI_MESH_NORMALS) && !b->face_vn) return mb_refuse(who, "face_vn must not be null");
+    if ((b->fields & TRI_MESH_PBR) && !b->mat_pbr) return mb_refuse(who, "mat_pbr must not be null");
+    *out = MeshBatch{b->verts, b->faces, b->vert_off, b->face_off, b->face_mat, b->mat_kd, b->mat_off, b->N};
+    if (tex) {
+        out->face_uv = b->face_uv; out->mat_tex = b->mat_tex; out->texels = (const unsigned*)b->texels;
+        out->tex_off = b->tex_off; out->tex_size = b->tex_size; out->T = b->T;
+    }
+    if (mips) { out->mip_texels = (const unsigned*)b->mip_texels; out->mip_off = b->mip_off; }
+    if (b->fields & TRI_MESH_NORMALS) out->face_vn = b->face_vn;
+    if (b->fields & TRI_MESH_PBR) out->mat_pbr = b->mat_pbr;
+    return TRI_OK;
+}
 
 // the mesh of global face gf: the largest n with face_off[n] <= gf (meshes without faces are stepped over)
 __device__ __forceinline__ int mb_mesh_of(const MeshBatch& m, long gf) {

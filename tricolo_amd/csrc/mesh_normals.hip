@@ -102,21 +102,23 @@ __global__ __launch_bounds__(MN_THREADS) void mesh_normals_write_kernel(MeshBatc
 
 extern "C" size_t tri_mesh_vertex_normals_workspace(long sumV) { return sumV > 0 ? (size_t)sumV * 24 : 0; }
 
-extern "C" int tri_mesh_vertex_normals(const float* verts, const int* faces, const long* vert_off, const long* face_off, int N, long sumV, long sumF,
-                                       int fill, void* workspace, const float* face_vn_in, float* face_vn_out, void* stream) {
-    if (N < 0 || sumV < 0 || sumF < 0) { tri_set_error("tri_mesh_vertex_normals: negative size"); return TRI_ERR_ARG; }
+extern "C" int tri_mesh_vertex_normals(const TriMeshBatch* batch, long sumV, long sumF, int fill, void* workspace, const float* face_vn_in,
+                                       float* face_vn_out, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_mesh_vertex_normals", 0, &m);
+    if (bad != TRI_OK) return bad;
+    if (sumV < 0 || sumF < 0) { tri_set_error("tri_mesh_vertex_normals: negative size"); return TRI_ERR_ARG; }
     if (fill != 0 && fill != 1) { tri_set_error("tri_mesh_vertex_normals: fill must be 0 (missing) or 1 (all)"); return TRI_ERR_ARG; }
     if (sumF >= (1L << 31) || sumV >= (1L << 31)) {
         tri_set_error("tri_mesh_vertex_normals: 2^31 or more faces or vertices in a batch");
         return TRI_ERR_UNSUPPORTED;
     }
-    if (sumF == 0 || N == 0) return TRI_OK;
-    if (!verts || !faces || !vert_off || !face_off || !face_vn_out || (sumV > 0 && !workspace)) {
+    if (sumF == 0 || m.N == 0) return TRI_OK;
+    if (!m.verts || !m.faces || !m.vert_off || !m.face_off || !face_vn_out || (sumV > 0 && !workspace)) {
         tri_set_error("tri_mesh_vertex_normals: the batch, the workspace and the output must not be null");
         return TRI_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    const MeshBatch m{verts, faces, vert_off, face_off, nullptr, nullptr, nullptr, N};
     const unsigned blocks = (unsigned)((sumF + MN_THREADS - 1) / MN_THREADS);
     if (sumV > 0) {
         const long n = sumV * 3;

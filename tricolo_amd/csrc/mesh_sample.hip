@@ -54,10 +54,14 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_bbox_kernel(const float* __re
     }
 }
 
-extern "C" int tri_mesh_bbox(const float* verts, const long* vert_off, int N, float* bbox, void* stream) {
-    if (N < 0) { tri_set_error("tri_mesh_bbox: negative size"); return TRI_ERR_ARG; }
-    for (long n0 = 0; n0 < N; n0 += MS_MAX_BLOCKS)
-        mesh_bbox_kernel<<<(unsigned)min((long)MS_MAX_BLOCKS, N - n0), MS_THREADS, 0, (hipStream_t)stream>>>(verts, vert_off, n0, bbox);
+extern "C" size_t tri_mesh_batch_size(void) { return sizeof(TriMeshBatch); }
+
+extern "C" int tri_mesh_bbox(const TriMeshBatch* batch, float* bbox, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_mesh_bbox", 0, &m);
+    if (bad != TRI_OK) return bad;
+    for (long n0 = 0; n0 < m.N; n0 += MS_MAX_BLOCKS)
+        mesh_bbox_kernel<<<(unsigned)min((long)MS_MAX_BLOCKS, m.N - n0), MS_THREADS, 0, (hipStream_t)stream>>>(m.verts, m.vert_off, n0, bbox);
     return tri_check_launch("tri_mesh_bbox");
 }
 
@@ -168,13 +172,16 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_cdf_apply_kernel(const long* 
     }
 }
 
-extern "C" int tri_mesh_face_cdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale, int N,
-                                 long max_faces, double* cdf, double* total, void* stream) {
-    if (N < 0 || max_faces < 0) { tri_set_error("tri_mesh_face_cdf: negative size"); return TRI_ERR_ARG; }
+extern "C" int tri_mesh_face_cdf(const TriMeshBatch* batch, const float* scale, long max_faces, double* cdf, double* total, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_mesh_face_cdf", 0, &m);
+    if (bad != TRI_OK) return bad;
+    if (max_faces < 0) { tri_set_error("tri_mesh_face_cdf: negative size"); return TRI_ERR_ARG; }
     if (max_faces >= (1L << 31)) { tri_set_error("tri_mesh_face_cdf: 2^31 or more faces in a mesh"); return TRI_ERR_UNSUPPORTED; }
+    const int N = m.N;
+    const long* face_off = m.face_off;
     if (N == 0) return TRI_OK;
     hipStream_t st = (hipStream_t)stream;
-    const MeshBatch m{verts, faces, vert_off, face_off, nullptr, nullptr, nullptr, N};
     // blockIdx.x walks the chunks of a mesh (grid-stride), blockIdx.y the meshes; max_faces (>= every mesh's face count) sizes the grid
     const long chunks = max(1L, min((max_faces + MS_CHUNK - 1) / MS_CHUNK, 4096L));
     const long per_launch = max(1L, min((long)MS_MAX_GRID_Y, (long)MS_MAX_BLOCKS / chunks));
@@ -273,15 +280,17 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_sample_kernel(MeshBatch m, co
     for (int j = t; j < cnt * 3; j += MS_THREADS) out[j] = sp[j];
 }
 
-extern "C" int tri_mesh_sample_points(const float* verts, const int* faces, const long* vert_off, const long* face_off, const float* scale,
-                                      const double* cdf, const double* total, int N, int S, unsigned long long seed, float* points,
-                                      long* face_idx, void* stream) {
-    if (N < 0 || S < 0) { tri_set_error("tri_mesh_sample_points: negative size"); return TRI_ERR_ARG; }
+extern "C" int tri_mesh_sample_points(const TriMeshBatch* batch, const float* scale, const double* cdf, const double* total, int S,
+                                      unsigned long long seed, float* points, long* face_idx, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_mesh_sample_points", 0, &m);
+    if (bad != TRI_OK) return bad;
+    if (S < 0) { tri_set_error("tri_mesh_sample_points: negative size"); return TRI_ERR_ARG; }
+    const int N = m.N;
     if (N == 0 || S == 0) return TRI_OK;
     const int tiles = (S + MS_TILE - 1) / MS_TILE;
     const long per_launch = max(1L, (long)MS_MAX_BLOCKS / tiles);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const MeshBatch m{verts, faces, vert_off, face_off, nullptr, nullptr, nullptr, N};
     for (long n0 = 0; n0 < N; n0 += per_launch) {
         const unsigned blocks = (unsigned)(min(per_launch, N - n0) * tiles);
         if (face_idx)

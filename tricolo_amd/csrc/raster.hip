@@ -21,7 +21,7 @@
 //     correctly rounded, e = eye - a, the normal is turned toward the eye by the sign of (cx ex + cy ey) + cz ez; with the light
 //     l = (0, 1, 0): ndl = max(+-cy / len, 0) (0 when len == 0), s = 0.1 + fl32(3 / pi) ndl, colour = clamp(Kd s, 0, 1),
 //     u8 = floor(255 colour + 0.5); background 255.
-//   textured shading (tri_raster_render_tex only; the batch's texture fields are laid out in mesh_batch.h): visibility is untouched.
+//   textured shading (TRI_MESH_TEXTURES only; the batch's texture fields are laid out in mesh_batch.h): visibility is untouched.
 //     The pixel's winning face is set up again (the snapped corners, d_i, 2A, the swap of corners 1 and 2 - their UVs swap with
 //     them), its three edge functions are formed at this pixel's centre in int64 and l_k = fl32(E_k) / fl32(2A) as for the depth; then
 //     w_k = l_k d_k,  d = (w0 + w1) + w2,  b_k = w_k / d (perspective-correct weights),  u = (b0 u0 + b1 u1) + b2 u2,  v likewise;
@@ -32,7 +32,7 @@
 //     samples at barycentric (1/3, 1/3, 1/3), (2/3, 1/6, 1/6), (1/6, 2/3, 1/6), (1/6, 1/6, 2/3) - u = (b0 u0 + b1 u1) + b2 u2 with the
 //     fp32 constants RS_B13, RS_B23, RS_B16 - summed in that order and multiplied by 0.25f; Kd for a face without a texture or with
 //     a sample that is not finite.
-//   four samples per pixel (tri_raster_render_aa only; everything above is untouched by it): the positions, in 1/256 pixel from the
+//   four samples per pixel (samples == 4 only; everything above is untouched by it): the positions, in 1/256 pixel from the
 //     pixel's top-left corner, are sample 0 (96, 32), 1 (224, 96), 2 (32, 160), 3 (160, 224) - the 4x rotated grid; the centre (128, 128)
 //     is not one of them.  Vertices are snapped to 1/256 pixel, so every position is an integer and coverage stays exact in int64.
 //     Coverage, depth and the key of a sample are the rules above evaluated at P = (256 px + ox, 256 py + oy) instead of the centre:
@@ -46,7 +46,7 @@
 //     four u8 colours: a multisample resolve for untextured faces, 4x supersampling for textured ones - no attribute is ever
 //     extrapolated outside its face.  The visibility output is int32 [N][views][H][W][4], the face at each sample.
 //   mip-mapped textures (tri_texture_mips builds the pyramid mesh_batch.h lays out - exact integer box means of level 0 - and
-//     tri_raster_render_mip alone reads it; everything above is untouched by it, visibility included).  A definition of our own:
+//     a TRI_MESH_MIPS render alone reads it; everything above is untouched by it, visibility included).  A definition of our own:
 //     nobody has compared a pixel of it with pyrender's mip-mapping.  At a position P - the pixel centre, or a sample's own position
 //     with four samples - where face f with texture t of size (H0, W0) and L levels won:
 //     (u, v) and d at P exactly as above (l_k, w_k = l_k d_k, d, b_k, u, v); a (u, v) that is not finite leaves the face untextured there.
@@ -63,7 +63,7 @@
 //     c_l = mb_mip_sample (mesh_batch.h) of level l at (u, v): mb_tex_sample's rule with the level's own (H_l, W_l).  g is linear in
 //     rho, not its logarithm, so that every step is reproducible; the selection is continuous and monotone in rho - at rho = 1, at
 //     every octave and at the top level - and within 0.087 of a level of the logarithm.  colour = clamp((Kd c) s, 0, 1) as above.
-//   smooth shading (tri_raster_render_smooth only; the batch's corner normals face_vn are laid out in mesh_batch.h; everything above
+//   smooth shading (TRI_MESH_NORMALS only; the batch's corner normals face_vn are laid out in mesh_batch.h; everything above
 //     is untouched by it, visibility included - the clear, faces and queue passes are the same kernels).  At a position P - the pixel
 //     centre, or a sample's own position with four samples - where face f won and f has normals (its marker is not NaN):
 //     the face is set up again, its edge functions are formed at P, and the perspective-correct weights are those of the textured
@@ -78,7 +78,7 @@
 //     silhouette, where the interpolated normal already points away from the eye.  The turn is ours; so is the reading that the
 //     reference's pyrender meshes are smooth-shaded (data/render.py).  With four samples an untextured face WITH normals is coloured
 //     per sample - its shade varies across the pixel - and no longer once per face; a face without normals keeps that path.
-//   the glTF metallic-roughness BRDF (tri_raster_render_brdf only; the batch's PBR factors mat_pbr are laid out in mesh_batch.h;
+//   the glTF metallic-roughness BRDF (TRI_MESH_PBR only; the batch's PBR factors mat_pbr are laid out in mesh_batch.h;
 //     everything above is untouched by it, visibility included - the clear, faces and queue passes are the same kernels).  The formulas
 //     are the glTF 2.0 specification's, the clamps of the cosines the Khronos glTF-WebGL-PBR reference shader's; that pyrender shades
 //     this way is a reading from memory nobody has checked (data/render.py).  At a position P - the pixel centre, or a sample's own
@@ -104,7 +104,7 @@
 //     No pow, exp or log; every root and quotient is the correctly rounded one (mb_sqrt, mb_div).
 //     Fallback: where a b_k is not finite, dist or hl is zero or not finite, or the len of the normal in use is zero or not finite (or
 //     the winner could not be set up again, which cannot happen), the position takes the Lambert colour u8(clamp(base s, 0, 1)) - what
-//     tri_raster_render_smooth (without normals: the plain, textured or mip-mapped call) writes there, bit for bit.
+//     the same batch without TRI_MESH_PBR writes there, bit for bit.
 //     With four samples every sample of every face is coloured at its own position - v varies across the pixel, so the once-per-face
 //     shortcut of untextured flat faces does not apply - and the pixel is still (c0 + c1 + c2 + c3 + 2) >> 2.
 //
@@ -850,16 +850,14 @@ static bool rs_sizes_ok(long sumF, int N, int views, int H, int W) {
     return N >= 0 && sumF >= 0 && views >= 0 && H >= 0 && W >= 0;
 }
 
-// keys (samples per pixel) | queue count (padded to 16 bytes) | queue; 0 for what rs_check refuses by its sizes
-static size_t rs_workspace(long sumF, int N, int views, int H, int W, int samples) {
-    if (!rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W * (double)samples >= (double)RS_MAX_PIXELS) return 0;
+static bool rs_samples_ok(int samples) { return samples == 1 || samples == 4; }
+
+// keys (samples per pixel) | queue count (padded to 16 bytes) | queue; 0 for what tri_raster_render refuses by its sizes.  Four samples
+// are four keys per pixel, so fewer than 2^31 SAMPLES.
+extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W, int samples) {
+    if (!rs_samples_ok(samples) || !rs_sizes_ok(sumF, N, views, H, W) || (double)N * views * H * W * (double)samples >= (double)RS_MAX_PIXELS) return 0;
     return (size_t)N * views * H * W * samples * 8 + 16 + (size_t)sumF * views * 8;
 }
-
-extern "C" size_t tri_raster_workspace(long sumF, int N, int views, int H, int W) { return rs_workspace(sumF, N, views, H, W, 1); }
-
-// the four-sample query: four keys per pixel, so fewer than 2^31 SAMPLES
-extern "C" size_t tri_raster_workspace_aa(long sumF, int N, int views, int H, int W) { return rs_workspace(sumF, N, views, H, W, 4); }
 
 // What every launch refuses before anything runs; samples: keys per pixel, 1 or 4.
 static int rs_check(int N, long sumF, int views, int H, int W, double yfov, double znear, int samples, const char* who) {
@@ -876,19 +874,6 @@ static int rs_check(int N, long sumF, int views, int H, int W, double yfov, doub
                       "split the batch", who);
         tri_set_error(msg);
         return TRI_ERR_UNSUPPORTED;
-    }
-    return TRI_OK;
-}
-
-// The texture arguments of entry point `who`: T and, for T > 0, the five texture fields (given: all of them are there); pyramid: the
-// two pyramid fields are among them.
-static int rs_check_textures(const char* who, int T, bool given, bool pyramid) {
-    char msg[200];
-    if (T < 0) { snprintf(msg, sizeof msg, "%s: negative size", who); tri_set_error(msg); return TRI_ERR_ARG; }
-    if (T > 0 && !given) {
-        snprintf(msg, sizeof msg, "%s: T > 0 needs all five texture fields%s", who, pyramid ? " and both pyramid fields" : "");
-        tri_set_error(msg);
-        return TRI_ERR_ARG;
     }
     return TRI_OK;
 }
@@ -935,38 +920,16 @@ static int rs_render(const MeshBatch& m, int mode, int samples, const float* cam
     return tri_check_launch(who);
 }
 
-extern "C" int tri_raster_render(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                 const float* mat_kd, const long* mat_off, const float* cam, int N, long sumF, int views, int H, int W,
-                                 double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
-    return rs_render(m, RS_PLAIN, 1, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, "tri_raster_render");
-}
-
-// the one-sample and the four-sample textured launches share their arguments
-static int rs_render_tex(const char* who, int samples, const float* verts, const int* faces, const long* vert_off, const long* face_off,
-                         const int* face_mat, const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex,
-                         const uint8_t* texels, const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
-                         int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, false);
+// THE render entry point: the batch's declared groups choose the resolve kernel (rs_render), TRI_MESH_MIPS and TRI_MESH_TEXTURES the mode.
+extern "C" int tri_raster_render(const TriMeshBatch* batch, const float* cam, long sumF, int views, int H, int W, double yfov, double znear,
+                                 int samples, void* workspace, uint8_t* image, int* visibility, void* stream) {
+    const char* who = "tri_raster_render";
+    if (!rs_samples_ok(samples)) { tri_set_error("tri_raster_render: samples must be 1 or 4"); return TRI_ERR_ARG; }
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, who, TRI_MESH_TEXTURES | TRI_MESH_MIPS | TRI_MESH_NORMALS | TRI_MESH_PBR, &m);
     if (bad != TRI_OK) return bad;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
-    return rs_render(m, RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
-}
-
-extern "C" int tri_raster_render_tex(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                     const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
-                                     int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    return rs_render_tex("tri_raster_render_tex", 1, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off,
-                         tex_size, T, cam, N, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream);
-}
-
-extern "C" int tri_raster_render_aa(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                    const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                    const long* tex_off, const int* tex_size, int T, const float* cam, int N, long sumF, int views, int H,
-                                    int W, double yfov, double znear, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    return rs_render_tex("tri_raster_render_aa", 4, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, face_uv, mat_tex, texels, tex_off,
-                         tex_size, T, cam, N, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream);
+    const int mode = (batch->fields & TRI_MESH_MIPS) ? RS_MIP : (batch->fields & TRI_MESH_TEXTURES) ? RS_TEX : RS_PLAIN;
+    return rs_render(m, mode, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
 }
 
 extern "C" int tri_texture_mips(const uint8_t* texels, const long* tex_off, const int* tex_size, int T, long sum_texels, const long* mip_off,
@@ -984,69 +947,13 @@ extern "C" int tri_texture_mips(const uint8_t* texels, const long* tex_off, cons
     return tri_check_launch("tri_texture_mips");
 }
 
-extern "C" int tri_raster_render_mip(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                     const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
-                                     const float* cam, int N, long sumF, int views, int H, int W, double yfov, double znear, int samples,
-                                     void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const char* who = "tri_raster_render_mip";
-    if (T >= 0 && samples != 1 && samples != 4) { tri_set_error("tri_raster_render_mip: samples must be 1 or 4"); return TRI_ERR_ARG; }
-    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size && mip_texels && mip_off, true);
+extern "C" int tri_mesh_face_colours(const TriMeshBatch* batch, long sumF, float* colours, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_mesh_face_colours", TRI_MESH_TEXTURES, &m);
     if (bad != TRI_OK) return bad;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
-                      (const unsigned*)mip_texels, mip_off};
-    return rs_render(m, RS_MIP, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
-}
-
-extern "C" int tri_raster_render_smooth(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                        const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                        const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
-                                        const float* face_vn, const float* cam, int N, long sumF, int views, int H, int W, double yfov,
-                                        double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const char* who = "tri_raster_render_smooth";
-    if (!face_vn) { tri_set_error("tri_raster_render_smooth: face_vn must not be null"); return TRI_ERR_ARG; }
-    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_smooth: samples must be 1 or 4"); return TRI_ERR_ARG; }
-    if (T > 0 && (mip_texels != nullptr) != (mip_off != nullptr)) {         // T == 0: an empty pyramid may be null, nothing is textured
-        tri_set_error("tri_raster_render_smooth: the two pyramid fields come together or not at all");
-        return TRI_ERR_ARG;
-    }
-    const bool pyramid = mip_texels && mip_off;
-    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, pyramid);
-    if (bad != TRI_OK) return bad;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
-                      (const unsigned*)mip_texels, mip_off, face_vn};
-    return rs_render(m, pyramid ? RS_MIP : RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
-}
-
-extern "C" int tri_raster_render_brdf(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                      const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                      const long* tex_off, const int* tex_size, int T, const uint8_t* mip_texels, const long* mip_off,
-                                      const float* face_vn, const float* mat_pbr, const float* cam, int N, long sumF, int views, int H, int W,
-                                      double yfov, double znear, int samples, void* workspace, uint8_t* image, int* visibility, void* stream) {
-    const char* who = "tri_raster_render_brdf";
-    if (!mat_pbr) { tri_set_error("tri_raster_render_brdf: mat_pbr must not be null"); return TRI_ERR_ARG; }
-    if (samples != 1 && samples != 4) { tri_set_error("tri_raster_render_brdf: samples must be 1 or 4"); return TRI_ERR_ARG; }
-    if (T > 0 && (mip_texels != nullptr) != (mip_off != nullptr)) {         // T == 0: an empty pyramid may be null, nothing is textured
-        tri_set_error("tri_raster_render_brdf: the two pyramid fields come together or not at all");
-        return TRI_ERR_ARG;
-    }
-    const bool pyramid = mip_texels && mip_off;
-    const int bad = rs_check_textures(who, T, face_uv && mat_tex && texels && tex_off && tex_size, pyramid);
-    if (bad != TRI_OK) return bad;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T,
-                      (const unsigned*)mip_texels, mip_off, face_vn, mat_pbr};
-    return rs_render(m, pyramid ? RS_MIP : RS_TEX, samples, cam, sumF, views, H, W, yfov, znear, workspace, image, visibility, stream, who);
-}
-
-extern "C" int tri_mesh_face_colours(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                     const float* mat_kd, const long* mat_off, const float* face_uv, const int* mat_tex, const uint8_t* texels,
-                                     const long* tex_off, const int* tex_size, int T, int N, long sumF, float* colours, void* stream) {
-    if (N < 0 || sumF < 0 || T < 0) { tri_set_error("tri_mesh_face_colours: negative size"); return TRI_ERR_ARG; }
+    if (sumF < 0) { tri_set_error("tri_mesh_face_colours: negative size"); return TRI_ERR_ARG; }
     if (sumF >= (1L << 31)) { tri_set_error("tri_mesh_face_colours: 2^31 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
-    const int bad = rs_check_textures("tri_mesh_face_colours", T, face_uv && mat_tex && texels && tex_off && tex_size, false);
-    if (bad != TRI_OK) return bad;
-    if (sumF == 0 || N == 0) return TRI_OK;
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N, face_uv, mat_tex, (const unsigned*)texels, tex_off, tex_size, T};
+    if (sumF == 0 || m.N == 0) return TRI_OK;
     mesh_face_colours_kernel<<<(unsigned)((sumF + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, (hipStream_t)stream>>>(m, sumF, colours);
     return tri_check_launch("tri_mesh_face_colours");
 }

@@ -304,10 +304,13 @@ extern "C" size_t tri_voxelize_workspace(long sumF, int N, int V) {
     return nvox * 16 + 3 * (nvox / 8) + 16 + (size_t)sumF * 4;           // sums | x, y, z bit rows | queue count (padded to 16 bytes) | queue
 }
 
-extern "C" int tri_voxelize_meshes(const float* verts, const int* faces, const long* vert_off, const long* face_off, const int* face_mat,
-                                   const float* mat_kd, const long* mat_off, const float* frame, int N, long sumF, int V, int fill,
-                                   void* workspace, uint8_t* grid, uint8_t* labels, void* stream) {
-    if (N < 0 || sumF < 0) { tri_set_error("tri_voxelize_meshes: negative size"); return TRI_ERR_ARG; }
+extern "C" int tri_voxelize_meshes(const TriMeshBatch* batch, const float* frame, long sumF, int V, int fill, void* workspace, uint8_t* grid,
+                                   uint8_t* labels, void* stream) {
+    MeshBatch m;
+    const int bad = mb_from_abi(batch, "tri_voxelize_meshes", 0, &m);
+    if (bad != TRI_OK) return bad;
+    const int N = m.N;
+    if (sumF < 0) { tri_set_error("tri_voxelize_meshes: negative size"); return TRI_ERR_ARG; }
     if (fill != 0 && fill != 1) { tri_set_error("tri_voxelize_meshes: fill must be 0 (surface) or 1 (carve)"); return TRI_ERR_ARG; }
     if (!vx_size_ok(V)) { tri_set_error("tri_voxelize_meshes: V must be 32, 64 or 128"); return TRI_ERR_UNSUPPORTED; }
     if (sumF >= VX_MAX_FACES) { tri_set_error("tri_voxelize_meshes: 2^24 or more faces in a batch"); return TRI_ERR_UNSUPPORTED; }
@@ -323,7 +326,6 @@ extern "C" int tri_voxelize_meshes(const float* verts, const int* faces, const l
     unsigned* queue = (unsigned*)(qcount + 2);
     const long nwords = 2 * nvox + 3 * (nvox / 64);
     const unsigned vblocks = (unsigned)((nvox + VX_THREADS - 1) / VX_THREADS);
-    const MeshBatch m{verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off, N};
     voxelize_clear_kernel<<<(unsigned)min((long)VX_CLEAR_BLOCKS, (nwords + VX_THREADS - 1) / VX_THREADS), VX_THREADS, 0, st>>>(acc, nwords, qcount);
     if (sumF > 0) {
         voxelize_faces_kernel<<<(unsigned)((sumF + VX_THREADS - 1) / VX_THREADS), VX_THREADS, 0, st>>>(m, frame, sumF, V, acc, qcount, queue,

@@ -1644,11 +1644,29 @@ def _mesh_batch(verts, faces, vert_off, face_off, scale=None, face_mat=None, mat
     return N
 
 
+def _mesh_desc(N, verts, faces, vert_off, face_off, face_mat=None, mat_kd=None, mat_off=None, textures=None, mips=None, normals=None,
+               brdf=None):
+    """The descriptor (include/tricolo_hip.h TriMeshBatch) of a batch whose tensors the caller has checked: the seven batch tensors
+    (None where a call has no use for one), then the optional groups - the five texture tensors, the pyramid pair, face_vn, mat_pbr -
+    each declared in `fields` when it is given.  The tensors must outlive the call the descriptor goes into."""
+    d = _C.TriMeshBatch(*(ptr(x) for x in (verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off)), N)
+    if textures is not None:
+        d.face_uv, d.mat_tex, d.texels, d.tex_off, d.tex_size = (ptr(x) for x in textures)
+        d.T, d.fields = textures[4].shape[0], d.fields | _C.TRI_MESH_TEXTURES
+    if mips is not None:
+        d.mip_texels, d.mip_off, d.fields = ptr(mips[0]), ptr(mips[1]), d.fields | _C.TRI_MESH_MIPS
+    if normals is not None:
+        d.face_vn, d.fields = ptr(normals), d.fields | _C.TRI_MESH_NORMALS
+    if brdf is not None:
+        d.mat_pbr, d.fields = ptr(brdf), d.fields | _C.TRI_MESH_PBR
+    return d
+
+
 def mesh_bbox(verts, vert_off):
     """verts fp32 [sumV, 3], vert_off int64 [N + 1] on the GPU -> bbox fp32 [N, 3, 2]: per-axis (min, max) over all vertices of a mesh."""
     N = _mesh_batch(verts, None, vert_off, None)
     bbox = torch.empty((N, 3, 2), dtype=torch.float32, device=verts.device)
-    check(lib().tri_mesh_bbox(ptr(verts), ptr(vert_off), N, ptr(bbox), stream()), "tri_mesh_bbox")
+    check(lib().tri_mesh_bbox(_mesh_desc(N, verts, None, vert_off, None), ptr(bbox), stream()), "tri_mesh_bbox")
     return bbox
 
 
@@ -1660,8 +1678,8 @@ def mesh_face_cdf(verts, faces, vert_off, face_off, scale=None, max_faces=None):
         max_faces = int((face_off[1:] - face_off[:-1]).max()) if N else 0
     cdf = torch.empty((faces.shape[0],), dtype=torch.float64, device=verts.device)
     total = torch.empty((N,), dtype=torch.float64, device=verts.device)
-    check(lib().tri_mesh_face_cdf(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(scale), N, int(max_faces), ptr(cdf), ptr(total),
-                                  stream()), "tri_mesh_face_cdf")
+    check(lib().tri_mesh_face_cdf(_mesh_desc(N, verts, faces, vert_off, face_off), ptr(scale), int(max_faces), ptr(cdf), ptr(total), stream()),
+          "tri_mesh_face_cdf")
     return cdf, total
 
 
@@ -1677,7 +1695,7 @@ def mesh_sample_points(verts, faces, vert_off, face_off, cdf, total, num_samples
         raise ValueError("num_samples must not be negative")
     points = torch.empty((N, S, 3), dtype=torch.float32, device=verts.device)
     idx = torch.empty((N, S), dtype=torch.int64, device=verts.device) if return_face_idx else None
-    check(lib().tri_mesh_sample_points(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(scale), ptr(cdf), ptr(total), N, S,
+    check(lib().tri_mesh_sample_points(_mesh_desc(N, verts, faces, vert_off, face_off), ptr(scale), ptr(cdf), ptr(total), S,
                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(points), ptr(idx), stream()), "tri_mesh_sample_points")
     return (points, idx) if return_face_idx else points
 
@@ -1689,9 +1707,8 @@ RENDER_MAX_PIXELS = 2 ** 31                                                     
 def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visibility, samples, normals=None, brdf=None):
     """The body of render_views and render_views_textured, whose own arguments are checked (batch: the seven tensors of the packed
     batch; textures: its five texture tensors, or None; mips: the checked pyramid pair, or None; normals: the checked face_vn, or
-    None; brdf: the checked mat_pbr, or None): the camera, the limits, then the one entry point of csrc/raster.hip for the mode -
-    tri_raster_render_brdf for every mode with brdf, tri_raster_render_smooth for every other mode with normals - or
-    data.render.render_views_cpu on CPU tensors."""
+    None; brdf: the checked mat_pbr, or None): the camera, the limits, then tri_raster_render of csrc/raster.hip, which takes its mode
+    from the groups the descriptor declares - or data.render.render_views_cpu on CPU tensors."""
     if cam.dtype != torch.float32 or cam.dim() != 3 or cam.shape[0] != N or cam.shape[2] != 12 or not cam.is_contiguous():
         raise ValueError(f"cam must be a contiguous float32 tensor of shape [{N}, views, 12], got {tuple(cam.shape)} {cam.dtype}")
     views, sumF, dev = cam.shape[1], batch[1].shape[0], batch[0].device
@@ -1709,26 +1726,12 @@ def _render(stage, N, batch, textures, mips, cam, H, W, yfov, znear, return_visi
                                 normals=normals, brdf=brdf)
     image = torch.empty((N, views, 3, H, W), dtype=torch.uint8, device=dev)
     vis = torch.empty((N, views, H, W) + ((4,) if samples == 4 else ()), dtype=torch.int32, device=dev) if return_visibility else None
-    size = (lib().tri_raster_workspace_aa if samples == 4 else lib().tri_raster_workspace)(sumF, N, views, H, W)
-    ws = torch.empty((max(16, size),), dtype=torch.uint8, device=dev)
-    mesh = [ptr(x) for x in batch]
-    tex = [ptr(x) for x in (textures or (None,) * 5)] + [textures[4].shape[0] if textures else 0]
-    view = [ptr(cam), N, sumF, views, H, W, float(yfov), float(znear)]
-    out = [ptr(ws), ptr(image), ptr(vis), stream()]
-    pyramid = [ptr(mips[0]), ptr(mips[1])] if mips is not None else [None, None]
-    if brdf is not None:
-        if brdf.shape[0] == 0:                                                      # a batch without a material: no row is ever read, but the
-            brdf = brdf.new_zeros((1, 2))                                           # entry point takes a null mat_pbr for "no BRDF"
-        name, args = "tri_raster_render_brdf", mesh + tex + pyramid + [ptr(normals), ptr(brdf)] + view + [samples] + out
-    elif normals is not None:
-        name, args = "tri_raster_render_smooth", mesh + tex + pyramid + [ptr(normals)] + view + [samples] + out
-    elif mips is not None:
-        name, args = "tri_raster_render_mip", mesh + tex + [ptr(mips[0]), ptr(mips[1])] + view + [samples] + out
-    elif samples == 4 or textures is not None:
-        name, args = "tri_raster_render_aa" if samples == 4 else "tri_raster_render_tex", mesh + tex + view + out
-    else:
-        name, args = "tri_raster_render", mesh + view + out
-    check(getattr(lib(), name)(*args), name)
+    ws = torch.empty((max(16, lib().tri_raster_workspace(sumF, N, views, H, W, samples)),), dtype=torch.uint8, device=dev)
+    if brdf is not None and brdf.shape[0] == 0:                                     # a batch without a material: no row is ever read, but the
+        brdf = brdf.new_zeros((1, 2))                                               # resolve kernel is chosen by a mat_pbr that is not null
+    desc = _mesh_desc(N, *batch, textures=textures, mips=mips, normals=normals, brdf=brdf)
+    check(lib().tri_raster_render(desc, ptr(cam), sumF, views, H, W, float(yfov), float(znear), samples, ptr(ws), ptr(image), ptr(vis), stream()),
+          "tri_raster_render")
     return (image, vis) if return_visibility else image
 
 
@@ -1935,7 +1938,7 @@ def mesh_vertex_normals(verts, faces, vert_off, face_off, face_vn=None, fill="mi
         return mesh_vertex_normals_cpu(verts, faces, vert_off, face_off, face_vn, fill == "all")
     out = torch.empty((sumF, 3, 3), dtype=torch.float32, device=verts.device)
     ws = torch.empty((max(16, lib().tri_mesh_vertex_normals_workspace(sumV)),), dtype=torch.uint8, device=verts.device)
-    check(lib().tri_mesh_vertex_normals(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), N, sumV, sumF, VERTEX_NORMAL_FILL[fill], ptr(ws),
+    check(lib().tri_mesh_vertex_normals(_mesh_desc(N, verts, faces, vert_off, face_off), sumV, sumF, VERTEX_NORMAL_FILL[fill], ptr(ws),
                                         ptr(face_vn), ptr(out), stream()), "tri_mesh_vertex_normals")
     return out
 
@@ -1949,7 +1952,7 @@ def mesh_face_colours(batch):
     if face_mat is None:
         raise ValueError("mesh_face_colours: the batch was packed without materials")
     N = _mesh_batch(verts, faces, vert_off, face_off, None, face_mat, mat_kd, mat_off, verts, stage="mesh_face_colours")
-    T = _mesh_textures("mesh_face_colours", faces, mat_kd, *batch.texture_tensors)
+    _mesh_textures("mesh_face_colours", faces, mat_kd, *batch.texture_tensors)
     sumF = faces.shape[0]
     if sumF >= 2 ** 31:
         raise ValueError("mesh_face_colours: 2^31 or more faces in one batch")
@@ -1957,8 +1960,8 @@ def mesh_face_colours(batch):
         from .data.render import mesh_face_colours_cpu
         return mesh_face_colours_cpu(*batch.tensors, *batch.texture_tensors)
     colours = torch.empty((sumF, 3), dtype=torch.float32, device=verts.device)
-    check(lib().tri_mesh_face_colours(*(ptr(x) for x in batch.tensors), *(ptr(x) for x in batch.texture_tensors), T, N, sumF, ptr(colours),
-                                      stream()), "tri_mesh_face_colours")
+    check(lib().tri_mesh_face_colours(_mesh_desc(N, *batch.tensors, textures=batch.texture_tensors), sumF, ptr(colours), stream()),
+          "tri_mesh_face_colours")
     return colours
 
 
@@ -1996,8 +1999,8 @@ def voxelize_meshes(verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off,
     grid = torch.empty((N, 4, V, V, V), dtype=torch.uint8, device=verts.device)
     labels = torch.empty((N, V, V, V), dtype=torch.uint8, device=verts.device) if return_labels else None
     ws = torch.empty((max(16, lib().tri_voxelize_workspace(sumF, N, V)),), dtype=torch.uint8, device=verts.device)
-    check(lib().tri_voxelize_meshes(ptr(verts), ptr(faces), ptr(vert_off), ptr(face_off), ptr(face_mat), ptr(mat_kd), ptr(mat_off), ptr(frame),
-                                    N, sumF, V, VOXELIZE_FILL[fill], ptr(ws), ptr(grid), ptr(labels), stream()), "tri_voxelize_meshes")
+    check(lib().tri_voxelize_meshes(_mesh_desc(N, verts, faces, vert_off, face_off, face_mat, mat_kd, mat_off), ptr(frame), sumF, V,
+                                    VOXELIZE_FILL[fill], ptr(ws), ptr(grid), ptr(labels), stream()), "tri_voxelize_meshes")
     return (grid, labels) if return_labels else grid
 
 
