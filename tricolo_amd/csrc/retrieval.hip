@@ -85,7 +85,12 @@ extern "C" int tri_retrieval_topk(const float* text, const float* shape, const i
     if (smem > 150 * 1024) { tri_set_error("tri_retrieval_topk: Ns + D > 19200 does not fit the per-query LDS ranking"); return TRI_ERR_UNSUPPORTED; }
     static size_t attr = 0;
     if (smem > attr) {
-        hipFuncSetAttribute((const void*)retrieval_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        // a runtime that declines the size must not be followed by a launch that asks for it
+        if (hipFuncSetAttribute((const void*)retrieval_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+            (void)hipGetLastError();
+            tri_set_error("tri_retrieval_topk: the runtime declined the per-query LDS ranking buffer (Ns + D too large for this device)");
+            return TRI_ERR_UNSUPPORTED;
+        }
         attr = smem;
     }
     retrieval_topk_kernel<<<Nq, 256, smem, (hipStream_t)stream>>>(text, shape, label, Ns, D, k, topk_idx, topk_sim, first_hit);
