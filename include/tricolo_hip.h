@@ -424,11 +424,14 @@ int tri_copy_segments(const void* const* srcs, void* const* dsts, const long* n,
 int tri_gru_bias_grads(const float* dbias, int nchunk, float* db_ih_f, float* db_hh_f, float* db_ih_r, float* db_hh_r, void* stream);
 
 /* ---- NT-Xent loss, forward + backward fused (tricolo/loss/nt_xent.py:24-74) ------------------------------------------ */
+/* One pair: loss (device scalar) = alpha * CE_rows(S) + (1 - alpha) * CE_cols(S), S = norm(za) norm(zb)^T / T; dza / dzb (optional,
+ * both or neither) = d loss / d za, zb.  1 <= B <= 8192, 1 <= D <= 2048 (TRI_ERR_ARG otherwise).  The M = 2 case of the all-pairs
+ * kernels below, with the same workspace layout: tri_ntxent_workspace(B, D) == tri_ntxent_multi_workspace(2, B, D). */
 size_t tri_ntxent_workspace(int B, int D);
 int tri_ntxent_fwd_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm, float* loss,
                        float* dza, float* dzb, void* workspace, size_t workspace_bytes, void* stream);
-/* gradient half alone, from the workspace a tri_ntxent_fwd_bwd(dza = dzb = NULL) call filled; dloss (optional DEVICE scalar)
- * = upstream d(total)/d(loss), folded in */
+/* gradient half alone, from the workspace a tri_ntxent_fwd_bwd(dza = dzb = NULL) call filled; dloss (optional DEVICE scalar,
+ * NULL = exactly 1) = upstream d(total)/d(loss), folded in */
 int tri_ntxent_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm, const float* dloss,
                    float* dza, float* dzb, const void* workspace, size_t workspace_bytes, void* stream);
 /* All pairs of a step at once (tricolo_net.py:56-63: the loss of every pair of modalities, summed): M = 2 or 3 embeddings
@@ -436,7 +439,8 @@ int tri_ntxent_bwd(const float* za, const float* zb, int B, int D, float tempera
  * side), 4 launches forward, 1 backward.  losses [P + 1] (device) = the pair losses in itertools.combinations order, then
  * their sum ((l0 + l1) + l2 in fp32, as Python's sum()).  The backward takes the upstream gradients of the pair losses
  * (HOST array of device scalars, NULL entries / NULL array = 0) and of the total (device scalar or NULL) and writes
- * dz[m] = sum over m's pairs.  B <= 512, D % 4 == 0, D <= 2048 (TRI_ERR_UNSUPPORTED otherwise: use the per-pair calls). */
+ * dz[m] = sum over m's pairs.  B <= 512, D % 4 == 0, 4 <= D <= 2048 (TRI_ERR_UNSUPPORTED otherwise: use the per-pair calls, which
+ * run the same kernels and past this range a tiled similarity kernel). */
 size_t tri_ntxent_multi_workspace(int M, int B, int D);
 int tri_ntxent_multi_fwd(const float* const* z, int M, int B, int D, float temperature, float alpha, int norm, float* losses,
                          void* workspace, size_t workspace_bytes, void* stream);

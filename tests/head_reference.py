@@ -15,8 +15,9 @@ NTX_EPS = 1e-12
 
 # (B, D): ntx_sim_kernel (64 x 64 LDS tiles, K chunks of 16) runs when B > 512 or D % 4 != 0
 NTX_TILED = [(70, 18), (130, 6), (513, 8)]
-# (B, D): ntx_grad_kernel / ntxm_grad_kernel register slots g[2..7] (D > 512)
+# (B, D): ntxm_grad_kernel register slots g[2..7] (D > 512), with one pair and with three
 NTX_WIDE = [(5, 2048), (9, 1284)]
+NTX_BATCH_LIMIT = (8192, 4)                       # the single-pair limit on B: ntxm_grad_kernel's coefficients fill 32 KiB of LDS
 NTX_ZERO_ROW = (6, 20)
 NTX_ZERO_ROW_INDEX = 2
 

@@ -58,7 +58,7 @@ def test_ntxent_tiled_similarity_kernel(B, D):
 
 
 def test_ntxent_tiled_similarity_kernel_without_normalise():
-    """ntx_sim_kernel reading za / zb themselves (norm=False: no l2norm_rows_kernel, ntx_grad_kernel without the Jacobian) at (70, 18),
+    """ntx_sim_kernel reading za / zb themselves (norm=False: no ntxm_l2norm_kernel, ntxm_grad_kernel without the Jacobian) at (70, 18),
     on rows normalised in float64 on the host so that the logits keep their scale."""
     B, D = hr.NTX_TILED[0]
     za, zb = [hr.normalise_rows_f64_to_f32(z) for z in hr.ntx_inputs(B, D)]
@@ -69,8 +69,8 @@ def test_ntxent_tiled_similarity_kernel_without_normalise():
 
 @pytest.mark.parametrize("B,D", hr.NTX_WIDE)
 def test_ntxent_wide_rows(B, D):
-    """ntx_grad_kernel register slots g[2..7]: D = 2048 fills all eight (the limit), D = 1284 leaves slot 5 ragged and 6, 7 empty.
-    (ntx_sim_rows_kernel computes the similarities: B <= 512, D % 4 == 0.)"""
+    """ntxm_grad_kernel register slots g[2..7] with one pair: D = 2048 fills all eight (the limit), D = 1284 leaves slot 5 ragged and
+    6, 7 empty.  (ntxm_sim_rows_kernel computes the similarities: B <= 512, D % 4 == 0.)"""
     from oracle.modules import nt_xent_numpy
     za, zb = hr.ntx_inputs(B, D)
     loss, dza, dzb = ops.ntxent_fwd_bwd(za.to(DEV), zb.to(DEV), T, ALPHA)
@@ -103,9 +103,19 @@ def test_ntxent_all_pairs_wide_rows(B, D):
         np.testing.assert_allclose(dzs[m].cpu().numpy(), acc[m], rtol=0, atol=hr.NTX_GRAD_ATOL)
 
 
+def test_ntxent_at_the_batch_limit():
+    """(8192, 4), the single-pair limit on B: ntxm_grad_kernel's B coefficients are 32 KiB of LDS, the one shape at which its request
+    is near the 64 KiB a launch gets (two pairs' worth would not launch); ntx_sim_kernel computes the similarities."""
+    from oracle.modules import nt_xent_numpy
+    B, D = hr.NTX_BATCH_LIMIT
+    za, zb = hr.ntx_inputs(B, D)
+    loss, dza, dzb = ops.ntxent_fwd_bwd(za.to(DEV), zb.to(DEV), T, ALPHA)
+    check_ntxent(f"ntxent_limit_{B}x{D}", loss.item(), dza, dzb, nt_xent_numpy(za.numpy(), zb.numpy(), T, ALPHA))
+
+
 def test_ntxent_split_forward_backward_on_the_tiled_path():
     """ops.ntxent_fwd then ops.ntxent_bwd at (70, 18): ntx_sim_kernel fills the workspace, tri_ntxent_bwd reads S, the lse vectors, the
-    normalised rows and the norms back from it and ntx_grad_kernel folds dloss = 0.5 into its coefficients."""
+    normalised rows and the norms back from it and ntxm_grad_kernel folds dloss = 0.5 into its coefficients."""
     from oracle.modules import nt_xent_numpy
     B, D = hr.NTX_TILED[0]
     za, zb = hr.ntx_inputs(B, D)
@@ -117,7 +127,7 @@ def test_ntxent_split_forward_backward_on_the_tiled_path():
 
 
 def test_ntxent_all_zero_row():
-    """(6, 20) with row 2 of za zero, norm=True: l2norm_rows_kernel's max(|x|, eps) clamp and ntx_grad_kernel's 1 / max(norm, eps).  The
+    """(6, 20) with row 2 of za zero, norm=True: ntxm_l2norm_kernel's max(|x|, eps) clamp and ntxm_grad_kernel's 1 / max(norm, eps).  The
     loss is finite; row 2's gradient is da_hat / eps, O(1e11), compared relatively."""
     from oracle.modules import nt_xent_numpy
     B, D = hr.NTX_ZERO_ROW
@@ -134,11 +144,17 @@ def test_ntxent_all_zero_row():
 
 
 def test_ntxent_rejections():
-    """tri_ntxent_fwd_bwd's argument check (1 <= B <= 8192, 1 <= D <= 2048: ntx_grad_kernel holds a row in eight register slots and
-    B coefficients in LDS) and the all-pairs range."""
+    """The single-pair argument check (1 <= B <= 8192, 1 <= D <= 2048: ntxm_grad_kernel holds a row in eight register slots and
+    B coefficients per pair in LDS), in tri_ntxent_fwd_bwd and in tri_ntxent_bwd, and the all-pairs range."""
     for B, D in [(4, 2052), (4, 0), (8193, 4)]:
+        za, zb = torch.zeros(B, D, device=DEV), torch.zeros(B, D, device=DEV)
         with pytest.raises(RuntimeError, match="tri_ntxent"):
-            ops.ntxent_fwd_bwd(torch.zeros(B, D, device=DEV), torch.zeros(B, D, device=DEV), T, ALPHA)
+            ops.ntxent_fwd_bwd(za, zb, T, ALPHA)
+        with pytest.raises(RuntimeError, match="tri_ntxent"):
+            ops.ntxent_fwd(za, zb, T, ALPHA)
+        ws = torch.empty(ops.lib().tri_ntxent_workspace(B, D), dtype=torch.uint8, device=DEV)
+        with pytest.raises(RuntimeError, match="tri_ntxent"):
+            ops.ntxent_bwd(za, zb, ws, T, ALPHA)
     assert not ops.ntxent_multi_supported(8, 2, 3)
     assert not ops.ntxent_multi_supported(8, 2052, 3)
     assert not ops.ntxent_multi_supported(513, 512, 3)

@@ -2,14 +2,19 @@
 //
 // Replaces the ~15 torch launches per modality pair of /root/reference/tricolo/loss/nt_xent.py:55-74
 // (2x normalize, eye, 2x matmul, 2x div, 2x log_softmax, 2x mul/sum, axpy) and their autograd graph with five
-// small launches: row-normalise (x2), S = a_hat b_hat^T / T in exact fp32 (LDS-tiled FMA: the all-pairs matrix is
-// tiny, parity matters more than MFMA here), row/column log-sum-exp with wave shuffles, scalar loss, and the
-// gradient  dS = [alpha (softmax_row - I) + (1 - alpha)(softmax_col - I)] / B  contracted on the fly with the
-// other modality and pushed through the normalise Jacobian - S^T is never materialised or recomputed.
+// small launches: row-normalise, S = a_hat b_hat^T / T in exact fp32 FMAs (the matrix is tiny, parity matters more
+// than MFMA here), row/column log-sum-exp with wave shuffles, the loss sums, and the gradient
+// dS = [alpha (softmax_row - I) + (1 - alpha)(softmax_col - I)] / B  contracted on the fly with the other modality
+// and pushed through the normalise Jacobian - S^T is never materialised or recomputed.
+//
+// One kernel set over NtxMulti, the modality / pair index a grid dimension: the all-pairs calls run M = 2 or 3 modalities,
+// the single-pair calls (tri_ntxent_fwd_bwd, tri_ntxent_bwd) are its M = 2 case with one pair.
+#include <stdio.h>
 #include "common.h"
 #include "../../include/tricolo_hip.h"
 
-// S[i][j] = <a_i, b_j> * inv_T ; 64x64 tile per block, 4x4 outputs per thread, K chunks of 16
+// S[i][j] = <a_i, b_j> * inv_T ; 64x64 tile per block, 4x4 outputs per thread, K chunks of 16.  The single-pair calls' similarity
+// outside the row kernel's range (B > 512 or D % 4 != 0); the all-pairs calls refuse that range, so it has no pair dimension.
 __global__ __launch_bounds__(256) void ntx_sim_kernel(const float* __restrict__ a, const float* __restrict__ b, int B, int D, float inv_T,
                                                       float* __restrict__ S) {
     __shared__ float sa[16][65], sb[16][65];
@@ -44,202 +49,6 @@ __global__ __launch_bounds__(256) void ntx_sim_kernel(const float* __restrict__ 
         }
 }
 
-// Small batches (the per-GPU batch of the training step): the 64x64 tiling above would run on one or a handful of CUs.
-// One block per row i keeps a_i in LDS; each wave takes columns j = wave, wave + 4, ... four at a time (16-byte loads of
-// b_j along D, 8 independent loads in flight), reduces with wave shuffles.  D % 4 == 0.
-__global__ __launch_bounds__(256) void ntx_sim_rows_kernel(const float* __restrict__ a, const float* __restrict__ b, int B, int D,
-                                                           float inv_T, float* __restrict__ S) {
-    extern __shared__ float sa[];
-    const int i = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    for (int k = t * 4; k < D; k += 1024) *(float4*)(sa + k) = *(const float4*)(a + (long)i * D + k);
-    __syncthreads();
-    for (int jb = wave * 4; jb < B; jb += 16) {
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = lane * 4; k < D; k += 256) {
-            const float4 av = *(const float4*)(sa + k);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = jb + u < B ? jb + u : B - 1;
-                const float4 bv = *(const float4*)(b + (long)j * D + k);
-                acc[u] = fmaf(av.x, bv.x, fmaf(av.y, bv.y, fmaf(av.z, bv.z, fmaf(av.w, bv.w, acc[u]))));
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float v = wave_sum(acc[u]);
-            if (lane == 0 && jb + u < B) S[(long)i * B + jb + u] = v * inv_T;
-        }
-    }
-}
-
-__device__ __forceinline__ float block_max(float v, float* sh) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;
-}
-
-// one block per index i: lse over row i and over column i, and that row's loss contribution
-__global__ __launch_bounds__(256) void ntx_lse_kernel(const float* __restrict__ S, int B, float alpha, float* __restrict__ lse_row,
-                                                      float* __restrict__ lse_col, float* __restrict__ rowloss) {
-    __shared__ float sh[4];
-    const int i = blockIdx.x, t = threadIdx.x;
-    float mr = -INFINITY, mc = -INFINITY;
-    for (int j = t; j < B; j += 256) { mr = fmaxf(mr, S[(long)i * B + j]); mc = fmaxf(mc, S[(long)j * B + i]); }
-    mr = block_max(mr, sh);
-    mc = block_max(mc, sh);
-    float sr = 0.f, sc = 0.f;
-    for (int j = t; j < B; j += 256) { sr += expf(S[(long)i * B + j] - mr); sc += expf(S[(long)j * B + i] - mc); }
-    sr = block_sum(sr, sh);
-    sc = block_sum(sc, sh);
-    if (t == 0) {
-        float lr = mr + logf(sr), lc = mc + logf(sc), d = S[(long)i * B + i];
-        lse_row[i] = lr;
-        lse_col[i] = lc;
-        rowloss[i] = -(alpha * (d - lr) + (1.f - alpha) * (d - lc)) / (float)B;
-    }
-}
-
-__global__ void ntx_loss_sum_kernel(const float* __restrict__ rowloss, int B, float* __restrict__ loss) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s = 0.0;
-        for (int i = 0; i < B; ++i) s += (double)rowloss[i];      // fixed order: reproducible
-        *loss = (float)s;
-    }
-}
-
-// block (i, side): side 0 -> d a_i, side 1 -> d b_i
-__global__ __launch_bounds__(256) void ntx_grad_kernel(const float* __restrict__ S, const float* __restrict__ lse_row,
-                                                       const float* __restrict__ lse_col, const float* __restrict__ ahat,
-                                                       const float* __restrict__ bhat, const float* __restrict__ na,
-                                                       const float* __restrict__ nb, int B, int D, float inv_T, float alpha, int norm,
-                                                       float eps, float* __restrict__ dza, float* __restrict__ dzb,
-                                                       const float* __restrict__ dloss) {
-    extern __shared__ float w[];                 // [B] coefficients dS_ij (side 0) or dS_ji (side 1), times 1/T
-    __shared__ float sh[4];
-    const int i = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
-    const float invB = (dloss ? *dloss : 1.0f) / (float)B;      // upstream d(total)/d(loss) folded into the coefficients
-    for (int j = t; j < B; j += 256) {
-        float s, pr, pc;
-        if (side == 0) { s = S[(long)i * B + j]; pr = expf(s - lse_row[i]); pc = expf(s - lse_col[j]); }
-        else           { s = S[(long)j * B + i]; pr = expf(s - lse_row[j]); pc = expf(s - lse_col[i]); }
-        float delta = (i == j) ? 1.f : 0.f;
-        w[j] = (alpha * (pr - delta) + (1.f - alpha) * (pc - delta)) * invB * inv_T;
-    }
-    __syncthreads();
-    const float* other = side == 0 ? bhat : ahat;
-    const float* self = side == 0 ? ahat : bhat;
-    const float* nrm = side == 0 ? na : nb;
-    float* out = side == 0 ? dza : dzb;
-    float dot = 0.f;
-    float g[8];                                  // D <= 2048; fixed unroll keeps g[] in registers
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        int c = t + q * 256;
-        g[q] = 0.f;
-        if (c < D) {
-            float acc = 0.f;
-            for (int j = 0; j < B; ++j) acc = fmaf(w[j], other[(long)j * D + c], acc);
-            g[q] = acc;
-            dot += acc * self[(long)i * D + c];
-        }
-    }
-    float inv = 1.0f;
-    if (norm) {
-        dot = block_sum(dot, sh);
-        inv = 1.0f / fmaxf(nrm[i], eps);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        int c = t + q * 256;
-        if (c < D) out[(long)i * D + c] = norm ? (g[q] - self[(long)i * D + c] * dot) * inv : g[q];
-    }
-}
-
-__global__ void l2norm_rows_kernel(const float* __restrict__ x, int rows, int D, float eps, float* __restrict__ z, float* __restrict__ norm) {
-    int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const float* p = x + (long)row * D;
-    float s = 0.f;
-    for (int i = lane; i < D; i += 64) s += p[i] * p[i];
-    s = wave_sum(s);
-    float nrm = sqrtf(s);
-    float inv = 1.0f / fmaxf(nrm, eps);
-    for (int i = lane; i < D; i += 64) z[(long)row * D + i] = p[i] * inv;
-    if (lane == 0) norm[row] = nrm;
-}
-
-extern "C" size_t tri_ntxent_workspace(int B, int D) {
-    return 2 * al256((size_t)B * D * 4) + 5 * al256((size_t)B * 4) + al256((size_t)B * B * 4);
-}
-
-// loss (device scalar) = alpha * CE_rows(S) + (1 - alpha) * CE_cols(S),  S = norm(za) norm(zb)^T / T; dza / dzb (optional)
-// receive d loss / d za, d loss / d zb.  zis -> za, zjs -> zb in the reference's argument order (alpha is asymmetric).
-extern "C" int tri_ntxent_fwd_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm,
-                                  float* loss, float* dza, float* dzb, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 1 || D < 1 || D > 2048 || B > 8192) { tri_set_error("tri_ntxent: need 1<=B<=8192, 1<=D<=2048"); return TRI_ERR_ARG; }
-    if (workspace_bytes < tri_ntxent_workspace(B, D)) { tri_set_error("tri_ntxent: workspace too small"); return TRI_ERR_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    float* ahat = (float*)w; w += al256((size_t)B * D * 4);
-    float* bhat = (float*)w; w += al256((size_t)B * D * 4);
-    float* na = (float*)w; w += al256((size_t)B * 4);
-    float* nb = (float*)w; w += al256((size_t)B * 4);
-    float* lse_row = (float*)w; w += al256((size_t)B * 4);
-    float* lse_col = (float*)w; w += al256((size_t)B * 4);
-    float* rowloss = (float*)w; w += al256((size_t)B * 4);
-    float* S = (float*)w;
-    const float eps = 1e-12f;                       // F.normalize default (nt_xent.py:56-57)
-    const float* a = za;
-    const float* b = zb;
-    if (norm) {
-        l2norm_rows_kernel<<<(B + 3) / 4, 256, 0, s>>>(za, B, D, eps, ahat, na);
-        l2norm_rows_kernel<<<(B + 3) / 4, 256, 0, s>>>(zb, B, D, eps, bhat, nb);
-        a = ahat; b = bhat;
-    }
-    float inv_T = 1.0f / temperature;
-    if (B <= 512 && D % 4 == 0 && D <= 8192) ntx_sim_rows_kernel<<<B, 256, (size_t)D * sizeof(float), s>>>(a, b, B, D, inv_T, S);
-    else ntx_sim_kernel<<<dim3((B + 63) / 64, (B + 63) / 64), 256, 0, s>>>(a, b, B, D, inv_T, S);
-    ntx_lse_kernel<<<B, 256, 0, s>>>(S, B, alpha, lse_row, lse_col, rowloss);
-    ntx_loss_sum_kernel<<<1, 64, 0, s>>>(rowloss, B, loss);
-    if (dza && dzb)
-        ntx_grad_kernel<<<dim3(B, 2), 256, (size_t)B * sizeof(float), s>>>(S, lse_row, lse_col, a, b, na, nb, B, D, inv_T, alpha, norm,
-                                                                            eps, dza, dzb, nullptr);
-    return tri_check_launch("tri_ntxent_fwd_bwd");
-}
-
-// The gradient half on its own, for a `workspace` that a tri_ntxent_fwd_bwd(..., dza = dzb = NULL, ...) call filled: dza / dzb =
-// (*dloss) * d loss / d za, zb.  Lets autograd's backward launch ONE kernel per pair with the upstream scalar folded in
-// (no elementwise `grad * dloss` passes).
-extern "C" int tri_ntxent_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm,
-                              const float* dloss, float* dza, float* dzb, const void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 1 || D < 1 || D > 2048 || B > 8192) { tri_set_error("tri_ntxent: need 1<=B<=8192, 1<=D<=2048"); return TRI_ERR_ARG; }
-    if (workspace_bytes < tri_ntxent_workspace(B, D)) { tri_set_error("tri_ntxent: workspace too small"); return TRI_ERR_ARG; }
-    const char* w = (const char*)workspace;
-    const float* ahat = (const float*)w; w += al256((size_t)B * D * 4);
-    const float* bhat = (const float*)w; w += al256((size_t)B * D * 4);
-    const float* na = (const float*)w; w += al256((size_t)B * 4);
-    const float* nb = (const float*)w; w += al256((size_t)B * 4);
-    const float* lse_row = (const float*)w; w += al256((size_t)B * 4);
-    const float* lse_col = (const float*)w; w += al256((size_t)B * 4);
-    w += al256((size_t)B * 4);
-    const float* S = (const float*)w;
-    ntx_grad_kernel<<<dim3(B, 2), 256, (size_t)B * sizeof(float), (hipStream_t)stream>>>(
-        S, lse_row, lse_col, norm ? ahat : za, norm ? bhat : zb, na, nb, B, D, 1.0f / temperature, alpha, norm, 1e-12f, dza, dzb, dloss);
-    return tri_check_launch("tri_ntxent_bwd");
-}
-
-// ================================================================================================ all pairs of a step at once
 // TriCoLoNet._calculate_losses (tricolo_net.py:56-63) evaluates the loss for every pair of modalities and sums them: per pair
 // five launches here (fifteen in the reference), plus the additions, plus autograd's accumulation of the two gradients every
 // embedding receives - ~25 launches of ~5 us each, in series, with all three towers waiting.  The multi form does the same
@@ -256,11 +65,12 @@ struct NtxMulti {
     float* lse_col[NTX_MAX_MOD];
     float* rowloss[NTX_MAX_MOD];
     const float* dpair[NTX_MAX_MOD];     // backward: upstream gradient of each pair's loss (device scalars, may be NULL)
-    const float* dtotal;                 //           ... and of the total
+    const float* dtotal;                 //           ... and of the total (NULL: up0)
     float* dz[NTX_MAX_MOD];
     int pa[NTX_MAX_MOD], pb[NTX_MAX_MOD];
     int M, P, B, D, norm;
     float inv_T, alpha, eps;
+    float up0;                           // host-set upstream of the total when dtotal is NULL: 0, or 1 for a single-pair call without dloss
 };
 
 __global__ void ntxm_l2norm_kernel(const NtxMulti p) {
@@ -279,7 +89,9 @@ __global__ void ntxm_l2norm_kernel(const NtxMulti p) {
     if (lane == 0) p.nrm[m][row] = nrm;
 }
 
-// block (row i, pair q): the arithmetic of ntx_sim_rows_kernel
+// Small batches (the per-GPU batch of the training step): the 64x64 tiling above would run on one or a handful of CUs.
+// Block (row i, pair q) keeps a_i in LDS; each wave takes columns j = wave, wave + 4, ... four at a time (16-byte loads of
+// b_j along D, 8 independent loads in flight), reduces with wave shuffles.  D % 4 == 0.
 __global__ __launch_bounds__(256) void ntxm_sim_rows_kernel(const NtxMulti p) {
     extern __shared__ float sa[];
     const int i = blockIdx.x, q = blockIdx.y, t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -308,6 +120,7 @@ __global__ __launch_bounds__(256) void ntxm_sim_rows_kernel(const NtxMulti p) {
     }
 }
 
+// block (index i, pair q): lse over row i and over column i of S_q, and that row's loss contribution
 __global__ __launch_bounds__(256) void ntxm_lse_kernel(const NtxMulti p) {
     __shared__ float sh[4];
     const int i = blockIdx.x, q = blockIdx.y, t = threadIdx.x, B = p.B;
@@ -329,18 +142,18 @@ __global__ __launch_bounds__(256) void ntxm_lse_kernel(const NtxMulti p) {
 }
 
 // one wave per pair sums its row losses (double, fixed order per lane + shuffle tree: reproducible); thread 0 forms the total
-__global__ void ntxm_loss_sum_kernel(const NtxMulti p, float* __restrict__ losses) {
+// (write_total = 0: `losses` holds the pair losses only - the single-pair calls' one float)
+__global__ void ntxm_loss_sum_kernel(const NtxMulti p, float* __restrict__ losses, int write_total) {
     __shared__ float lp[NTX_MAX_MOD];
     const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (q < p.P) {
         double s = 0.0;
         for (int i = lane; i < p.B; i += 64) s += (double)p.rowloss[q][i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum_d(s);
         if (lane == 0) { lp[q] = (float)s; losses[q] = (float)s; }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && write_total) {
         float tot = 0.f;                                           // Python's sum(): ((0 + l0) + l1) + l2 in fp32
         for (int q2 = 0; q2 < p.P; ++q2) tot += lp[q2];
         losses[p.P] = tot;
@@ -349,17 +162,17 @@ __global__ void ntxm_loss_sum_kernel(const NtxMulti p, float* __restrict__ losse
 
 // block (row i, modality m): d z_m[i] summed over the pairs m takes part in
 __global__ __launch_bounds__(256) void ntxm_grad_kernel(const NtxMulti p) {
-    extern __shared__ float w[];                 // [2][B] coefficients of the (at most two) pairs of this modality
+    extern __shared__ float w[];                 // [np][B] coefficients dS_ij (alpha side) or dS_ji, times 1/T, of this modality's np <= 2 pairs
     __shared__ float sh[4];
     const int i = blockIdx.x, m = blockIdx.y, t = threadIdx.x, B = p.B, D = p.D;
     const float* other[2] = {nullptr, nullptr};
     int np = 0;
-    const float gt = p.dtotal ? *p.dtotal : 0.f;
+    const float gt = p.dtotal ? *p.dtotal : p.up0;
     for (int q = 0; q < p.P; ++q) {
         const int side = p.pa[q] == m ? 0 : (p.pb[q] == m ? 1 : -1);
         if (side < 0) continue;
         const float up = gt + (p.dpair[q] ? *p.dpair[q] : 0.f);
-        const float invB = up / (float)B;
+        const float invB = up / (float)B;         // upstream d(total)/d(loss) folded into the coefficients
         const float* S = p.S[q];
         const float* lr = p.lse_row[q];
         const float* lc = p.lse_col[q];
@@ -377,14 +190,14 @@ __global__ __launch_bounds__(256) void ntxm_grad_kernel(const NtxMulti p) {
     __syncthreads();
     const float* self = p.norm ? p.zhat[m] : p.z[m];
     float dot = 0.f;
-    float g[8];                                  // D <= 2048
+    float g[8];                                  // D <= 2048; fixed unroll keeps g[] in registers
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         int c = t + q * 256;
         g[q] = 0.f;
         if (c < D) {
             float tot = 0.f;
-            for (int k = 0; k < np; ++k) {       // pair by pair, each in the single-pair kernel's order, then summed
+            for (int k = 0; k < np; ++k) {       // pair by pair, then summed: with one pair tot = 0.f + acc
                 float acc = 0.f;
                 const float* ot = other[k];
                 const float* wk = w + k * B;
@@ -408,20 +221,28 @@ __global__ __launch_bounds__(256) void ntxm_grad_kernel(const NtxMulti p) {
     }
 }
 
-extern "C" size_t tri_ntxent_multi_workspace(int M, int B, int D) {
+static size_t ntx_workspace(int M, int B, int D) {
     const int P = M * (M - 1) / 2;
     return (size_t)M * (al256((size_t)B * D * 4) + al256((size_t)B * 4)) + (size_t)P * (3 * al256((size_t)B * 4) + al256((size_t)B * B * 4));
 }
 
-static int ntxm_setup(NtxMulti& p, const float* const* z, int M, int B, int D, float temperature, float alpha, int norm, void* workspace,
-                      size_t workspace_bytes) {
+// multi: the fused range of the all-pairs forms (the row similarity kernel's); the single-pair forms take any 1 <= D <= 2048 and B up to 8192
+static int ntx_setup(NtxMulti& p, const float* const* z, int M, int B, int D, float temperature, float alpha, int norm, void* workspace,
+                     size_t workspace_bytes, bool multi) {
+    const char* who = multi ? "tri_ntxent_multi" : "tri_ntxent";
+    char msg[160];
     if (M < 2 || M > NTX_MAX_MOD) { tri_set_error("tri_ntxent_multi: 2 or 3 modalities"); return TRI_ERR_ARG; }
-    if (B < 1 || B > 512 || D < 4 || D > 2048 || D % 4) { tri_set_error("tri_ntxent_multi: need 1<=B<=512, 4<=D<=2048, D%4==0 (else use tri_ntxent_fwd_bwd per pair)"); return TRI_ERR_UNSUPPORTED; }
-    if (!z || !workspace || workspace_bytes < tri_ntxent_multi_workspace(M, B, D)) { tri_set_error("tri_ntxent_multi: workspace too small"); return TRI_ERR_ARG; }
-    p.M = M; p.P = M * (M - 1) / 2; p.B = B; p.D = D; p.norm = norm; p.inv_T = 1.0f / temperature; p.alpha = alpha; p.eps = 1e-12f;
+    if (multi ? (B < 1 || B > 512 || D < 4 || D > 2048 || D % 4) : (B < 1 || B > 8192 || D < 1 || D > 2048)) {
+        tri_set_error(multi ? "tri_ntxent_multi: need 1<=B<=512, 4<=D<=2048, D%4==0 (else use tri_ntxent_fwd_bwd per pair)"
+                            : "tri_ntxent: need 1<=B<=8192, 1<=D<=2048");
+        return multi ? TRI_ERR_UNSUPPORTED : TRI_ERR_ARG;
+    }
+    if (!z || !workspace || workspace_bytes < ntx_workspace(M, B, D)) { snprintf(msg, sizeof(msg), "%s: workspace too small", who); tri_set_error(msg); return TRI_ERR_ARG; }
+    p.M = M; p.P = M * (M - 1) / 2; p.B = B; p.D = D; p.norm = norm; p.inv_T = 1.0f / temperature; p.alpha = alpha;
+    p.eps = 1e-12f;                                // F.normalize default (nt_xent.py:56-57)
     char* w = (char*)workspace;
     for (int m = 0; m < M; ++m) {
-        if (!z[m]) { tri_set_error("tri_ntxent_multi: NULL embedding"); return TRI_ERR_ARG; }
+        if (!z[m]) { snprintf(msg, sizeof(msg), "%s: NULL embedding", who); tri_set_error(msg); return TRI_ERR_ARG; }
         p.z[m] = z[m];
         p.zhat[m] = (float*)w; w += al256((size_t)B * D * 4);
         p.nrm[m] = (float*)w; w += al256((size_t)B * 4);
@@ -438,18 +259,66 @@ static int ntxm_setup(NtxMulti& p, const float* const* z, int M, int B, int D, f
     return 0;
 }
 
+// norm == 0: no normalise launch, the kernels read z, and zhat / nrm are never touched
+static int ntx_forward(const NtxMulti& p, float* losses, int write_total, hipStream_t s, const char* who) {
+    const int B = p.B, D = p.D;
+    if (p.norm) ntxm_l2norm_kernel<<<dim3((B + 3) / 4, p.M), 256, 0, s>>>(p);
+    if (B <= 512 && D % 4 == 0) ntxm_sim_rows_kernel<<<dim3(B, p.P), 256, (size_t)D * sizeof(float), s>>>(p);
+    else ntx_sim_kernel<<<dim3((B + 63) / 64, (B + 63) / 64), 256, 0, s>>>(p.norm ? p.zhat[0] : p.z[0], p.norm ? p.zhat[1] : p.z[1], B, D, p.inv_T, p.S[0]);
+    ntxm_lse_kernel<<<dim3(B, p.P), 256, 0, s>>>(p);
+    ntxm_loss_sum_kernel<<<1, 64 * NTX_MAX_MOD, 0, s>>>(p, losses, write_total);
+    return tri_check_launch(who);
+}
+
+static int ntx_backward(const NtxMulti& p, hipStream_t s, const char* who) {
+    const int np = p.M == 3 ? 2 : 1;               // pairs per modality: at B = 8192 one pair's coefficients are 32 KiB of the 64 KiB a launch gets
+    ntxm_grad_kernel<<<dim3(p.B, p.M), 256, (size_t)np * p.B * sizeof(float), s>>>(p);
+    return tri_check_launch(who);
+}
+
+extern "C" size_t tri_ntxent_workspace(int B, int D) { return ntx_workspace(2, B, D); }
+
+// loss (device scalar) = alpha * CE_rows(S) + (1 - alpha) * CE_cols(S),  S = norm(za) norm(zb)^T / T; dza / dzb (optional, both or
+// neither) receive d loss / d za, d loss / d zb.  zis -> za, zjs -> zb in the reference's argument order (alpha is asymmetric).
+extern "C" int tri_ntxent_fwd_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm,
+                                  float* loss, float* dza, float* dzb, void* workspace, size_t workspace_bytes, void* stream) {
+    NtxMulti p{};
+    const float* z[2] = {za, zb};
+    int rc = ntx_setup(p, z, 2, B, D, temperature, alpha, norm, workspace, workspace_bytes, false);
+    if (rc) return rc;
+    if (!loss) { tri_set_error("tri_ntxent_fwd_bwd: loss is NULL"); return TRI_ERR_ARG; }
+    rc = ntx_forward(p, loss, 0, (hipStream_t)stream, "tri_ntxent_fwd_bwd");
+    if (rc || !dza || !dzb) return rc;
+    p.dz[0] = dza; p.dz[1] = dzb;
+    p.up0 = 1.0f;
+    return ntx_backward(p, (hipStream_t)stream, "tri_ntxent_fwd_bwd");
+}
+
+// The gradient half on its own, for a `workspace` that a tri_ntxent_fwd_bwd(..., dza = dzb = NULL, ...) call filled: dza / dzb =
+// (*dloss) * d loss / d za, zb (dloss NULL: exactly 1).  Lets autograd's backward launch ONE kernel per pair with the upstream
+// scalar folded in (no elementwise `grad * dloss` passes).
+extern "C" int tri_ntxent_bwd(const float* za, const float* zb, int B, int D, float temperature, float alpha, int norm,
+                              const float* dloss, float* dza, float* dzb, const void* workspace, size_t workspace_bytes, void* stream) {
+    NtxMulti p{};
+    const float* z[2] = {za, zb};
+    int rc = ntx_setup(p, z, 2, B, D, temperature, alpha, norm, (void*)workspace, workspace_bytes, false);
+    if (rc) return rc;
+    if (!dza || !dzb) { tri_set_error("tri_ntxent_bwd: NULL gradient buffer"); return TRI_ERR_ARG; }
+    p.dz[0] = dza; p.dz[1] = dzb;
+    p.dpair[0] = dloss;
+    p.up0 = dloss ? 0.f : 1.0f;
+    return ntx_backward(p, (hipStream_t)stream, "tri_ntxent_bwd");
+}
+
+extern "C" size_t tri_ntxent_multi_workspace(int M, int B, int D) { return ntx_workspace(M, B, D); }
+
 // losses [P + 1] (device): the pair losses in combination order ((0,1), (0,2), (1,2)), then their sum
 extern "C" int tri_ntxent_multi_fwd(const float* const* z, int M, int B, int D, float temperature, float alpha, int norm, float* losses,
                                     void* workspace, size_t workspace_bytes, void* stream) {
     NtxMulti p{};
-    int rc = ntxm_setup(p, z, M, B, D, temperature, alpha, norm, workspace, workspace_bytes);
+    int rc = ntx_setup(p, z, M, B, D, temperature, alpha, norm, workspace, workspace_bytes, true);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (norm) ntxm_l2norm_kernel<<<dim3((B + 3) / 4, M), 256, 0, s>>>(p);
-    ntxm_sim_rows_kernel<<<dim3(B, p.P), 256, (size_t)D * sizeof(float), s>>>(p);
-    ntxm_lse_kernel<<<dim3(B, p.P), 256, 0, s>>>(p);
-    ntxm_loss_sum_kernel<<<1, 64 * NTX_MAX_MOD, 0, s>>>(p, losses);
-    return tri_check_launch("tri_ntxent_multi_fwd");
+    return ntx_forward(p, losses, 1, (hipStream_t)stream, "tri_ntxent_multi_fwd");
 }
 
 // dz[m] = sum over the pairs of m of (dtotal + dpair[pair]) * d loss_pair / d z_m, from the workspace the forward call filled
@@ -457,7 +326,7 @@ extern "C" int tri_ntxent_multi_bwd(const float* const* z, int M, int B, int D, 
                                     const float* const* dpair, const float* dtotal, float* const* dz, const void* workspace,
                                     size_t workspace_bytes, void* stream) {
     NtxMulti p{};
-    int rc = ntxm_setup(p, z, M, B, D, temperature, alpha, norm, (void*)workspace, workspace_bytes);
+    int rc = ntx_setup(p, z, M, B, D, temperature, alpha, norm, (void*)workspace, workspace_bytes, true);
     if (rc) return rc;
     if (!dz) { tri_set_error("tri_ntxent_multi_bwd: dz is NULL"); return TRI_ERR_ARG; }
     for (int m = 0; m < M; ++m) {
@@ -466,6 +335,5 @@ extern "C" int tri_ntxent_multi_bwd(const float* const* z, int M, int B, int D, 
     }
     for (int q = 0; q < p.P; ++q) p.dpair[q] = dpair ? dpair[q] : nullptr;
     p.dtotal = dtotal;
-    ntxm_grad_kernel<<<dim3(B, M), 256, (size_t)2 * B * sizeof(float), (hipStream_t)stream>>>(p);
-    return tri_check_launch("tri_ntxent_multi_bwd");
+    return ntx_backward(p, (hipStream_t)stream, "tri_ntxent_multi_bwd");
 }

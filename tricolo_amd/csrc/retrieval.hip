@@ -9,11 +9,6 @@
 #include "common.h"
 #include "../../include/tricolo_hip.h"
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // (sim, index) order of the reference ranking: larger sim first, equal sims -> larger index first
 __device__ __forceinline__ bool ranks_before(double sa, int ia, double sb, int ib) { return sa > sb || (sa == sb && ia > ib); }
 
@@ -33,7 +28,7 @@ __global__ __launch_bounds__(256) void retrieval_topk_kernel(const float* __rest
         const float* row = shape + (size_t)s * D;
         double acc = 0.0;
         for (int d = lane; d < D; d += 64) acc = fma(tq[d], (double)row[d], acc);
-        acc = wave_sum_f64(acc);
+        acc = wave_sum_d(acc);
         if (lane == 0) sims[s] = acc;
     }
     __syncthreads();

@@ -32,34 +32,6 @@ struct TrpMulti {
     double margin;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// 256 threads; sh holds 4 values
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ int block_sum_i(int v, int* sh) {
-    v = wave_sum_i(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;
-}
-
 // one wave per row, block (4 rows, modality m)
 __global__ __launch_bounds__(256) void trp_norm_kernel(const TrpMulti p) {
     const int m = blockIdx.y, row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;

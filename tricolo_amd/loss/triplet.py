@@ -10,6 +10,7 @@ import torch
 
 from .. import ops
 from ..layers import TriModule, require_gpu
+from .all_pairs import all_pairs
 
 
 class _TripletFn(torch.autograd.Function):
@@ -29,28 +30,6 @@ class _TripletFn(torch.autograd.Function):
         return dzis, dzls, None, None
 
 
-class _TripletAllFn(torch.autograd.Function):
-    """All pairs of M = 2 / 3 embeddings: outputs (loss_pair_0, ..., loss_pair_{P-1}, total)."""
-
-    @staticmethod
-    def forward(ctx, margin, module, *zs):
-        zs = tuple(z.contiguous() for z in zs)
-        losses, counts, ws = ops.triplet_multi_fwd(zs, margin)
-        module.last_counts = counts
-        ctx.save_for_backward(ws, *zs)
-        ctx.margin = margin
-        ctx.set_materialize_grads(False)             # unused outputs (normally every pair loss) arrive as None, not as zeros
-        return tuple(losses[i] for i in range(losses.numel()))
-
-    @staticmethod
-    def backward(ctx, *grads):
-        ws, *zs = ctx.saved_tensors
-        f = lambda g: None if g is None else g.contiguous().to(torch.float32)     # noqa: E731
-        dpairs = [f(g) for g in grads[:-1]]
-        dzs = ops.triplet_multi_bwd(zs, ws, ctx.margin, dpairs=dpairs if any(d is not None for d in dpairs) else None, dtotal=f(grads[-1]))
-        return (None, None, *dzs)
-
-
 class TripletLoss(TriModule):
     def __init__(self, margin):
         super().__init__()
@@ -68,9 +47,9 @@ class TripletLoss(TriModule):
         tricolo_net.py:59-61) and their sum, from ONE autograd node: 3 launches forward, 1 backward, each embedding's gradient
         already summed over its pairs.  Returns ([pair losses in combination order], total), or None when the shape is outside
         the fused kernels' range (callers then loop over forward())."""
-        zs = list(embeddings)
-        if not (all(z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.shape == zs[0].shape for z in zs)
-                and ops.triplet_multi_supported(zs[0].shape[0], zs[0].shape[1], len(zs))):
-            return None
-        out = _TripletAllFn.apply(float(self.margin), self, *zs)
-        return list(out[:-1]), out[-1]
+        margin = float(self.margin)
+
+        def fwd(zs):
+            losses, self.last_counts, ws = ops.triplet_multi_fwd(zs, margin)
+            return losses, ws
+        return all_pairs(embeddings, ops.triplet_multi_supported, fwd, lambda zs, ws, **up: ops.triplet_multi_bwd(zs, ws, margin, **up))

@@ -1452,17 +1452,28 @@ def ntxent_multi_supported(B: int, D: int, M: int) -> bool:
     return M in (2, 3) and 1 <= B <= 512 and 4 <= D <= 2048 and D % 4 == 0
 
 
-def ntxent_multi_fwd(zs, temperature, alpha, norm=True):
-    """Every pair of the M = 2 / 3 embeddings `zs` at once: (losses [P + 1] = pair losses in combination order, then their
-    sum; workspace for ntxent_multi_bwd)."""
+def _multi_args(zs, workspace=None, dpairs=None):
+    """The pair plumbing of the all-pairs calls over the M = 2 / 3 embeddings `zs`.  head = (zp, M, B, D) are their leading arguments
+    (zp: HOST array of the device pointers).  Forward (workspace = the library's size function): (head, P, losses [P + 1], workspace
+    tensor); backward: (head, dp, dzs, dzp) = HOST array of the upstream pair gradients (None without), the gradient tensors and
+    their HOST array."""
     M = len(zs)
     B, D = zs[0].shape
     P = M * (M - 1) // 2
-    losses = torch.empty((P + 1,), dtype=torch.float32, device=zs[0].device)
-    nbytes = lib().tri_ntxent_multi_workspace(M, B, D)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=zs[0].device)
-    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
-    check(lib().tri_ntxent_multi_fwd(zp, M, B, D, float(temperature), float(alpha), 1 if norm else 0, ptr(losses), ptr(ws), nbytes,
+    arr = lambda ts: (_C.C.c_void_p * len(ts))(*[ptr(t) for t in ts])     # noqa: E731
+    head = (arr([_f32(z) for z in zs]), M, B, D)
+    if workspace is not None:
+        losses = torch.empty((P + 1,), dtype=torch.float32, device=zs[0].device)
+        return head, P, losses, torch.empty((workspace(M, B, D),), dtype=torch.uint8, device=zs[0].device)
+    dzs = [torch.empty_like(z) for z in zs]
+    return head, arr(dpairs) if dpairs is not None else None, dzs, arr(dzs)
+
+
+def ntxent_multi_fwd(zs, temperature, alpha, norm=True):
+    """Every pair of the M = 2 / 3 embeddings `zs` at once: (losses [P + 1] = pair losses in combination order, then their
+    sum; workspace for ntxent_multi_bwd)."""
+    head, _, losses, ws = _multi_args(zs, lib().tri_ntxent_multi_workspace)
+    check(lib().tri_ntxent_multi_fwd(*head, float(temperature), float(alpha), 1 if norm else 0, ptr(losses), ptr(ws), ws.numel(),
                                      stream()), "tri_ntxent_multi_fwd")
     return losses, ws
 
@@ -1470,14 +1481,8 @@ def ntxent_multi_fwd(zs, temperature, alpha, norm=True):
 def ntxent_multi_bwd(zs, ws, temperature, alpha, norm=True, dpairs=None, dtotal=None):
     """Gradients of all M embeddings in one launch; dpairs (list of 0-d device tensors or None) / dtotal are the upstream
     gradients of the pair losses / of their sum."""
-    M = len(zs)
-    B, D = zs[0].shape
-    P = M * (M - 1) // 2
-    dzs = [torch.empty_like(z) for z in zs]
-    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
-    dp = (_C.C.c_void_p * P)(*[ptr(d) for d in dpairs]) if dpairs is not None else None
-    dzp = (_C.C.c_void_p * M)(*[ptr(d) for d in dzs])
-    check(lib().tri_ntxent_multi_bwd(zp, M, B, D, float(temperature), float(alpha), 1 if norm else 0, dp, ptr(dtotal), dzp, ptr(ws),
+    head, dp, dzs, dzp = _multi_args(zs, dpairs=dpairs)
+    check(lib().tri_ntxent_multi_bwd(*head, float(temperature), float(alpha), 1 if norm else 0, dp, ptr(dtotal), dzp, ptr(ws),
                                      ws.numel(), stream()), "tri_ntxent_multi_bwd")
     return dzs
 
@@ -1523,29 +1528,17 @@ def triplet_multi_supported(B: int, D: int, M: int) -> bool:
 def triplet_multi_fwd(zs, margin):
     """Every pair of the M = 2 / 3 embeddings `zs` at once: (losses [P + 1] = pair losses in combination order, then their
     sum; counts int32 [P, 2] = (|S|, |H|) per pair; workspace for triplet_multi_bwd)."""
-    M = len(zs)
-    B, D = zs[0].shape
-    P = M * (M - 1) // 2
-    losses = torch.empty((P + 1,), dtype=torch.float32, device=zs[0].device)
+    head, P, losses, ws = _multi_args(zs, lib().tri_triplet_multi_workspace)
     counts = torch.empty((P, 2), dtype=torch.int32, device=zs[0].device)
-    nbytes = lib().tri_triplet_multi_workspace(M, B, D)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=zs[0].device)
-    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
-    check(lib().tri_triplet_multi_fwd(zp, M, B, D, float(margin), ptr(losses), ptr(counts), ptr(ws), nbytes, stream()), "tri_triplet_multi_fwd")
+    check(lib().tri_triplet_multi_fwd(*head, float(margin), ptr(losses), ptr(counts), ptr(ws), ws.numel(), stream()), "tri_triplet_multi_fwd")
     return losses, counts, ws
 
 
 def triplet_multi_bwd(zs, ws, margin, dpairs=None, dtotal=None):
     """Gradients of all M embeddings in one launch; dpairs (list of 0-d device tensors or None) / dtotal are the upstream
     gradients of the pair losses / of their sum."""
-    M = len(zs)
-    B, D = zs[0].shape
-    P = M * (M - 1) // 2
-    dzs = [torch.empty_like(z) for z in zs]
-    zp = (_C.C.c_void_p * M)(*[ptr(_f32(z)) for z in zs])
-    dp = (_C.C.c_void_p * P)(*[ptr(d) for d in dpairs]) if dpairs is not None else None
-    dzp = (_C.C.c_void_p * M)(*[ptr(d) for d in dzs])
-    check(lib().tri_triplet_multi_bwd(zp, M, B, D, float(margin), dp, ptr(dtotal), dzp, ptr(ws), ws.numel(), stream()), "tri_triplet_multi_bwd")
+    head, dp, dzs, dzp = _multi_args(zs, dpairs=dpairs)
+    check(lib().tri_triplet_multi_bwd(*head, float(margin), dp, ptr(dtotal), dzp, ptr(ws), ws.numel(), stream()), "tri_triplet_multi_bwd")
     return dzs
 
 
