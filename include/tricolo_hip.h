@@ -73,6 +73,16 @@ int tri_embedding_bwd(const int* tokens, const float* dout, int B, int L, int V,
  * 0-based rank of the query's own shape label[q] in the full ordering (first_hit, may be NULL together with label). */
 int tri_retrieval_topk(const float* text, const float* shape, const int* label, int Nq, int Ns, int D, int k, int* topk_idx /* [Nq,k] */,
                        double* topk_sim /* [Nq,k] */, int* first_hit /* [Nq] */, void* stream);
+/* The same ranking for a gallery of any size (csrc/gallery.hip): a workgroup owns a tile of queries and streams the shape rows past
+ * them, keeping running top-k lists instead of a query's Ns similarities, so there is no limit on Ns.  Every similarity is the
+ * float64 value tri_retrieval_topk forms for the pair: wherever both accept a call they return the same bits.  1 <= k <= min(Ns,
+ * TRI_GALLERY_MAX_K); D <= 4096 (the float64 query tile takes at most 32 KiB of LDS: 8 queries per loaded shape row up to D = 512,
+ * 4 / 2 / 1 up to 1024 / 2048 / 4096).  label and first_hit may be NULL (first_hit needs label); a label outside [0, Ns) gives
+ * first_hit -1. */
+#define TRI_GALLERY_MAX_K 64
+int tri_retrieval_gallery(const float* text /* [Nq,D] */, const float* shape /* [Ns,D] */, const int* label /* [Nq] or NULL */, int Nq, int Ns,
+                          int D, int k, int* topk_idx /* [Nq,k] */, double* topk_sim /* [Nq,k] */, int* first_hit /* [Nq] or NULL */,
+                          void* stream);
 
 /* ---- dense layers with <= 64 rows (MLP heads at the per-GPU batch) ---------------------------------------------
  * nn.Linear forward / backward of sparse_cnn.py:39-44, mv_cnn.py:21-26, bigru.py:12, clip_text.py:9-14 in three launches,

@@ -5,7 +5,8 @@ model_id (:49-56), similarities are plain dot products on a float64 text matrix 
 ascending argsort flipped (:75-82, which fixes the tie order), RR@k counts queries with a correct shape in the top k.
 
 The ranking itself runs on the GPU: `tri_retrieval_topk` computes the float64 similarities, the five
-best shapes per query and the rank of the query's own shape in one launch (csrc/retrieval.hip); the host only builds the
+best shapes per query and the rank of the query's own shape in one launch (csrc/retrieval.hip; beyond its limit of Ns + D = 19200
+`tri_retrieval_gallery`, csrc/gallery.hip, which streams the shapes past a tile of queries); the host only builds the
 label tables from the model_id strings and turns [Nq,5] indices + [Nq] ranks into the four numbers.  There is no host
 ranking path in this package: without the HIP library / a GPU the call raises (the reference's numpy algorithm lives in
 oracle/retrieval.py, test infrastructure).  Unlike the reference it does not write nearest.jsonl into the CWD unless asked.
@@ -14,6 +15,7 @@ import json
 
 import numpy as np
 
+RETRIEVAL_TOPK_LIMIT = 19200            # tri_retrieval_topk keeps a query's Ns similarities and its D values in 150 KiB of LDS
 
 def construct_embeddings_matrix(dataset, embeddings_dict):
     tuples = embeddings_dict["caption_embedding_tuples"]
@@ -44,7 +46,9 @@ def nearest_neighbors_hip(shape, text, labels, n_neighbors):
     t = torch.from_numpy(np.ascontiguousarray(text, dtype=np.float32)).to(dev)     # the f64 text matrix holds f32 values
     s = torch.from_numpy(np.ascontiguousarray(shape, dtype=np.float32)).to(dev)
     lab = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
-    idx, sim, hit = ops.retrieval_topk(t, s, lab, n_neighbors)
+    # past the per-query LDS ranking's limit the tiled gallery kernel takes over (csrc/gallery.hip: any Ns, the same bits)
+    rank = ops.retrieval_topk if s.shape[0] + s.shape[1] <= RETRIEVAL_TOPK_LIMIT else ops.retrieval_gallery
+    idx, sim, hit = rank(t, s, lab, n_neighbors)
     return sim.cpu().numpy(), idx.cpu().numpy().astype(np.int64), hit.cpu().numpy().astype(np.int64)
 
 

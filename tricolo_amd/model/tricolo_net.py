@@ -247,12 +247,31 @@ class TriCoLoNet(TriModule):
     def test_step(self, data_dict, idx=0):
         self._stash(data_dict, self(data_dict))
 
-    def on_test_epoch_end(self):
+    def encode_text(self, data_dict):
+        """Text embeddings [B, D] of data_dict['tokens'], without autograd: the queries of evaluation.gallery.ShapeGallery."""
+        with torch.no_grad():
+            return self.text_encoder(data_dict["tokens"], data_dict)
+
+    def encode_shapes(self, data_dict):
+        """Shape embeddings [B, D] without autograd: image + voxel features, summed in that order and NOT re-normalised (the rule of
+        _collate_output, on the device).  Needs no captions: 'model_id' only gives the batch size."""
+        if self.image_encoder is None and self.voxel_encoder is None:
+            raise RuntimeError("encode_shapes: the net has neither an image nor a voxel tower")
+        with torch.no_grad():
+            s = None
+            if self.image_encoder is not None:
+                s = self.image_encoder(data_dict["images"].flatten(end_dim=1), data_dict)
+            if self.voxel_encoder is not None:
+                v = self.voxel_encoder(data_dict["voxels"], len(data_dict["model_id"]))
+                s = v if s is None else s + v
+            return s
+
+    def on_test_epoch_end(self, nearest_path=None):
         embeddings_dict = self._collate_output()
         self.val_test_step_outputs.clear()
         pr = None
         if self._cfg.inference.evaluate:
-            pr = compute_metrics(self._cfg.data.dataset, embeddings_dict, print_results=True)
+            pr = compute_metrics(self._cfg.data.dataset, embeddings_dict, print_results=True, nearest_path=nearest_path)
         if self._cfg.inference.save_predictions:
             os.makedirs(self._cfg.inference.output_dir, exist_ok=True)
             path = os.path.join(self._cfg.inference.output_dir, "output.p")

@@ -1301,6 +1301,22 @@ def retrieval_topk(text, shape, labels, k=5):
     return idx, sim, hit
 
 
+GALLERY_MAX_K, GALLERY_MAX_D = 64, 4096                 # TRI_GALLERY_MAX_K and the D bound of csrc/gallery.hip
+
+
+def retrieval_gallery(text, shape, labels=None, k=5):
+    """retrieval_topk for a gallery of any size (csrc/gallery.hip; k <= 64, D <= 4096), the same bits wherever both accept the call.
+    text [Nq,D], shape [Ns,D] fp32 on the GPU, labels [Nq] int32 or None -> (indices [Nq,k] i32, sims [Nq,k] f64, first_hit [Nq] i32 | None)."""
+    Nq, D = text.shape
+    Ns = shape.shape[0]
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=text.device)
+    sim = torch.empty((Nq, k), dtype=torch.float64, device=text.device)
+    hit = None if labels is None else torch.empty((Nq,), dtype=torch.int32, device=text.device)
+    check(lib().tri_retrieval_gallery(ptr(_f32(text)), ptr(_f32(shape)), ptr(labels), Nq, Ns, D, k, ptr(idx), ptr(sim), ptr(hit), stream()),
+          "tri_retrieval_gallery")
+    return idx, sim, hit
+
+
 # ------------------------------------------------------------------------------------------------ small dense layers
 def linear_small_supported(rows, K, N):
     return bool(lib().tri_linear_small_supported(int(rows), int(K), int(N)))

@@ -109,40 +109,54 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
 PACKED_DATASETS = ("Text2ShapeChairTable", "Text2ShapeC13")
 
 
-def main(argv=None):
+def check_dataset(cfg, program="tricolo_amd.train"):
+    if cfg.data.get("dataset") not in ("Synthetic",) + PACKED_DATASETS:
+        raise SystemExit(f"{program} reads data=synthetic and the packed Text2Shape sets {PACKED_DATASETS} "
+                         f"(data/dataset.py: <exp_data_root_path>/<category>/<model_id>.npz + <split>_map.json), not {cfg.data.get('dataset')!r}")
+
+
+def split_batches(cfg, split, shuffle_seed=None, drop_last=False):
+    """The batch source of one split, as fit() takes it (a callable epoch -> iterable of batch dicts); shared by train.main and
+    test.main.  Packed Text2Shape sets: PackedDataset(cfg, split) in file order, or shuffled per epoch with shuffle_seed.  The store
+    lives where the step runs; without a GPU it is still built (on the host) so that a data problem shows before anything else.
+    data=synthetic: split "train" is the 1024-shape training set, every other split its held-out set of 256 distinct shapes, two
+    captions each, in batches of min(data.batch_size, 64) on the GPU."""
+    if cfg.data.dataset in PACKED_DATASETS:
+        from .data.dataset import PackedDataset
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+        return PackedDataset(cfg, split, device=dev).batches(int(cfg.data.batch_size), shuffle_seed=shuffle_seed, drop_last=drop_last)
     from .data import synthetic as syn
+    V = cfg.data.voxel_size if cfg.model.voxel_encoder else None
+    nv = cfg.data.num_views if cfg.model.image_encoder else None
+    B = min(int(cfg.data.get("batch_size", 32)), 64)
+    if split == "train":
+        items = syn.make_factor_retrieval_set(1024, 2, V or 32, nv, cfg.data.image_size, seed=syn.BASE_SEED + 301, distinct=False)
+    else:
+        items = syn.make_factor_retrieval_set(256, 2, V or 32, nv, cfg.data.image_size, seed=syn.BASE_SEED + 302, distinct=True)
+
+    def gen(epoch):
+        import numpy as np
+        order = np.arange(len(items)) if shuffle_seed is None else np.random.default_rng(shuffle_seed + epoch).permutation(len(items))
+        stop = len(order) - len(order) % B if drop_last else len(order)
+        for i in range(0, stop, B):
+            yield syn.batch_to_device(syn.collate_items([items[j] for j in order[i:i + B]], voxel=V is not None, views=nv is not None), "cuda")
+    return gen
+
+
+def main(argv=None):
     from .model.tricolo_net import TriCoLoNet
     cfg = tcfg.compose(overrides=list(argv if argv is not None else sys.argv[1:]))
-    if cfg.data.get("dataset") not in ("Synthetic",) + PACKED_DATASETS:
-        raise SystemExit(f"tricolo_amd.train reads data=synthetic and the packed Text2Shape sets {PACKED_DATASETS} "
-                         f"(data/dataset.py: <exp_data_root_path>/<category>/<model_id>.npz + <split>_map.json), not {cfg.data.get('dataset')!r}")
+    check_dataset(cfg)
     torch.manual_seed(cfg.train_seed)
     net = TriCoLoNet(cfg)
     out = os.path.join(cfg.experiment_output_path, "training") if cfg.get("experiment_name") else None
     ckpt = os.path.join(out, cfg.ckpt_name) if (out and cfg.get("ckpt_name")) else None
-    if cfg.data.dataset in PACKED_DATASETS:
-        from .data.dataset import PackedDataset
-        # data_module.py:14-31: train split shuffled with drop_last, cfg.inference.split in file order.  The store lives where the step
-        # runs; without a GPU it is still built (on the host) so that a data problem shows before anything else - fit() itself needs the GPU.
-        dev = "cuda" if torch.cuda.is_available() else "cpu"
-        bs = int(cfg.data.batch_size)
-        train_set, val_set = PackedDataset(cfg, "train", device=dev), PackedDataset(cfg, cfg.inference.split, device=dev)
-        return fit(net, cfg, train_set.batches(bs, shuffle_seed=cfg.train_seed, drop_last=True), val_set.batches(bs), ckpt_path=ckpt,
-                   out_dir=out)
-    V = cfg.data.voxel_size if cfg.model.voxel_encoder else None
-    nv = cfg.data.num_views if cfg.model.image_encoder else None
-    B = min(int(cfg.data.get("batch_size", 32)), 64)
-    train = syn.make_factor_retrieval_set(1024, 2, V or 32, nv, cfg.data.image_size, seed=syn.BASE_SEED + 301, distinct=False)
-    held = syn.make_factor_retrieval_set(256, 2, V or 32, nv, cfg.data.image_size, seed=syn.BASE_SEED + 302, distinct=True)
-
-    def batches(items, shuffle_seed=None):
-        def gen(epoch):
-            import numpy as np
-            order = np.arange(len(items)) if shuffle_seed is None else np.random.default_rng(shuffle_seed + epoch).permutation(len(items))
-            for i in range(0, len(order) - B + 1, B):
-                yield syn.batch_to_device(syn.collate_items([items[j] for j in order[i:i + B]], voxel=V is not None, views=nv is not None), "cuda")
-        return gen
-    return fit(net, cfg, batches(train, cfg.train_seed), batches(held), ckpt_path=ckpt, out_dir=out)
+    # data_module.py:14-31: train split shuffled with drop_last, cfg.inference.split in file order (the synthetic sets have always
+    # dropped a ragged last batch of either split)
+    synthetic = cfg.data.dataset not in PACKED_DATASETS
+    train = split_batches(cfg, "train", shuffle_seed=cfg.train_seed, drop_last=True)
+    val = split_batches(cfg, "held_out" if synthetic else cfg.inference.split, drop_last=synthetic)
+    return fit(net, cfg, train, val, ckpt_path=ckpt, out_dir=out)
 
 
 if __name__ == "__main__":
