@@ -687,6 +687,20 @@ int tri_adam_step_segments(float* p, const void* grad_ptrs, const long* grad_sta
                            const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
                            void* stream);
 
+/* ---- Counter-based dropout (the Dropout(0.1) of the reference's clip_text.py / clip_img.py heads; csrc/dropout.hip) ------------ */
+/* used[0] = step[0]; step[0] += 1   (one thread; device int64 [1] each).  Stream-ordered: every later launch on `stream` that reads
+ * `used` sees the value of THIS forward, also when the launches are replayed from a HIP graph. */
+int tri_dropout_tick(long long* step, long long* used, void* stream);
+/* y[r][c] = x[r][c] * m(r, c),  m = 0 when dropped, `scale` when kept: ONE fp32 multiply per element (inf / NaN propagate as in torch:
+ * inf * 0 = NaN).  x, y: contiguous fp32 [rows][cols], distinct buffers, any cols >= 1, 4-byte alignment is all that is assumed
+ * (16-byte accesses only where cols % 4 == 0 and both pointers are 16-byte aligned).
+ * Element (r, c) is dropped iff  (w >> 8) < threshold,  w = word (c & 3) of Philox4x32-10(key = (seed & 0xffffffff, seed >> 32),
+ * counter = (c >> 2, (row0 + r) & 0xffffffff, used[0] & 0xffffffff, tower)).   threshold in [0, 2^24] = round(p * 2^24).
+ * Forward and backward are the same call (dx = dy * m).  rows == 0 returns success without a launch (pointers are not looked at);
+ * threshold > 2^24, cols < 1, rows < 0 or a null pointer is TRI_ERR_ARG. */
+int tri_dropout_apply(const float* x, float* y, long rows, int cols, unsigned threshold, float scale, unsigned long long seed,
+                      const long long* used, unsigned long long row0, unsigned tower, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,8 @@ SIGNATURES = {
     "tri_adam_guard_segments": (I, [P, P, I, L, P, P]),
     "tri_adam_step": (I, [P, P, P, P, L, P, F, P, F, F, F, F, F, P]),
     "tri_adam_step_segments": (I, [P, P, P, I, P, P, L, P, F, P, F, F, F, F, F, P]),
+    "tri_dropout_tick": (I, [P, P, P]),
+    "tri_dropout_apply": (I, [P, P, L, I, C.c_uint, F, C.c_ulonglong, P, C.c_ulonglong, C.c_uint, P]),
 }
 
 _lib = None

@@ -8,18 +8,21 @@ loading is `load_state_dict(strict=True)`; the only deliberate difference is `vo
 (in_features 512 instead of the reference's hard-coded 4096) - reported, not hidden.
 
 Known differences, handled explicitly:
-  * the reference's CLIPTextEncoder registers the frozen CLIP model as a submodule (clip_text.py:8), so its checkpoints carry
-    `text_encoder.clip_model.*` keys the MLP never uses: they are dropped on load (`ignored` in the return value) and, when
-    a checkpoint is written for the reference, copied through from `clip_state` if the caller has them;
+  * the reference's CLIPTextEncoder and CLIPImageEncoder register the frozen CLIP model as a submodule (clip_text.py:8,
+    clip_img.py:9 - the SAME module under both towers), so its checkpoints carry `text_encoder.clip_model.*` and
+    `image_encoder.clip_model.*` keys the MLPs never use: they are dropped on load under any prefix and, when a checkpoint is
+    written for the reference, copied through from `clip_state` if the caller has them - under `text_encoder.clip_model.` always
+    (as before) and under `image_encoder.clip_model.` too when the image tower is CLIPImageEncoder;
   * `TriCoLoNet.load_from_checkpoint` rebuilds the module from `hyper_parameters['cfg']` (tricolo_net.py:14) and reads it by
     ATTRIBUTE (`cfg.model.image_encoder`, tricolo_net.py:20-37) through `hydra.utils.instantiate`, i.e. it expects an OmegaConf
     DictConfig whose `_target_`s name the reference's classes.  save_reference_checkpoint therefore stores the net's config with
     every `tricolo_amd.*` target rewritten to its `tricolo.*` counterpart (FusedAdam -> torch.optim.Adam) as a DictConfig when
     omegaconf is importable (it is wherever the reference runs), else as a plain nested dict that `OmegaConf.create()` turns into
     one - in that case only the `state_dict` / `optimizer_states` halves are directly consumable by the reference;
-  * CLIPImageEncoder (config.yaml:86-89) is outside the hot path and is not built: a config that names it raises in
-    tricolo_amd.config.instantiate (no such class under tricolo_amd), it does not load silently.  TripletLoss (config.yaml:102-104) is
-    built (tricolo_amd.loss.triplet) and maps to tricolo.loss.triplet.TripletLoss like every other target.
+  * CLIPImageEncoder (config.yaml:86-89) is built (tricolo_amd.model.module.img_encoder.clip_img, keys
+    `image_encoder.mlp.{0,3}.{weight,bias}`; the step counter of its dropout is a non-persistent buffer and never enters a state
+    dict) and TripletLoss (config.yaml:102-104) is built (tricolo_amd.loss.triplet); both map to their tricolo.* counterparts like
+    every other target.
 Pure host code: no kernel is involved.
 """
 from __future__ import annotations
@@ -111,8 +114,9 @@ def load_reference_hparams(ckpt):
 def save_reference_checkpoint(net: torch.nn.Module, path, hyper_parameters=None, epoch: int = 0, global_step: int = 0,
                               optimizer=None, clip_state: dict | None = None, extra: dict | None = None) -> None:
     """Writes a Lightning-style file: the state dict under the reference's names (strictly loadable by the reference's modules),
-    `optimizer_states` in torch.optim.Adam's format when `optimizer` is given (FusedAdam.state_dict() speaks it), `clip_state` as the
-    `text_encoder.clip_model.*` tensors of a CLIP-text run, and the hyper-parameter slot of `save_hyperparameters()`
+    `optimizer_states` in torch.optim.Adam's format when `optimizer` is given (FusedAdam.state_dict() speaks it), `clip_state` (CLIP's own state dict, bare
+    or already prefixed) as the `text_encoder.clip_model.*` tensors of a CLIP run - and as `image_encoder.clip_model.*` as well when the
+    image tower is CLIPImageEncoder: the reference registers one CLIP module under both towers -, and the hyper-parameter slot of `save_hyperparameters()`
     (tricolo_net.py:14): by default reference_hparams(net._cfg) - reference `_target_`s, a DictConfig when omegaconf is importable
     (then `TriCoLoNet.load_from_checkpoint` of the reference can rebuild the module), a plain nested dict otherwise (module
     docstring)."""
@@ -125,8 +129,15 @@ def save_reference_checkpoint(net: torch.nn.Module, path, hyper_parameters=None,
         raise ValueError("hyper_parameters must hold 'cfg' (TriCoLoNet(**hyper_parameters), tricolo_net.py:12-14)")
     sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
     if clip_state:
-        sd.update({(k if k.startswith("text_encoder.clip_model.") else "text_encoder.clip_model." + k): v.detach().cpu()
-                   for k, v in clip_state.items()})
+        prefixes = ["text_encoder.clip_model."]
+        if type(getattr(net, "image_encoder", None)).__name__ == "CLIPImageEncoder":
+            prefixes.append("image_encoder.clip_model.")
+        for k, v in clip_state.items():
+            for known in ("text_encoder.clip_model.", "image_encoder.clip_model."):
+                if k.startswith(known):
+                    k = k[len(known):]
+            for prefix in prefixes:
+                sd[prefix + k] = v.detach().cpu()
     doc = {"state_dict": sd, "epoch": epoch, "global_step": global_step, "hyper_parameters": hyper_parameters,
            "pytorch-lightning_version": "2.0.0"}
     if optimizer is not None:

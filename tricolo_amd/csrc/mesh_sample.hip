@@ -195,18 +195,7 @@ extern "C" int tri_mesh_face_cdf(const TriMeshBatch* batch, const float* scale, 
 }
 
 // ---- the sampler -----------------------------------------------------------------------------------------------------------------------
-struct Philox4 { uint32_t x[4]; };
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
+// (Philox4x32-10: common.h)
 // One workgroup = MS_TILE consecutive samples of one mesh.  Every (MS_COARSE-th part of the) CDF's last entry is staged in LDS once per
 // workgroup; a sample's search is ~11 LDS steps and then log2(stride) dependent global loads instead of log2(F) of them, four samples
 // per thread in lockstep so that four such chains are in flight.  Points leave through LDS as consecutive dwords (a lane's own 12 bytes

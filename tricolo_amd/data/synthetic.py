@@ -109,9 +109,10 @@ def make_tokens(rng: np.random.Generator, vocab: int = DEFAULT_VOCAB, min_len: i
 
 def make_batch(batch_size: int, voxel_size: int | None = 32, num_views: int | None = 6, image_size: int = 128,
                vocab_size: int = DEFAULT_VOCAB, clip_text: bool = False, seed: int = BASE_SEED, rank: int = 0,
-               keep_grids: bool = False) -> dict:
+               keep_grids: bool = False, clip_img: bool = False) -> dict:
     """Batch dict with the keys of data_module.py:40-65 (`model_id`, `category`, `tokens`, `images`,
-    `voxels`={'locs','feats'}, optional `clip_embeddings_text`).  Per-rank seed = seed*1000 + rank."""
+    `voxels`={'locs','feats'}, optional `clip_embeddings_text` / `clip_embeddings_img`).  Per-rank seed = seed*1000 + rank.
+    clip_img is drawn after every other draw: switching it on moves no other tensor of the batch."""
     rng = np.random.default_rng(seed * 1000 + rank)
     d: dict = {"model_id": [f"syn{seed}_{rank}_{i:05d}" for i in range(batch_size)],
                "category": ["synthetic"] * batch_size}
@@ -137,6 +138,11 @@ def make_batch(batch_size: int, voxel_size: int | None = 32, num_views: int | No
         v = rng.integers(-1000, 1001, size=(batch_size, 768)).astype(np.float32)
         v /= np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)
         d["clip_embeddings_text"] = torch.from_numpy(v.astype(np.float32))
+    if clip_img:
+        # the view-averaged, unit-normalised CLIP image vector of extract_clip_feats.py:19-24, drawn like the text vector
+        v = rng.integers(-1000, 1001, size=(batch_size, 768)).astype(np.float32)
+        v /= np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)
+        d["clip_embeddings_img"] = torch.from_numpy(v.astype(np.float32))
     return d
 
 

@@ -129,6 +129,48 @@ class L2NormFn(torch.autograd.Function):
         return ops.l2norm_bwd(z, norm, dz)
 
 
+class DropoutFn(torch.autograd.Function):
+    """Counter-based dropout (csrc/dropout.hip): the forward ticks the device-side step counter and applies the mask of that step;
+    the backward applies the same mask to dy, read through the `used` its own forward saved - whatever ticked in between."""
+
+    @staticmethod
+    def forward(ctx, x, step, p, seed, row0, tower):
+        used = ops.dropout_tick(step)
+        ctx.save_for_backward(used)
+        ctx.args = (p, seed, row0, tower)
+        return ops.dropout_apply(x, p, seed, used, row0, tower)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (used,) = ctx.saved_tensors
+        p, seed, row0, tower = ctx.args
+        return ops.dropout_apply(dy, p, seed, used, row0, tower), None, None, None, None, None
+
+
+class CounterDropout(nn.Module):
+    """nn.Dropout(p) whose mask is a function of (seed, step, tower, global row, column) instead of the device generator's state:
+    the CPU restates it bit for bit (ops.dropout_mask), and a data-parallel caller that sets `row0 = rank * B_local` draws the rows
+    of the global batch.  `tower` keeps the streams of two heads apart (0 text, 1 image).  seed=None: torch.initial_seed() at
+    construction, so torch.manual_seed(cfg.train_seed) fixes the masks of a run.  `step` counts the train-mode forwards on the
+    device - a step replayed from a HIP graph draws a new mask every time - and is a NON-persistent buffer: the state-dict keys stay
+    the reference's, and a resumed run starts again at step 0.  Eval mode is the identity and launches nothing."""
+
+    def __init__(self, p=0.1, tower=0, seed=None):
+        super().__init__()
+        ops.dropout_threshold_scale(p)                                  # ValueError outside [0, 1]
+        self.p, self.tower, self.row0 = float(p), int(tower), 0
+        self.seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+        self.register_buffer("step", torch.zeros(1, dtype=torch.int64), persistent=False)
+
+    def extra_repr(self):
+        return f"p={self.p}, tower={self.tower}, seed={self.seed}"
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        return DropoutFn.apply(x, self.step, self.p, self.seed, self.row0, self.tower)
+
+
 class SideStream:
     """Weight-gradient side stream of a tower.  wgrad(layer) and dgrad(layer) both consume the same dy and are
     independent, and each leaves most CUs idle (latency-bound k-loops, few workgroups), so the tower's wgrad launches

@@ -107,7 +107,7 @@ class TriCoLoNet(TriModule):
         if not overlap:
             output_dict = {"text_features": self.text_encoder(tokens, data_dict)}
             if self.image_encoder is not None:
-                output_dict["image_features"] = self.image_encoder(data_dict["images"].flatten(end_dim=1), data_dict)
+                output_dict["image_features"] = self.image_encoder(self._images(data_dict), data_dict)
             if self.voxel_encoder is not None:
                 output_dict["voxel_features"] = self._gate(self.voxel_encoder(data_dict["voxels"], len(data_dict["model_id"])))
             return output_dict
@@ -163,7 +163,7 @@ class TriCoLoNet(TriModule):
         #  the step is the same, 2.486 against 2.477-2.493 ms)
         for which in order:
             if which == "i" and self.image_encoder is not None:
-                img = self.image_encoder(data_dict["images"].flatten(end_dim=1), data_dict)
+                img = self.image_encoder(self._images(data_dict), data_dict)
                 ops.stamp("image.fwd.end")
             else:
                 run_tower(which)
@@ -197,6 +197,14 @@ class TriCoLoNet(TriModule):
         for st in streams:
             if st is not None and st != cur:
                 cur.wait_stream(st)
+
+    def _images(self, data_dict):
+        """The image tower's first argument: the renderings as [B * Nv, 3, S, S] - or None when the batch has none and the tower is
+        CLIPImageEncoder, which reads data_dict["clip_embeddings_img"] and ignores it (a Bi(CLIP image, CLIP text) run opens no
+        rendering at all)."""
+        if data_dict.get("images") is None and type(self.image_encoder).__name__ == "CLIPImageEncoder":
+            return None
+        return data_dict["images"].flatten(end_dim=1)
 
     def _gate(self, z):
         return self.dp_split.gate(z) if (self.dp_split is not None and torch.is_grad_enabled() and z.requires_grad) else z
@@ -260,7 +268,7 @@ class TriCoLoNet(TriModule):
         with torch.no_grad():
             s = None
             if self.image_encoder is not None:
-                s = self.image_encoder(data_dict["images"].flatten(end_dim=1), data_dict)
+                s = self.image_encoder(self._images(data_dict), data_dict)
             if self.voxel_encoder is not None:
                 v = self.voxel_encoder(data_dict["voxels"], len(data_dict["model_id"]))
                 s = v if s is None else s + v

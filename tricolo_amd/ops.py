@@ -2037,3 +2037,68 @@ def adam_step_segments(p, grad_ptrs, grad_starts, m, v, step, lr, b1, b2, eps, w
 def adam_step(p, g, m, v, step, lr, b1, b2, eps, wd, gscale=1.0, lr_dev=None):
     check(lib().tri_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(step), lr, ptr(lr_dev), b1, b2, eps, wd, gscale, stream()),
           "tri_adam_step")
+
+
+# ------------------------------------------------------------------------------------------------ counter-based dropout
+DROPOUT_BITS = 24                                                   # uniform bits compared with p (csrc/dropout.hip)
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def dropout_threshold_scale(p):
+    """p in [0, 1] -> (threshold, scale) of tri_dropout_apply: an element is dropped when its 24 uniform bits are below
+    threshold = round(p * 2^24) (float64); a kept one is multiplied by scale = fp32(1 / (1 - p)), 0 at p = 1."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    scale = 0.0 if p == 1.0 else float(torch.tensor(1.0 / (1.0 - p), dtype=torch.float32).item())
+    return int(p * 16777216.0 + 0.5), scale
+
+
+def dropout_mask(rows, cols, p, seed, step, row0=0, tower=0):
+    """The multiplier m of dropout_apply as a CPU fp32 [rows, cols] tensor (0 or scale), from Python ints: the torch restatement of
+    csrc/dropout.hip on evaluation.mesh.philox4x32_10, the same bits."""
+    from .evaluation.mesh import philox4x32_10
+    threshold, scale = dropout_threshold_scale(p)
+    rows, cols, seed = int(rows), int(cols), int(seed) & _M64
+    groups = (cols + 3) // 4
+    g = torch.arange(groups, dtype=torch.int64)[None, :].expand(rows, groups)
+    r = (((int(row0) & _M32) + torch.arange(rows, dtype=torch.int64)) & _M32)[:, None].expand(rows, groups)
+    zero = torch.zeros((rows, groups), dtype=torch.int64)
+    words = philox4x32_10((g, r, zero + (int(step) & _M32), zero + (int(tower) & _M32)), (seed & _M32, seed >> 32))
+    w = torch.stack(words, dim=-1).reshape(rows, groups * 4)[:, :cols]
+    return torch.where((w >> 8) < threshold, 0.0, scale).to(torch.float32)
+
+
+def dropout_tick(step):
+    """used = step.clone(); step += 1, as one launch on the current stream (step, used: int64 [1] on step's device).  `used` is what
+    dropout_apply reads, in this forward and in its backward; under HIP-graph replay both follow the counter."""
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise ValueError("dropout_tick: step must be an int64 tensor with one element")
+    if not step.is_cuda:
+        used = step.clone()
+        step += 1
+        return used
+    used = torch.empty((1,), dtype=torch.int64, device=step.device)
+    check(lib().tri_dropout_tick(ptr(step), ptr(used), stream()), "tri_dropout_tick")
+    return used
+
+
+def dropout_apply(x, p, seed, used, row0=0, tower=0):
+    """y = x * m for fp32 x [rows, cols]: m(r, c) = 0 where the counter-based mask of (seed, used[0], tower, row0 + r, c) drops the
+    element, fp32(1 / (1 - p)) elsewhere (head of csrc/dropout.hip; inf / NaN propagate through the multiply as in torch).  The same
+    call serves the backward (dx = dy * m).  used: the int64 [1] tensor of dropout_tick.  row0: the global index of row 0 (a
+    data-parallel rank passes rank * B_local and draws the rows of the global batch).  CPU tensors run the torch restatement
+    dropout_mask: the same bits."""
+    threshold, scale = dropout_threshold_scale(p)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < 1:
+        raise ValueError(f"dropout_apply: x must be float32 [rows, cols >= 1], got {x.dtype} {tuple(x.shape)}")
+    if used.dtype != torch.int64 or used.numel() != 1 or used.device != x.device:
+        raise ValueError("dropout_apply: used must be the int64 [1] tensor of dropout_tick, on x's device")
+    x = x.contiguous()
+    rows, cols = x.shape
+    if not x.is_cuda:
+        return x * dropout_mask(rows, cols, p, seed, int(used.item()), row0, tower)
+    y = torch.empty_like(x)
+    check(lib().tri_dropout_apply(ptr(x), ptr(y), rows, cols, threshold, scale, int(seed) & _M64, ptr(used), int(row0) & _M64,
+                                  int(tower) & _M32, stream()), "tri_dropout_apply")
+    return y

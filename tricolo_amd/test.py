@@ -8,7 +8,8 @@ the towers the config switches off (a Tri(I+V) checkpoint serves a Bi(I) or Bi(V
 net.eval() / no_grad / test_step and on_test_epoch_end.  With inference.evaluate the `RR@1 RR@5 NDCG@5 MRR` line is printed and
 <inference.output_dir>/nearest.jsonl written (the file evaluation.shape_f1 reads; records in caption order, not the reference's random
 order); with inference.save_predictions <inference.output_dir>/output.p is written (the file tricolo_amd.eval reads).  Data sources are
-train.main's: data=synthetic (its held-out set) and the packed Text2Shape sets.  main() returns the metrics dict (None without
+train.main's: data=synthetic (its held-out set) and the packed Text2Shape sets - with model.text_encoder=CLIPTextEncoder and / or
+model.image_encoder=CLIPImageEncoder the latter need their clip_embeddings_<split>.pth (data/dataset.py).  main() returns the metrics dict (None without
 inference.evaluate).
 """
 from __future__ import annotations

@@ -15,6 +15,11 @@ The packed Text2Shape sets of the reference's data/preprocess_all_data.py are re
 
     python -m tricolo_amd.train data=text2shape_chair_table data.dataset_root_path=/path/to/data model.text_encoder=BiGRUEncoder \
         model.image_encoder=MVCNNEncoder model.voxel_encoder=SparseCNNEncoder experiment_name=chair_table
+
+Runs on cached CLIP features (model.text_encoder=CLIPTextEncoder and / or model.image_encoder=CLIPImageEncoder) read the
+clip_embeddings_<split>.pth files of the reference's extract_clip_feats.py from data.exp_data_root_path; data=synthetic has none.
+torch.manual_seed(cfg.train_seed) below also fixes the dropout masks of layers.CounterDropout (CLIPImageEncoder, and CLIPTextEncoder
+with model.modules.CLIPTextEncoder.dropout=counter).
 """
 from __future__ import annotations
 
@@ -110,6 +115,9 @@ PACKED_DATASETS = ("Text2ShapeChairTable", "Text2ShapeC13")
 
 
 def check_dataset(cfg, program="tricolo_amd.train"):
+    if cfg.data.get("dataset") == "Synthetic" and (cfg.model.text_encoder == "CLIPTextEncoder" or cfg.model.image_encoder == "CLIPImageEncoder"):
+        raise SystemExit(f"{program}: data=synthetic has no cached CLIP vectors; CLIPTextEncoder / CLIPImageEncoder run on the packed Text2Shape "
+                         f"sets {PACKED_DATASETS} with their clip_embeddings_<split>.pth files")
     if cfg.data.get("dataset") not in ("Synthetic",) + PACKED_DATASETS:
         raise SystemExit(f"{program} reads data=synthetic and the packed Text2Shape sets {PACKED_DATASETS} "
                          f"(data/dataset.py: <exp_data_root_path>/<category>/<model_id>.npz + <split>_map.json), not {cfg.data.get('dataset')!r}")
