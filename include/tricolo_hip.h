@@ -83,6 +83,17 @@ int tri_retrieval_topk(const float* text, const float* shape, const int* label, 
 int tri_retrieval_gallery(const float* text /* [Nq,D] */, const float* shape /* [Ns,D] */, const int* label /* [Nq] or NULL */, int Nq, int Ns,
                           int D, int k, int* topk_idx /* [Nq,k] */, double* topk_sim /* [Nq,k] */, int* first_hit /* [Nq] or NULL */,
                           void* stream);
+/* Shape -> text: the same ranking (the same kernel, the same float64 bits, the same top k) where SEVERAL candidates are correct for a
+ * query.  A query names a class, query_class[q]; the candidate rows of class g are class_rows[class_off[g] .. class_off[g + 1]) (CSR:
+ * class_off ascending, class_off[ncls] <= Nc).  With b the row of the query's class that ranks first, first_hit[q] is the number of
+ * candidates c != b that rank before (sim(q, b), b): the 0-based position of the first correct candidate.  first_hit[q] = -1 when
+ * query_class[q] is outside [0, ncls) or the class holds no row (nothing is read for it); a class_rows entry outside [0, Nc) is
+ * skipped, never dereferenced.  With class_off = 0..Nc and class_rows = 0..Nc-1 the three outputs are tri_retrieval_gallery's byte for
+ * byte.  Limits and return codes are tri_retrieval_gallery's; first_hit may be NULL (then query_class, class_off and class_rows may be
+ * NULL too), first_hit without all three is TRI_ERR_ARG. */
+int tri_retrieval_classes(const float* query /* [Nq,D] */, const float* cand /* [Nc,D] */, const int* query_class /* [Nq] */,
+                          const int* class_off /* [ncls+1] */, const int* class_rows, int Nq, int Nc, int D, int ncls, int k,
+                          int* topk_idx /* [Nq,k] */, double* topk_sim /* [Nq,k] */, int* first_hit /* [Nq] or NULL */, void* stream);
 
 /* ---- dense layers with <= 64 rows (MLP heads at the per-GPU batch) ---------------------------------------------
  * nn.Linear forward / backward of sparse_cnn.py:39-44, mv_cnn.py:21-26, bigru.py:12, clip_text.py:9-14 in three launches,

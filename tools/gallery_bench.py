@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """tri_retrieval_topk against tri_retrieval_gallery at the chair/table val shape (7,424 captions x 1,486 shapes x 512), alternating in one
 process under device events, and tri_retrieval_gallery alone against a 40,000-shape gallery (past the old kernel's limit):
-python tools/gallery_bench.py [--rounds 5] [--reps 10].  Prints one line per measurement (profiles/r20/NOTES_gallery.md keeps them)."""
+python tools/gallery_bench.py [--rounds 5] [--reps 10].  Prints one line per measurement (profiles/r20/NOTES_gallery.md keeps them).
+--s2t measures the other direction instead: 1,486 shapes ask 7,424 captions (tri_retrieval_classes, CSR built once outside the timed
+window) against tri_retrieval_gallery on the same swapped operands without labels - the same dot products, no pass over the classes -
+alternating, with the spread of each (profiles/r22/NOTES_s2t.md)."""
 import argparse
 import os
 import sys
@@ -32,12 +35,48 @@ def timed(fn, args, reps):
     return a.elapsed_time(b) / reps, out
 
 
+def stats(t):
+    return f"min {min(t):.3f} median {sorted(t)[len(t) // 2]:.3f} max {max(t):.3f} spread {(max(t) - min(t)) / sorted(t)[len(t) // 2] * 100:.1f}%"
+
+
+def s2t(a):
+    """Shape -> text at the val split's size: every shape asks, a caption's class is the shape it was made from."""
+    Nt, Ns, D = 7424, 1486, 512
+    text, shape, pick = inputs(Nt, Ns, D)
+    qc = torch.arange(Ns, dtype=torch.int32, device="cuda")
+    off, rows, ncls = ops.class_csr(pick, Ns)
+    base = lambda q, c, k: ops.retrieval_gallery(q, c, None, k)                              # noqa: E731
+    new = lambda q, c, k: ops.retrieval_classes_csr(q, c, qc, off, rows, ncls, k)            # noqa: E731
+    whole = lambda q, c, k: ops.retrieval_classes(q, c, qc, pick, k, ncls=Ns)                # noqa: E731  (with the CSR build)
+    for fn in (base, new, whole):
+        timed(fn, (shape, text), 3)
+    tb, tn, tw = [], [], []
+    for _ in range(a.rounds):                                       # alternating: all see the same neighbours on the machine
+        for fn, t in ((base, tb), (new, tn), (whole, tw)):
+            ms, out = timed(fn, (shape, text), a.reps)
+            t.append(ms)
+            if fn is base:
+                o = out
+            elif fn is new:
+                n = out
+    same = torch.equal(o[0], n[0]) and torch.equal(o[1].view(torch.int64), n[1].view(torch.int64))
+    sizes = torch.bincount(pick.long(), minlength=Ns)
+    print(f"s2t {Ns} shapes x {Nt} captions x {D}, k = 5, {a.rounds} alternating rounds of {a.reps} calls; top k bit-identical: {same}; "
+          f"captions per shape 0..{int(sizes.max())}, first_hit -1 for {int((n[2] < 0).sum())} shapes")
+    print(f"  tri_retrieval_gallery, no labels   ms/call {stats(tb)}")
+    print(f"  tri_retrieval_classes              ms/call {stats(tn)}   (+{Nt} dot products of the class pass on {Ns * Nt})")
+    print(f"  ops.retrieval_classes (CSR + call) ms/call {stats(tw)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--s2t", action="store_true", help="measure the shape -> text direction instead")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "gallery_bench.py needs an MI355X"
+    if a.s2t:
+        return s2t(a)
     Nq, Ns, D = 7424, 1486, 512
     args = inputs(Nq, Ns, D)
     for fn in (ops.retrieval_topk, ops.retrieval_gallery):

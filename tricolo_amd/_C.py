@@ -66,6 +66,7 @@ SIGNATURES = {
     "tri_embedding_bwd": (I, [P, P, I, I, I, I, I, P, P]),
     "tri_retrieval_topk": (I, [P, P, P, I, I, I, I, P, P, P, P]),
     "tri_retrieval_gallery": (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    "tri_retrieval_classes": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
     "tri_linear_small_supported": (I, [I, I, I]),
     "tri_linear_small_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "tri_linear_small_dgrad": (I, [P, P, P, P, I, I, I, I, I, P]),

@@ -15,9 +15,13 @@
 //   * at the end one pass ranks the at most 4 k list entries of a query against each other (one entry per thread, k <= 64) and writes
 //     the k first; the four counters are summed.
 // The order on (similarity, index) is strict and total, so the result does not depend on which wave saw which row.
+// tri_retrieval_classes (shape -> text: several candidates are correct for a query) is the same kernel, CLS = true: the "own shape" is the
+// row of the query's class that ranks first, found by a pass over the class's rows before the stream starts - one row at a time, by the
+// same lanes in the same order, so its similarity has the stream's bits -, and first_hit counts the rows ranking before it.
 // LDS: QT * D * 8 (queries) + 4 * QT * k * 12 (lists) + QT * 28 + 16 bytes <= 57,584: below 64 KiB, no attribute to raise.
 #include "common.h"
 #include "../../include/tricolo_hip.h"
+#include <stdio.h>
 
 #define GALLERY_ROWS 2                                  // shape rows a wave holds accumulators for at a time
 #define GALLERY_MAX_D 4096
@@ -67,9 +71,12 @@ __device__ __forceinline__ double gallery_uniform(double x) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
 
-template <int QT>
+// CLS: label[q] names a CLASS of shape rows (class_rows[class_off[g] .. class_off[g + 1]), tri_retrieval_classes) instead of one row; the
+// "own shape" of a query is then the row of its class that ranks first, found by a pass over the class before the stream starts
+template <int QT, bool CLS>
 __global__ __launch_bounds__(256) void retrieval_gallery_kernel(const float* __restrict__ text, const float* __restrict__ shape,
-                                                                const int* __restrict__ label, int Nq, int Ns, int D, int k,
+                                                                const int* __restrict__ label, const int* __restrict__ class_off,
+                                                                const int* __restrict__ class_rows, int ncls, int Nq, int Ns, int D, int k,
                                                                 int* __restrict__ topk_idx, double* __restrict__ topk_sim,
                                                                 int* __restrict__ first_hit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -90,16 +97,38 @@ __global__ __launch_bounds__(256) void retrieval_gallery_kernel(const float* __r
     // the own shape's similarity, by the same lanes in the same order as every other pair
     for (int q = wave; q < QT; q += 4) {
         int c = -1;
-        if (label && q0 + q < Nq) {
-            c = label[q0 + q];
-            if (c < 0 || c >= Ns) c = -1;                          // no such shape: first_hit reports -1, nothing is read
-        }
         double acc = 0.0;
-        if (c >= 0) {
-            const float* row = shape + (size_t)c * D;
+        if constexpr (CLS) {
+            // the best row of the query's class: one row at a time (a class may hold any number of rows), everything wave-uniform
+            int lo = 0, hi = 0;
+            if (label && q0 + q < Nq) {
+                const int g = label[q0 + q];
+                if (g >= 0 && g < ncls) {                          // no such class: first_hit reports -1, nothing is read
+                    lo = max(class_off[g], 0);
+                    hi = min(class_off[g + 1], Ns);                // class_rows holds at most Ns entries
+                }
+            }
             const double* tr = tq + (size_t)q * D;
-            for (int d = lane; d < D; d += 64) acc = fma(tr[d], (double)row[d], acc);
-            acc = wave_sum_d(acc);
+            for (int j = lo; j < hi; ++j) {
+                const int r = __builtin_amdgcn_readfirstlane(class_rows[j]);
+                if (r < 0 || r >= Ns) continue;                    // no such row: skipped, never dereferenced
+                const float* row = shape + (size_t)r * D;
+                double a = 0.0;
+                for (int d = lane; d < D; d += 64) a = fma(tr[d], (double)row[d], a);
+                a = gallery_uniform(wave_sum_d(a));
+                if (c < 0 || gallery_ranks_before(a, r, acc, c)) { acc = a; c = r; }
+            }
+        } else {
+            if (label && q0 + q < Nq) {
+                c = label[q0 + q];
+                if (c < 0 || c >= Ns) c = -1;                      // no such shape: first_hit reports -1, nothing is read
+            }
+            if (c >= 0) {
+                const float* row = shape + (size_t)c * D;
+                const double* tr = tq + (size_t)q * D;
+                for (int d = lane; d < D; d += 64) acc = fma(tr[d], (double)row[d], acc);
+                acc = wave_sum_d(acc);
+            }
         }
         if (lane == 0) { osim[q] = acc; oidx[q] = c; }
     }
@@ -200,25 +229,48 @@ __global__ __launch_bounds__(256) void retrieval_gallery_kernel(const float* __r
     }
 }
 
-template <int QT>
-static void launch_gallery(const float* text, const float* shape, const int* label, int Nq, int Ns, int D, int k, int* topk_idx,
-                           double* topk_sim, int* first_hit, hipStream_t stream) {
+template <int QT, bool CLS>
+static void launch_gallery(const float* text, const float* shape, const int* label, const int* class_off, const int* class_rows, int ncls,
+                           int Nq, int Ns, int D, int k, int* topk_idx, double* topk_sim, int* first_hit, hipStream_t stream) {
     const size_t smem = (size_t)QT * D * 8 + (size_t)4 * QT * k * 12 + (size_t)QT * 28 + 16;
-    retrieval_gallery_kernel<QT><<<(Nq + QT - 1) / QT, 256, smem, stream>>>(text, shape, label, Nq, Ns, D, k, topk_idx, topk_sim, first_hit);
+    retrieval_gallery_kernel<QT, CLS><<<(Nq + QT - 1) / QT, 256, smem, stream>>>(text, shape, label, class_off, class_rows, ncls, Nq, Ns, D, k,
+                                                                                 topk_idx, topk_sim, first_hit);
+}
+
+// the argument checks and the tile choice of both entry points (name: whose message it is)
+template <bool CLS>
+static int gallery_call(const char* name, const float* text, const float* shape, const int* label, const int* class_off,
+                        const int* class_rows, int ncls, int Nq, int Ns, int D, int k, int* topk_idx, double* topk_sim, int* first_hit,
+                        void* stream) {
+    char msg[160];
+    if (Nq <= 0) return TRI_OK;
+    if (k < 1 || k > Ns) { snprintf(msg, sizeof msg, "%s: need 1 <= k <= number of shapes", name); tri_set_error(msg); return TRI_ERR_ARG; }
+    if (k > TRI_GALLERY_MAX_K) { snprintf(msg, sizeof msg, "%s: k > 64 (TRI_GALLERY_MAX_K): a wave keeps one list entry per lane", name); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
+    if (first_hit && (!label || (CLS && (!class_off || !class_rows || ncls < 0)))) {
+        snprintf(msg, sizeof msg, CLS ? "%s: first_hit needs query_class, class_off and class_rows" : "%s: first_hit needs label", name);
+        tri_set_error(msg);
+        return TRI_ERR_ARG;
+    }
+    if (D < 1) { snprintf(msg, sizeof msg, "%s: need D >= 1", name); tri_set_error(msg); return TRI_ERR_ARG; }
+    if (D > GALLERY_MAX_D) { snprintf(msg, sizeof msg, "%s: D > 4096 does not fit the 32 KiB float64 query tile in LDS", name); tri_set_error(msg); return TRI_ERR_UNSUPPORTED; }
+    if (CLS && !first_hit) label = nullptr;                        // nothing to count: no pass over the classes either
+    hipStream_t st = (hipStream_t)stream;
+    if (D <= 512) launch_gallery<8, CLS>(text, shape, label, class_off, class_rows, ncls, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
+    else if (D <= 1024) launch_gallery<4, CLS>(text, shape, label, class_off, class_rows, ncls, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
+    else if (D <= 2048) launch_gallery<2, CLS>(text, shape, label, class_off, class_rows, ncls, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
+    else launch_gallery<1, CLS>(text, shape, label, class_off, class_rows, ncls, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
+    return tri_check_launch(name);
 }
 
 extern "C" int tri_retrieval_gallery(const float* text, const float* shape, const int* label, int Nq, int Ns, int D, int k, int* topk_idx,
                                      double* topk_sim, int* first_hit, void* stream) {
-    if (Nq <= 0) return TRI_OK;
-    if (k < 1 || k > Ns) { tri_set_error("tri_retrieval_gallery: need 1 <= k <= number of shapes"); return TRI_ERR_ARG; }
-    if (k > TRI_GALLERY_MAX_K) { tri_set_error("tri_retrieval_gallery: k > 64 (TRI_GALLERY_MAX_K): a wave keeps one list entry per lane"); return TRI_ERR_UNSUPPORTED; }
-    if (first_hit && !label) { tri_set_error("tri_retrieval_gallery: first_hit needs label"); return TRI_ERR_ARG; }
-    if (D < 1) { tri_set_error("tri_retrieval_gallery: need D >= 1"); return TRI_ERR_ARG; }
-    if (D > GALLERY_MAX_D) { tri_set_error("tri_retrieval_gallery: D > 4096 does not fit the 32 KiB float64 query tile in LDS"); return TRI_ERR_UNSUPPORTED; }
-    hipStream_t st = (hipStream_t)stream;
-    if (D <= 512) launch_gallery<8>(text, shape, label, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
-    else if (D <= 1024) launch_gallery<4>(text, shape, label, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
-    else if (D <= 2048) launch_gallery<2>(text, shape, label, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
-    else launch_gallery<1>(text, shape, label, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, st);
-    return tri_check_launch("tri_retrieval_gallery");
+    return gallery_call<false>("tri_retrieval_gallery", text, shape, label, nullptr, nullptr, 0, Nq, Ns, D, k, topk_idx, topk_sim, first_hit, stream);
+}
+
+// Shape -> text: several candidates are correct for a query, named by a class.  first_hit[q] = the rows ranking before the best row of
+// class query_class[q] (-1: no such class, or an empty one); the top k are tri_retrieval_gallery's.
+extern "C" int tri_retrieval_classes(const float* query, const float* cand, const int* query_class, const int* class_off, const int* class_rows,
+                                     int Nq, int Nc, int D, int ncls, int k, int* topk_idx, double* topk_sim, int* first_hit, void* stream) {
+    return gallery_call<true>("tri_retrieval_classes", query, cand, query_class, class_off, class_rows, ncls, Nq, Nc, D, k, topk_idx, topk_sim,
+                              first_hit, stream);
 }

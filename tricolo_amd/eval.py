@@ -1,9 +1,11 @@
 """Score a saved prediction file: the reference's eval.py (`python eval.py data=... +prediction_file_path=output.p`).
 
-    python -m tricolo_amd.eval data=text2shape_chair_table +prediction_file_path=output.p [+nearest_path=nearest.jsonl]
+    python -m tricolo_amd.eval data=text2shape_chair_table +prediction_file_path=output.p [+nearest_path=nearest.jsonl] [+direction=both]
 
 Unpickles the embeddings dict that tricolo_amd.test (or the reference's test.py) wrote and prints compute_metrics' `RR@1 RR@5 NDCG@5
-MRR` line; with +nearest_path= the nearest.jsonl of evaluation.shape_f1 is written too.  The reference also passes
+MRR` line; with +nearest_path= the nearest.jsonl of evaluation.shape_f1 is written too.  +direction=s2t|both (or +inference.direction=)
+scores the shape -> text direction as well: a second `S2T RR@1 RR@5 NDCG@5 MRR` line, records in nearest_s2t.jsonl beside nearest_path,
+the numbers under "s2t" of the returned dict (evaluation.eval_retrieval.compute_metrics).  The reference also passes
 `metric=cfg.evaluation.metric`, an argument its own compute_metrics does not have: it is not read here.  main() returns the metrics dict.
 """
 import pickle
@@ -26,7 +28,8 @@ def main(argv=None):
     cfg, path, nearest_path = parse(argv)
     with open(path, "rb") as f:
         embeddings_dict = pickle.load(f)
-    return compute_metrics(cfg.data.dataset, embeddings_dict, print_results=True, nearest_path=nearest_path)
+    direction = str(cfg.get("direction") or cfg.inference.get("direction", "t2s"))
+    return compute_metrics(cfg.data.dataset, embeddings_dict, print_results=True, nearest_path=nearest_path, direction=direction)
 
 
 if __name__ == "__main__":

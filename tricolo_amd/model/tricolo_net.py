@@ -245,12 +245,23 @@ class TriCoLoNet(TriModule):
     def on_validation_epoch_end(self):
         embeddings_dict = self._collate_output()
         self.val_test_step_outputs.clear()
-        pr_at_k = compute_metrics(self._cfg.data.dataset, embeddings_dict)
+        # text -> shape always (the checkpoint monitor is its RR@5); shape -> text beside it when inference.direction asks for it
+        pr_at_k = compute_metrics(self._cfg.data.dataset, embeddings_dict, direction="t2s" if self._direction() == "t2s" else "both")
         self._log("val_eval/RR@1", pr_at_k["recall_rate"][0] * 100)
         self._log("val_eval/RR@5", pr_at_k["recall_rate"][4] * 100)
         self._log("val_eval/NDCG@5", pr_at_k["ndcg"][4] * 100)
         self._log("val_eval/MRR", pr_at_k["mrr"] * 100)
+        if "s2t" in pr_at_k:
+            s2t = pr_at_k["s2t"]
+            self._log("val_eval/S2T_RR@1", s2t["recall_rate"][0] * 100)
+            self._log("val_eval/S2T_RR@5", s2t["recall_rate"][4] * 100)
+            self._log("val_eval/S2T_NDCG@5", s2t["ndcg"][4] * 100)
+            self._log("val_eval/S2T_MRR", s2t["mrr"] * 100)
         return pr_at_k
+
+    def _direction(self):
+        """inference.direction: "t2s" (the default; the key need not exist), "s2t" or "both" (evaluation.eval_retrieval)."""
+        return str(self._cfg.inference.get("direction", "t2s"))
 
     def test_step(self, data_dict, idx=0):
         self._stash(data_dict, self(data_dict))
@@ -279,7 +290,8 @@ class TriCoLoNet(TriModule):
         self.val_test_step_outputs.clear()
         pr = None
         if self._cfg.inference.evaluate:
-            pr = compute_metrics(self._cfg.data.dataset, embeddings_dict, print_results=True, nearest_path=nearest_path)
+            pr = compute_metrics(self._cfg.data.dataset, embeddings_dict, print_results=True, nearest_path=nearest_path,
+                                 direction=self._direction())
         if self._cfg.inference.save_predictions:
             os.makedirs(self._cfg.inference.output_dir, exist_ok=True)
             path = os.path.join(self._cfg.inference.output_dir, "output.p")

@@ -1317,6 +1317,52 @@ def retrieval_gallery(text, shape, labels=None, k=5):
     return idx, sim, hit
 
 
+def class_csr(cand_class, ncls=None):
+    """Candidate classes [Nc] (any integer dtype, on the device) -> (class_off [ncls + 1] i32, class_rows [Nc] i32, ncls): the rows of
+    class g are class_rows[class_off[g] : class_off[g + 1]], ascending within a class (a stable sort).  A candidate whose class is
+    negative - or not below an explicit ncls - belongs to no class: it sorts behind the last class, past class_off[ncls].  Without
+    ncls, ncls = max class + 1 (one host read)."""
+    cc = cand_class.to(torch.int64)
+    if ncls is None:
+        ncls = max(int(cc.max()) + 1, 0) if cc.numel() else 0
+    ncls = int(ncls)
+    key = torch.where((cc >= 0) & (cc < ncls), cc, torch.full_like(cc, ncls))
+    rows = torch.argsort(key, stable=True).to(torch.int32)
+    counts = torch.bincount(key, minlength=ncls + 1)[:ncls]
+    off = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32)
+    return off, rows, ncls
+
+
+def retrieval_classes_csr(query, cand, query_class, class_off, class_rows, ncls, k=5):
+    """tri_retrieval_classes on a CSR that is already built (class_csr): query [Nq,D], cand [Nc,D] fp32 on the GPU, query_class [Nq] i32,
+    class_off [ncls + 1] i32, class_rows i32; the three may be None together -> (indices [Nq,k] i32, sims [Nq,k] f64, first_hit [Nq] i32
+    | None)."""
+    Nq, D = query.shape
+    Nc = cand.shape[0]
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=query.device)
+    sim = torch.empty((Nq, k), dtype=torch.float64, device=query.device)
+    hit = None if query_class is None else torch.empty((Nq,), dtype=torch.int32, device=query.device)
+    check(lib().tri_retrieval_classes(ptr(_f32(query)), ptr(_f32(cand)), ptr(query_class), ptr(class_off), ptr(class_rows), Nq, Nc, D,
+                                      int(ncls), k, ptr(idx), ptr(sim), ptr(hit), stream()), "tri_retrieval_classes")
+    return idx, sim, hit
+
+
+def retrieval_classes(query, cand, query_class=None, cand_class=None, k=5, ncls=None):
+    """Shape -> text ranking (csrc/gallery.hip, the kernel of retrieval_gallery; k <= 64, D <= 4096): several candidates are correct for
+    a query.  query [Nq,D], cand [Nc,D] fp32 on the GPU; query_class [Nq] and cand_class [Nc] integer classes (a negative cand_class:
+    no class), both or neither; ncls = max cand_class + 1 unless given -> (indices [Nq,k] i32, sims [Nq,k] f64, first_hit [Nq] i32 |
+    None).  first_hit[q]: the candidates ranking before the best candidate of class query_class[q]; -1 when the class is outside
+    [0, ncls) or empty."""
+    if (query_class is None) != (cand_class is None):
+        raise ValueError("retrieval_classes: query_class and cand_class go together")
+    if query_class is None:
+        return retrieval_classes_csr(query, cand, None, None, None, 0, k)
+    if cand_class.shape != (cand.shape[0],) or query_class.shape != (query.shape[0],):
+        raise ValueError("retrieval_classes: one class per query row and one per candidate row")
+    off, rows, ncls = class_csr(cand_class.to(cand.device), ncls)
+    return retrieval_classes_csr(query, cand, query_class.to(query.device, torch.int32).contiguous(), off, rows, ncls, k)
+
+
 # ------------------------------------------------------------------------------------------------ small dense layers
 def linear_small_supported(rows, K, N):
     return bool(lib().tri_linear_small_supported(int(rows), int(K), int(N)))

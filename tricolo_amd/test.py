@@ -7,7 +7,9 @@ Same steps as the reference's test.py:11-32: seed with cfg.test_seed, build TriC
 the towers the config switches off (a Tri(I+V) checkpoint serves a Bi(I) or Bi(V) run), then cfg.inference.split in file order through
 net.eval() / no_grad / test_step and on_test_epoch_end.  With inference.evaluate the `RR@1 RR@5 NDCG@5 MRR` line is printed and
 <inference.output_dir>/nearest.jsonl written (the file evaluation.shape_f1 reads; records in caption order, not the reference's random
-order); with inference.save_predictions <inference.output_dir>/output.p is written (the file tricolo_amd.eval reads).  Data sources are
+order); with inference.save_predictions <inference.output_dir>/output.p is written (the file tricolo_amd.eval reads).  With
++inference.direction=s2t|both the shape -> text direction is scored too (evaluation.eval_retrieval.compute_metrics: a second line
+`S2T RR@1 RR@5 NDCG@5 MRR`, records in nearest_s2t.jsonl, the numbers under "s2t" of the returned dict); output.p is the same file.  Data sources are
 train.main's: data=synthetic (its held-out set) and the packed Text2Shape sets - with model.text_encoder=CLIPTextEncoder and / or
 model.image_encoder=CLIPImageEncoder the latter need their clip_embeddings_<split>.pth (data/dataset.py).  main() returns the metrics dict (None without
 inference.evaluate).

@@ -96,6 +96,10 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
                     net.validation_step(batch, i)
                 m = net.on_validation_epoch_end()
             rec["val_eval/RR@1"], rec["val_eval/RR@5"] = float(m["recall_rate"][0] * 100), float(m["recall_rate"][4] * 100)
+            if "s2t" in m:                                            # inference.direction=s2t|both: shape -> text beside it, never the monitor
+                s2t = m["s2t"]
+                rec["val_eval/S2T_RR@1"], rec["val_eval/S2T_RR@5"] = float(s2t["recall_rate"][0] * 100), float(s2t["recall_rate"][4] * 100)
+                rec["val_eval/S2T_NDCG@5"], rec["val_eval/S2T_MRR"] = float(s2t["ndcg"][4] * 100), float(s2t["mrr"] * 100)
             if out_dir is not None and (best is None or rec["val_eval/RR@5"] > best[0]):      # ModelCheckpoint(monitor=RR@5, mode=max)
                 os.makedirs(out_dir, exist_ok=True)
                 path = os.path.join(out_dir, f"epoch={epoch}-RR5={rec['val_eval/RR@5']:.2f}.ckpt")
