@@ -698,6 +698,37 @@ int tri_adam_step_segments(float* p, const void* grad_ptrs, const long* grad_sta
                            const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
                            void* stream);
 
+/* ---- Gradient clipping, decided on the device (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; csrc/misc.hip) -------------- */
+/* Launch order of a clipped step: tri_adam_guard*, tri_adam_tick, tri_grad_sumsq*, tri_grad_clip_coef, tri_adam_step*_clipped.  Nothing
+ * here uses an atomic or a ticket: the same input gives the same bits, also replayed from a HIP graph.
+ * tri_grad_norm_blocks(n): how many doubles ONE tri_grad_sumsq / tri_grad_sumsq_segments call over n elements writes to `partial` - a
+ * function of n alone (1 <= blocks <= 4096; no stream, no device memory; n < 0 is TRI_ERR_ARG). */
+int tri_grad_norm_blocks(long n);
+/* partial[b] = sum of (double)g[i] * (double)g[i] over workgroup b's share of the elements (a function of n and the grid only), for
+ * every b < tri_grad_norm_blocks(n); nothing else is written.  Any n >= 0 (n == 0 writes one 0.0; g is not looked at), g 4-byte aligned:
+ * scalar head up to the first 16-byte boundary, 16-byte body, scalar tail. */
+int tri_grad_sumsq(const float* g, long n, double* partial, void* stream);
+/* the same over the pointer table of tri_adam_step_segments (grad_ptrs / grad_starts: DEVICE arrays of nseg entries, 1 <= nseg <= 1024,
+ * segment sizes and n multiples of 4, gradients 16-byte aligned; n = the flat size the starts count in).  A NULL segment is NOT part of
+ * the norm: the update skips it, as torch.optim.Adam ignores a parameter without a gradient. */
+int tri_grad_sumsq_segments(const void* grad_ptrs, const long* grad_starts, int nseg, long n, double* partial, void* stream);
+/* One workgroup adds partial[0 .. nblk) in a fixed order (nblk >= 0; several tri_grad_sumsq calls may have filled consecutive parts) and
+ * computes, in double:  total = |gscale| * sqrt(sum),  rec[0] = (float)total,  c = max_norm / (total + 1e-6),
+ * rec[1] = c < 1 ? (float)c : 1.0f.  A total that is inf / NaN gives rec[1] = 1.0f and rec[0] keeps the non-finite value: that step
+ * belongs to the guard.  clipped[0] += 1 (one thread) when and only when rec[1] < 1.  max_norm = +inf measures only (rec[1] = 1.0f).
+ * rec: DEVICE float[2], clipped: DEVICE int[1].  TRI_ERR_ARG: max_norm <= 0 or NaN, nblk < 0, rec or clipped NULL (partial NULL with
+ * nblk > 0). */
+int tri_grad_clip_coef(const double* partial, int nblk, float gscale, float max_norm, float* rec, int* clipped, void* stream);
+/* tri_adam_step / tri_adam_step_segments with  gi = clamp(g * (gscale * coef), -clip_value, clip_value) + wd * p.  coef is read from
+ * coef_dev at run time (DEVICE float, e.g. rec + 1 of tri_grad_clip_coef; NULL = 1) and gscale * coef is formed once, in fp32.  The clamp
+ * exists only in a separate instantiation, launched when clip_value is finite; clip_value = +inf runs the expression of the plain entry
+ * points with that one scalar replaced, so coef == 1 gives their bits.  clip_value <= 0 or NaN is TRI_ERR_ARG. */
+int tri_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, const int* step, float lr, const float* lr_dev, float b1,
+                          float b2, float eps, float wd, float gscale, const float* coef_dev, float clip_value, void* stream);
+int tri_adam_step_segments_clipped(float* p, const void* grad_ptrs, const long* grad_starts, int nseg, float* m, float* v, long n,
+                                   const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
+                                   const float* coef_dev, float clip_value, void* stream);
+
 /* ---- Counter-based dropout (the Dropout(0.1) of the reference's clip_text.py / clip_img.py heads; csrc/dropout.hip) ------------ */
 /* used[0] = step[0]; step[0] += 1   (one thread; device int64 [1] each).  Stream-ordered: every later launch on `stream` that reads
  * `used` sees the value of THIS forward, also when the launches are replayed from a HIP graph. */

@@ -180,6 +180,12 @@ SIGNATURES = {
     "tri_adam_guard_segments": (I, [P, P, I, L, P, P]),
     "tri_adam_step": (I, [P, P, P, P, L, P, F, P, F, F, F, F, F, P]),
     "tri_adam_step_segments": (I, [P, P, P, I, P, P, L, P, F, P, F, F, F, F, F, P]),
+    "tri_grad_norm_blocks": (I, [L]),
+    "tri_grad_sumsq": (I, [P, L, P, P]),
+    "tri_grad_sumsq_segments": (I, [P, P, I, L, P, P]),
+    "tri_grad_clip_coef": (I, [P, I, F, F, P, P, P]),
+    "tri_adam_step_clipped": (I, [P, P, P, P, L, P, F, P, F, F, F, F, F, P, F, P]),
+    "tri_adam_step_segments_clipped": (I, [P, P, P, I, P, P, L, P, F, P, F, F, F, F, F, P, F, P]),
     "tri_dropout_tick": (I, [P, P, P]),
     "tri_dropout_apply": (I, [P, P, L, I, C.c_uint, F, C.c_ulonglong, P, C.c_ulonglong, C.c_uint, P]),
 }

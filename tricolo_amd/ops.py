@@ -2085,6 +2085,56 @@ def adam_step(p, g, m, v, step, lr, b1, b2, eps, wd, gscale=1.0, lr_dev=None):
           "tri_adam_step")
 
 
+# ------------------------------------------------------------------------------------------------ gradient clipping (include/tricolo_hip.h)
+def grad_norm_blocks(n: int) -> int:
+    """Doubles one grad_sumsq / grad_sumsq_segments call over n elements writes (a host query: no launch)."""
+    nblk = lib().tri_grad_norm_blocks(int(n))
+    check(min(nblk, 0), "tri_grad_norm_blocks")
+    return nblk
+
+
+def _partial(partial, nblk):
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() >= nblk, "expected a contiguous float64 partial buffer of at least nblk elements"
+    return partial
+
+
+def grad_sumsq(g, partial) -> int:
+    """partial[:nblk] = per-workgroup sums of g^2 in double over a flat fp32 gradient (any size, 4-byte alignment); returns nblk."""
+    nblk = grad_norm_blocks(g.numel())
+    check(lib().tri_grad_sumsq(ptr(_f32(g)), g.numel(), ptr(_partial(partial, nblk)), stream()), "tri_grad_sumsq")
+    return nblk
+
+
+def grad_sumsq_segments(grad_ptrs, grad_starts, n, partial) -> int:
+    """The same over adam_step_segments' pointer table (null pointers are not part of the norm); n: the flat size the starts count in."""
+    nblk = grad_norm_blocks(n)
+    check(lib().tri_grad_sumsq_segments(ptr(grad_ptrs), ptr(grad_starts), grad_starts.numel(), n, ptr(_partial(partial, nblk)), stream()),
+          "tri_grad_sumsq_segments")
+    return nblk
+
+
+def grad_clip_coef(partial, nblk, gscale, max_norm, rec, clipped):
+    """rec[0] = |gscale| * sqrt(sum(partial[:nblk])), rec[1] = min(1, max_norm / (rec[0] + 1e-6)) (1 when the norm is not finite);
+    clipped[0] += 1 when rec[1] < 1.  rec: fp32 [2], clipped: int32 [1], both on the device."""
+    assert rec.dtype == torch.float32 and rec.numel() >= 2 and clipped.dtype == torch.int32 and clipped.numel() >= 1
+    check(lib().tri_grad_clip_coef(ptr(_partial(partial, nblk)) if nblk else None, nblk, gscale, max_norm, ptr(rec), ptr(clipped), stream()),
+          "tri_grad_clip_coef")
+
+
+def adam_step_clipped(p, g, m, v, step, lr, b1, b2, eps, wd, gscale=1.0, lr_dev=None, coef_dev=None, clip_value=math.inf):
+    """adam_step with the gradient multiplied by the device scalar coef_dev (None: 1) and, for a finite clip_value, clamped to
+    [-clip_value, clip_value] before the weight decay is added."""
+    check(lib().tri_adam_step_clipped(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(step), lr, ptr(lr_dev), b1, b2, eps, wd, gscale,
+                                      ptr(coef_dev), clip_value, stream()), "tri_adam_step_clipped")
+
+
+def adam_step_segments_clipped(p, grad_ptrs, grad_starts, m, v, step, lr, b1, b2, eps, wd, gscale=1.0, lr_dev=None, coef_dev=None,
+                               clip_value=math.inf):
+    check(lib().tri_adam_step_segments_clipped(ptr(p), ptr(grad_ptrs), ptr(grad_starts), grad_starts.numel(), ptr(m), ptr(v), p.numel(),
+                                               ptr(step), lr, ptr(lr_dev), b1, b2, eps, wd, gscale, ptr(coef_dev), clip_value, stream()),
+          "tri_adam_step_segments_clipped")
+
+
 # ------------------------------------------------------------------------------------------------ counter-based dropout
 DROPOUT_BITS = 24                                                   # uniform bits compared with p (csrc/dropout.hip)
 _M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF

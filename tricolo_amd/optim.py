@@ -12,7 +12,12 @@ change ``param_groups[0]["lr"]`` as usual; eager steps pick it up by themselves,
 
 ``state_dict()`` / ``load_state_dict()`` speak torch.optim.Adam's format (per-parameter ``step``, ``exp_avg``,
 ``exp_avg_sq``), so Lightning's ``optimizer_states`` checkpoints resume in either optimizer.
+
+Gradient clipping (``max_grad_norm`` / ``clip_grad_value`` / ``set_gradient_clip``, Lightning's ``gradient_clip_val``) is decided on the
+device as the overflow guard is: guard, tick, sum of squares, finalize, update.  The norm is taken AFTER the data-parallel all-reduce and
+the whole step still replays from one HIP graph; with clipping off a step launches exactly what it launched before the option existed.
 """
+import math
 import os
 
 import torch
@@ -24,12 +29,14 @@ _GUARD_NOTE = os.environ.get("TRICOLO_GUARD_NOTE", "1") != "0"     # A/B switch 
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, flatten=True, guard=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, flatten=True, guard=True, max_grad_norm=None,
+                 clip_grad_value=None):
         """guard: scan every step's gradient for inf / NaN first (one extra read of the gradients, ~10 us for 18.5 M parameters) and skip
         the WHOLE step when one is found - parameters, both moments and the step counter stay, `skipped_steps()` counts it (what
         torch.cuda.amp.GradScaler does with an overflowed step; the f16 mode's activation gradients can overflow).  guard=False keeps
         only the per-element fallback of the update kernels (a non-finite element leaves its own p, m, v alone).  Either way this
-        DIFFERS from torch.optim.Adam, which would write the NaN into the weights (the reference's behaviour: a NaN surfaces as a NaN loss)."""
+        DIFFERS from torch.optim.Adam, which would write the NaN into the weights (the reference's behaviour: a NaN surfaces as a NaN loss).
+        max_grad_norm / clip_grad_value: set_gradient_clip(value, "norm") / set_gradient_clip(value, "value"); at most one of them."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._guard = bool(guard)
         self._flatten = flatten and len(self.param_groups) == 1
@@ -40,6 +47,14 @@ class FusedAdam(torch.optim.Optimizer):
         self._captures = 0
         self._zg_event = None
         self._seg_side = None
+        self._clip = None                                                        # None | ("norm", max_norm) | ("value", clip_value)
+        self._clip_partial = self._clip_rec = self._clip_cnt = self._clip_blocks = None
+        if max_grad_norm is not None and clip_grad_value is not None:
+            raise ValueError("FusedAdam: max_grad_norm and clip_grad_value exclude each other")
+        if max_grad_norm is not None:
+            self.set_gradient_clip(max_grad_norm, "norm")
+        elif clip_grad_value is not None:
+            self.set_gradient_clip(clip_grad_value, "value")
 
     def zero_grad(self, set_to_none: bool = True):
         """torch.optim.Optimizer.zero_grad; inside a HIP-graph capture it also marks the point the step's gradient-pointer table may be
@@ -58,6 +73,8 @@ class FusedAdam(torch.optim.Optimizer):
         captures of the step the caller is going to make (each keeps one pinned gradient-pointer table; 32 are provided anyway)."""
         self._captures = max(int(captures), getattr(self, "_captures", 0))
         if self._step_dev is not None:
+            if self._clip is not None:
+                self._alloc_clip()
             while hasattr(self, "_seg_capture_pool") and len(self._seg_capture_pool) + len(self._seg_captured) < self._captures:
                 self._seg_capture_pool.append(torch.zeros((3 * len(self._params),), dtype=torch.int64).pin_memory())
             return
@@ -122,6 +139,82 @@ class FusedAdam(torch.optim.Optimizer):
         if self._pending_state is not None:                          # load_state_dict() came before the first step
             sd, self._pending_state = self._pending_state, None
             self._restore(sd)
+        if self._clip is not None:
+            self._alloc_clip()
+
+    # ------------------------------------------------------------------ gradient clipping
+    def set_gradient_clip(self, value, algorithm: str = "norm"):
+        """Clip every following step's gradient: algorithm "norm" scales it so that its global L2 norm (all parameters, after grad_scale and
+        after the data-parallel all-reduce) is at most `value` - torch.nn.utils.clip_grad_norm_'s coefficient min(1, value / (norm + 1e-6)) -,
+        "value" clamps every element to [-value, value] (clip_grad_value_); weight decay joins afterwards, as in torch.optim.Adam.
+        value=None switches clipping off; value=inf with "norm" only measures (grad_norm()), the update keeps its bits.  The decision is
+        taken on the device, so a step the overflow guard skips stays skipped and is not counted as clipped.
+        A captured HIP graph keeps the setting it was captured with: the launches and their constants are recorded, so call this BEFORE
+        capturing and re-capture to change it.  Inside a capture it raises unless the buffers exist already (prepare() with clipping
+        on, or an earlier eager call)."""
+        if value is None:
+            self._clip = None
+            return
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"FusedAdam.set_gradient_clip: algorithm {algorithm!r} is not 'norm' or 'value'")
+        value = float(value)
+        if not value > 0.0:                                              # (NaN fails every comparison)
+            raise ValueError(f"FusedAdam.set_gradient_clip: a positive value expected, not {value}")
+        if self._step_dev is not None and self._clip_rec is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdam.set_gradient_clip inside a HIP-graph capture: the clipping buffers are not allocated yet - "
+                                   "set the clip (or call prepare() with it set) before capturing")
+            self._alloc_clip()
+        self._clip = (algorithm, value)
+
+    def _alloc_clip(self):
+        """Partial sums (one double per workgroup of the sum-of-squares launches of one step), the (norm, coefficient) record, the count."""
+        if self._clip_rec is not None or self._params is None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdam: the clipping buffers cannot be allocated inside a HIP-graph capture - call prepare() first")
+        dev = self._params[0].device
+        if self._flatten:
+            nblk = ops.grad_norm_blocks(self._flat_p.numel())
+        else:                                                        # per-parameter path: consecutive parts, one per gradient
+            self._clip_blocks = {id(p): ops.grad_norm_blocks(p.numel()) for p in self._params}
+            nblk = sum(self._clip_blocks.values())
+        self._clip_partial = torch.zeros((nblk,), dtype=torch.float64, device=dev)
+        self._clip_cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._clip_rec = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+
+    def grad_norm(self):
+        """Global L2 norm of the last step's gradient BEFORE clipping (times |grad_scale|; inf / NaN when the guard skipped that step for it).
+        One device read: synchronises - once per epoch, not per step.  None unless the "norm" algorithm has run."""
+        if self._clip_rec is None or self._clip is None or self._clip[0] != "norm":
+            return None
+        return float(self._clip_rec[0].item())
+
+    def clipped_steps(self) -> int:
+        """Steps whose gradient norm exceeded max_grad_norm so far ("norm" algorithm; reads a device counter: synchronises)."""
+        return 0 if self._clip_cnt is None else int(self._clip_cnt[0].item())
+
+    def _clip_coef(self, sums, grad_scale):
+        """The norm algorithm's two launches after the tick: sums(partial) -> number of partials it filled, then the finalize.
+        Returns the keyword arguments of the *_clipped update (coefficient read on the device / clamp value)."""
+        if self._clip_rec is None:
+            self._alloc_clip()
+        algorithm, value = self._clip
+        if algorithm == "value":
+            return dict(coef_dev=None, clip_value=value)
+        ops.grad_clip_coef(self._clip_partial, sums(self._clip_partial), grad_scale, value, self._clip_rec, self._clip_cnt)
+        return dict(coef_dev=self._clip_rec[1:], clip_value=math.inf)
+
+    def _update_flat(self, g, group, b1, b2, grad_scale):
+        """guard, tick, (sum of squares, finalize,) update over one packed gradient."""
+        if self._guard:
+            ops.adam_guard(g, self._step_dev)                        # (after the all-reduce: every rank takes the same decision)
+        ops.adam_tick(self._step_dev)
+        args = (self._flat_p, g, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"], group["weight_decay"], grad_scale)
+        if self._clip is None:
+            ops.adam_step(*args, lr_dev=self._lr_dev)
+        else:
+            ops.adam_step_clipped(*args, lr_dev=self._lr_dev, **self._clip_coef(lambda partial: ops.grad_sumsq(g, partial), grad_scale))
 
     def nonfinite_skipped(self) -> int:
         """Number of gradient elements the kernels refused so far because they were inf / NaN (f16 activation-gradient overflow guard:
@@ -281,8 +374,14 @@ class FusedAdam(torch.optim.Optimizer):
         # (round 6: the tick folded into the guard launch's last workgroup - one node less - was built and measured: 4,096 workgroups taking a
         #  ticket on one address cost 110 us; the kernel-argument form of the pointer table was dropped with it)
         ops.adam_tick(self._step_dev)                       # step += 1 on the device (or skipped += 1), once per optimizer step
-        ops.adam_step_segments(self._flat_p, self._seg_ptr, self._seg_start, self._flat_m, self._flat_v, self._step_dev, group["lr"],
-                               b1, b2, group["eps"], group["weight_decay"], grad_scale, lr_dev=self._lr_dev)
+        args = (self._flat_p, self._seg_ptr, self._seg_start, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"],
+                group["weight_decay"], grad_scale)
+        if self._clip is None:
+            ops.adam_step_segments(*args, lr_dev=self._lr_dev)
+        else:
+            def sums(partial):                              # the table the update reads: a parameter without a gradient is not in the norm
+                return ops.grad_sumsq_segments(self._seg_ptr, self._seg_start, self._flat_p.numel(), partial)
+            ops.adam_step_segments_clipped(*args, lr_dev=self._lr_dev, **self._clip_coef(sums, grad_scale))
         return True
 
     @torch.no_grad()
@@ -294,11 +393,7 @@ class FusedAdam(torch.optim.Optimizer):
         group = self.param_groups[0]
         b1, b2 = group["betas"]
         self.sync_lr()
-        if self._guard:
-            ops.adam_guard(g, self._step_dev)
-        ops.adam_tick(self._step_dev)
-        ops.adam_step(self._flat_p, g, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"],
-                      group["weight_decay"], grad_scale, lr_dev=self._lr_dev)
+        self._update_flat(g, group, b1, b2, grad_scale)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0, reduce_fn=None):
@@ -323,11 +418,7 @@ class FusedAdam(torch.optim.Optimizer):
             g = self.flat_grad()
             if reduce_fn is not None:
                 reduce_fn(g)
-            if self._guard:
-                ops.adam_guard(g, self._step_dev)               # (after the all-reduce: every rank takes the same decision)
-            ops.adam_tick(self._step_dev)
-            ops.adam_step(self._flat_p, g, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"],
-                          group["weight_decay"], grad_scale, lr_dev=self._lr_dev)
+            self._update_flat(g, group, b1, b2, grad_scale)
             return loss
         if reduce_fn is not None:
             raise RuntimeError("reduce_fn needs flatten=True")
@@ -337,13 +428,30 @@ class FusedAdam(torch.optim.Optimizer):
                     if p.grad is not None:
                         ops.adam_guard(p.grad if p.grad.is_contiguous() else p.grad.contiguous(), self._step_dev)
         ops.adam_tick(self._step_dev)
+        grads = {id(p): (p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+                 for group in self.param_groups for p in group["params"] if p.grad is not None}
+        clip = None
+        if self._clip is not None:                               # ONE norm over every gradient: a sum-of-squares call each, one finalize
+
+            def sums(partial):
+                off = 0
+                for p in self._params:
+                    if id(p) in grads:
+                        nb = self._clip_blocks[id(p)]
+                        ops.grad_sumsq(grads[id(p)], partial[off:off + nb])
+                        off += nb
+                return off
+            clip = self._clip_coef(sums, grad_scale)
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 st = self.state[p]
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                ops.adam_step(p, g, st["exp_avg"], st["exp_avg_sq"], self._step_dev, group["lr"], b1, b2, group["eps"],
-                              group["weight_decay"], grad_scale)             # per-group lr by value: this path is never graph-captured
+                args = (p, grads[id(p)], st["exp_avg"], st["exp_avg_sq"], self._step_dev, group["lr"], b1, b2, group["eps"],
+                        group["weight_decay"], grad_scale)                   # per-group lr by value: this path is never graph-captured
+                if clip is None:
+                    ops.adam_step(*args)
+                else:
+                    ops.adam_step_clipped(*args, **clip)
         return loss

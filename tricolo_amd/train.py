@@ -56,6 +56,22 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
         if doc.get("optimizer_states"):
             opt.load_state_dict(doc["optimizer_states"][0])
         start_epoch, step = int(doc.get("epoch", -1)) + 1, int(doc.get("global_step", 0))
+    # Lightning's Trainer(gradient_clip_val=..., gradient_clip_algorithm="norm" | "value"), given as +trainer.gradient_clip_val=...:
+    # FusedAdam clips inside its step (on the device, after the data-parallel all-reduce, graph-capturable); any other optimizer
+    # gets torch's utilities between backward() and step()
+    clip_val, clip_alg = cfg.trainer.get("gradient_clip_val"), cfg.trainer.get("gradient_clip_algorithm", "norm") or "norm"
+    if clip_val is not None and float(clip_val) == 0.0:               # (Lightning: 0 does not clip)
+        clip_val = None
+    torch_clip, clip_norm, clip_count = None, None, None
+    if clip_val is not None:
+        if clip_alg not in ("norm", "value"):
+            raise ValueError(f"trainer.gradient_clip_algorithm={clip_alg!r}: 'norm' or 'value' expected")
+        if hasattr(opt, "set_gradient_clip"):
+            opt.set_gradient_clip(float(clip_val), clip_alg)
+        else:
+            if not float(clip_val) > 0.0:
+                raise ValueError(f"trainer.gradient_clip_val={clip_val}: a positive value expected")
+            torch_clip = torch.nn.utils.clip_grad_norm_ if clip_alg == "norm" else torch.nn.utils.clip_grad_value_
     best, history = None, []
     every = int(cfg.trainer.get("check_val_every_n_epoch", 1) or 1)
     epoch_start_step = step                                           # global step the first epoch of THIS run starts from (resume: the checkpoint's)
@@ -66,10 +82,21 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
             opt.zero_grad(set_to_none=True)
             loss = net.training_step(batch, step)
             loss.backward(gradient=ops.one(loss.device))
+            if torch_clip is not None:
+                total = torch_clip([p for g in opt.param_groups for p in g["params"]], float(clip_val))
+                if clip_alg == "norm":                                # kept on the device: read once per epoch below
+                    hit = (float(clip_val) / (total.detach() + 1e-6) < 1.0).to(torch.int64)
+                    clip_norm, clip_count = total.detach(), hit if clip_count is None else clip_count + hit
             opt.step()
             last, step = loss, step + 1
         rec = {"epoch": epoch, "global_step": step, "train_loss": float(last.item()) if last is not None else None,
                "lr": float(opt.param_groups[0]["lr"])}
+        if clip_val is not None and clip_alg == "norm":               # norm of the epoch's last step before clipping; steps clipped so far
+            if torch_clip is None:
+                rec["grad_norm"], rec["clipped_steps"] = opt.grad_norm(), opt.clipped_steps()
+            else:
+                rec["grad_norm"] = float(clip_norm.item()) if clip_norm is not None else None
+                rec["clipped_steps"] = int(clip_count.item()) if clip_count is not None else 0
         if hasattr(opt, "skipped_steps"):                             # FusedAdam's overflow guard: one device read per epoch
             rec["skipped_steps"], rec["skipped_elements"] = opt.skipped_steps(), opt.nonfinite_skipped()
             seen = (history[-1].get("skipped_steps", 0) + history[-1].get("skipped_elements", 0)) if history else 0
