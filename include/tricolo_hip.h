@@ -698,7 +698,7 @@ int tri_adam_step_segments(float* p, const void* grad_ptrs, const long* grad_sta
                            const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
                            void* stream);
 
-/* ---- Gradient clipping, decided on the device (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; csrc/misc.hip) -------------- */
+/* ---- Gradient clipping, decided on the device (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; csrc/adam.hip) -------------- */
 /* Launch order of a clipped step: tri_adam_guard*, tri_adam_tick, tri_grad_sumsq*, tri_grad_clip_coef, tri_adam_step*_clipped.  Nothing
  * here uses an atomic or a ticket: the same input gives the same bits, also replayed from a HIP graph.
  * tri_grad_norm_blocks(n): how many doubles ONE tri_grad_sumsq / tri_grad_sumsq_segments call over n elements writes to `partial` - a

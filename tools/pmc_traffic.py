@@ -87,7 +87,7 @@ def main():
                       "write_bytes_per_launch": int(wt[k] / wc[k] * 1024)}
     # bytes of one training step: every kernel's total over the run / the number of steps the run executed (= launches of the fused
     # Adam kernel, one per step)
-    steps = max([v["dispatches"] for k, v in kernels.items() if k.startswith("adam_seg_kernel") or k.startswith("adam_kernel")] or [0])
+    steps = max([v["dispatches"] for k, v in kernels.items() if k.startswith(("adam_seg_kernel", "adam_flat_kernel"))] or [0])
     step_bytes = int(sum((v["fetch_bytes_per_launch"] + v["write_bytes_per_launch"]) * v["dispatches"] for v in kernels.values()) / steps) if steps else None
     json.dump({"step_bytes": step_bytes, "steps_in_run": steps, "method": f"two rocprofv3 runs of `python3 bench.py --steps 3 --warmup 2 --precision {mode} --full --modes '' --no-cpu-baseline`, one with "
                          "--pmc FETCH_SIZE, one with --pmc WRITE_SIZE (the TCC block cannot hold both); per-kernel mean over all dispatches of "

@@ -1251,7 +1251,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_krow_kernel(const KrowJobs 
 
 // Overflow note of the reduces (round 6): the reduce holds every FINAL gradient element in a register right before its only store, so the
 // optimizer's non-finite scan of these tensors (adam_guard_seg_kernel: one more read of 64 of the step's 74 MB of gradients, on the serial
-// tail of the step) is free here.  `note` = the optimizer's device record (misc.hip: [0] applied steps, [2] attempt flagged, [3] steps
+// tail of the step) is free here.  `note` = the optimizer's device record (adam.hip: [0] applied steps, [2] attempt flagged, [3] steps
 // skipped whole); a workgroup that stored an inf / NaN flags the current attempt exactly as the guard kernel does.
 __device__ __forceinline__ unsigned wgrad_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
 __device__ __forceinline__ void wgrad_note_bad(unsigned bad, int* note) {

@@ -1,5 +1,5 @@
 // Small kernels of the TriCoLo step (gfx950): error plumbing, layout converters (COO voxels -> dense masked grid,
-// NCHW images -> NHWC4), row L2-normalise forward/backward, column sums (bias gradients), fused Adam.
+// NCHW images -> NHWC4), row L2-normalise forward/backward, column sums (bias gradients).  The optimizer's kernels are in adam.hip.
 #include "common.h"
 #include "../../include/tricolo_hip.h"
 #include <stdio.h>
@@ -659,335 +659,4 @@ extern "C" int tri_cast_to_f32(const void* src, float* dst, long n, int act_fmt,
     if (n % 4) { tri_set_error("tri_cast_to_f32: n must be a multiple of 4"); return TRI_ERR_ARG; }
     TRI_ACT_DISPATCH(act_fmt, cast_to_f32_kernel<T><<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>((const T*)src, (float4*)dst, n / 4));
     return tri_check_launch("tri_cast_to_f32");
-}
-
-// ------------------------------------------------------------------------------------------------ fused Adam
-// torch.optim.Adam(lr, betas, eps, weight_decay) single-tensor update, L2-in-gradient (config.yaml:50-53,
-// tricolo_net.py:43-44).  `step` lives on the device (incremented by tri_adam_tick) so the launch is graph-replayable.
-// `step` is a device int[4]: [0] optimizer steps APPLIED (the t of the bias corrections), [1] gradient elements skipped by the per-element
-// guard below, [2] the attempt number (applied + skipped steps + 1) of the last step whose gradient tri_adam_guard* found non-finite,
-// [3] steps skipped WHOLE for that reason.  Per-step guard (VERDICT r3 item 9 / ADVICE r3): one inf / NaN in an f16 activation gradient
-// poisons the BatchNorm-backward sums and through them every gradient further down that tower, so skipping the bad ELEMENTS trains
-// the healthy towers on while one tower stands still.  tri_adam_guard* scans the step's gradient once (before the tick); a bad
-// gradient makes tri_adam_tick count a skipped step instead of an applied one and the update kernels leave p, m and v untouched -
-// what torch.cuda.amp.GradScaler does with an overflowed step.  All device-side: the decision replays inside a captured HIP graph.
-__global__ void adam_tick_kernel(int* step) {
-    const int attempt = step[0] + step[3] + 1;
-    if (step[2] == attempt) step[3] += 1;                          // the guard flagged this attempt: nothing is applied
-    else step[0] += 1;
-}
-extern "C" int tri_adam_tick(int* step, void* stream) {
-    adam_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(step);
-    return tri_check_launch("tri_adam_tick");
-}
-__device__ __forceinline__ bool adam_step_skipped(const int* step) { return step[2] == step[0] + step[3]; }   // (after the tick)
-__device__ __forceinline__ unsigned nonfinite_bits(const float4& v) {
-    const unsigned e = 0x7f800000u;
-    return (unsigned)((__builtin_bit_cast(unsigned, v.x) & e) == e) | (unsigned)((__builtin_bit_cast(unsigned, v.y) & e) == e) |
-           (unsigned)((__builtin_bit_cast(unsigned, v.z) & e) == e) | (unsigned)((__builtin_bit_cast(unsigned, v.w) & e) == e);
-}
-__global__ __launch_bounds__(256) void adam_guard_kernel(const float* __restrict__ g, long n, int* __restrict__ step) {
-    // scalar head up to the first 16-byte boundary, float4 body, scalar tail
-    long head = (long)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2, tail0 = head + n4 * 4;
-    const float4* body = (const float4*)(g + head);
-    unsigned bad = 0;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) bad |= nonfinite_bits(body[i]);
-    if (blockIdx.x == 0) {
-        if ((long)threadIdx.x < head) bad |= (unsigned)!__builtin_isfinite(g[threadIdx.x]);
-        if ((long)threadIdx.x < n - tail0) bad |= (unsigned)!__builtin_isfinite(g[tail0 + threadIdx.x]);
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicMax(step + 2, step[0] + step[3] + 1);
-}
-extern "C" int tri_adam_guard(const float* g, long n, int* step, void* stream) {
-    if ((uintptr_t)g & 3) { tri_set_error("tri_adam_guard: gradient not 4-byte aligned"); return TRI_ERR_ARG; }
-    adam_guard_kernel<<<ew_grid(n / 4 + 1), 256, 0, (hipStream_t)stream>>>(g, n, step);
-    return tri_check_launch("tri_adam_guard");
-}
-// bias corrections as torch computes them (Python doubles): 1 - beta^t in double, then step_size / bias_correction2_sqrt
-struct AdamCoef { float step_size, inv_sqrt_bc2; };
-__device__ __forceinline__ AdamCoef adam_coef(int t, float lr, const float* lr_dev, float b1, float b2) {
-    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-    const double l = lr_dev ? (double)*lr_dev : (double)lr;
-    AdamCoef c;
-    c.step_size = (float)(l / bc1);
-    c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    return c;
-}
-// Overflow guard of the 16-bit modes: activation gradients are stored in f16 under a static 2^12 scale; should one
-// overflow, the inf / NaN reaches a parameter gradient.  An element whose gradient is not finite is NOT applied - its parameter and
-// both moments keep their values, so a non-finite value can never enter the fp32 master weights or the Adam state, also inside a
-// replayed HIP graph - and counted in step[1] (FusedAdam.nonfinite_skipped() reads it).  This per-ELEMENT guard is the fallback of
-// callers that do not run tri_adam_guard* first; with the guard pass a bad gradient skips the whole step (see adam_tick_kernel).
-__device__ __forceinline__ void adam_note_bad(const int* step, int bad) {
-    if (bad) atomicAdd(const_cast<int*>(step) + 1, bad);
-}
-// The gradient term of the update: g * gmul + wd * p.  CLAMP (a separate instantiation, the clip_grad_value_ rule: tri_adam_step*_clipped with a
-// finite clip_value) limits the scaled gradient to [-clip_value, clip_value] BEFORE the weight decay joins it; a NaN passes through the
-// clamp, so the per-element guard below still refuses it.  Without CLAMP this is the one expression the update has always evaluated.
-template <bool CLAMP>
-__device__ __forceinline__ float adam_grad(float g, float gmul, float clip_value, float wd, float p) {
-    if constexpr (CLAMP) {
-        const float t = g * gmul;
-        return (t != t ? t : fminf(fmaxf(t, -clip_value), clip_value)) + wd * p;
-    } else {
-        return g * gmul + wd * p;
-    }
-}
-// One body for tri_adam_step and tri_adam_step_clipped: gmul is gscale there and gscale * coef here (formed once, in fp32, by the kernel).
-// i0 / stride: the grid-stride loop's start and step, taken in the kernel itself (blockDim folds there as it always has).
-template <bool CLAMP>
-__device__ __forceinline__ void adam_flat_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                               long n, const int* __restrict__ step, float lr, const float* __restrict__ lr_dev, float b1,
-                                               float b2, float eps, float wd, float gmul, float clip_value, long i0, long stride) {
-    if (adam_step_skipped(step)) return;
-    const AdamCoef co = adam_coef(*step, lr, lr_dev, b1, b2);
-    const float step_size = co.step_size, inv_sqrt_bc2 = co.inv_sqrt_bc2;
-    int bad = 0;
-    for (long i = i0; i < n; i += stride) {
-        float pi = p[i];
-        float gi = adam_grad<CLAMP>(g[i], gmul, clip_value, wd, pi);
-        if (!__builtin_isfinite(gi)) { ++bad; continue; }          // overflow guard: p, m, v of that element stay (see adam_note_bad)
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-    }
-    adam_note_bad(step, bad);
-}
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
-                            const int* __restrict__ step, float lr, const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                            float wd, float gscale) {
-    adam_flat_body<false>(p, g, m, v, n, step, lr, lr_dev, b1, b2, eps, wd, gscale, 0.f,
-                          (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-// coef_dev (DEVICE float, NULL = 1): the clipping coefficient tri_grad_clip_coef left in rec[1] - read at run time, so the decision replays
-// inside a captured HIP graph.  gscale * 1.0f is gscale: a step that does not clip takes the bits of adam_kernel.
-template <bool CLAMP>
-__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
-                                 const int* __restrict__ step, float lr, const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                 float wd, float gscale, const float* __restrict__ coef_dev, float clip_value) {
-    adam_flat_body<CLAMP>(p, g, m, v, n, step, lr, lr_dev, b1, b2, eps, wd, gscale * (coef_dev ? *coef_dev : 1.f), clip_value,
-                          (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-// Same update, gradients read in place from the per-parameter tensors autograd produced (segment table: device pointer and
-// flat start offset of every parameter, ascending) - no concatenation pass over the 74 MB of gradients first.  Four elements
-// per thread; segment sizes / starts are multiples of 4 and the gradient tensors 16-byte aligned (checked by the caller).
-#define ADAM_MAX_SEG 1024
-template <bool CLAMP>
-__device__ __forceinline__ void adam_seg_body(float* __restrict__ p, const float* const* __restrict__ gptr, const long* __restrict__ gstart,
-                                              int nseg, float* __restrict__ m, float* __restrict__ v, long n4, const int* __restrict__ step,
-                                              float lr, const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd, float gmul,
-                                              float clip_value, long i0, long stride) {
-    __shared__ long sstart[ADAM_MAX_SEG];
-    __shared__ const float* sptr[ADAM_MAX_SEG];
-    if (adam_step_skipped(step)) return;
-    for (int i = threadIdx.x; i < nseg; i += 256) { sstart[i] = gstart[i]; sptr[i] = gptr[i]; }
-    __syncthreads();
-    const AdamCoef co = adam_coef(*step, lr, lr_dev, b1, b2);
-    const float step_size = co.step_size, inv_sqrt_bc2 = co.inv_sqrt_bc2;
-    int bad = 0;
-    for (long i4 = i0; i4 < n4; i4 += stride) {
-        const long i = i4 * 4;
-        int lo = 0, hi = nseg - 1;                                  // last segment whose start is <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (sstart[mid] <= i) lo = mid; else hi = mid - 1;
-        }
-        const float* gs = sptr[lo];
-        if (!gs) continue;                                          // no gradient: torch.optim.Adam leaves p, m, v untouched
-        const float4 gv = *(const float4*)(gs + (i - sstart[lo]));
-        float4 pv = *(const float4*)(p + i), mv = *(const float4*)(m + i), vv = *(const float4*)(v + i);
-#define ADAM1(P, G, M, V)                                   \
-    {                                                       \
-        const float gi = adam_grad<CLAMP>(G, gmul, clip_value, wd, P); \
-        if (__builtin_isfinite(gi)) {                       \
-            M = b1 * M + (1.f - b1) * gi;                   \
-            V = b2 * V + (1.f - b2) * gi * gi;              \
-            P = P - step_size * M / (sqrtf(V) * inv_sqrt_bc2 + eps); \
-        } else ++bad;                                       \
-    }
-        ADAM1(pv.x, gv.x, mv.x, vv.x) ADAM1(pv.y, gv.y, mv.y, vv.y) ADAM1(pv.z, gv.z, mv.z, vv.z) ADAM1(pv.w, gv.w, mv.w, vv.w)
-#undef ADAM1
-        *(float4*)(p + i) = pv; *(float4*)(m + i) = mv; *(float4*)(v + i) = vv;
-    }
-    adam_note_bad(step, bad);
-}
-__global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, const float* const* __restrict__ gptr,
-                                                       const long* __restrict__ gstart, int nseg, float* __restrict__ m,
-                                                       float* __restrict__ v, long n4, const int* __restrict__ step, float lr,
-                                                       const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd,
-                                                       float gscale) {
-    adam_seg_body<false>(p, gptr, gstart, nseg, m, v, n4, step, lr, lr_dev, b1, b2, eps, wd, gscale, 0.f,
-                          (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-template <bool CLAMP>
-__global__ __launch_bounds__(256) void adam_seg_clip_kernel(float* __restrict__ p, const float* const* __restrict__ gptr,
-                                                            const long* __restrict__ gstart, int nseg, float* __restrict__ m,
-                                                            float* __restrict__ v, long n4, const int* __restrict__ step, float lr,
-                                                            const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd,
-                                                            float gscale, const float* __restrict__ coef_dev, float clip_value) {
-    adam_seg_body<CLAMP>(p, gptr, gstart, nseg, m, v, n4, step, lr, lr_dev, b1, b2, eps, wd, gscale * (coef_dev ? *coef_dev : 1.f), clip_value,
-                          (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-}
-__global__ __launch_bounds__(256) void adam_guard_seg_kernel(const float* const* __restrict__ gptr, const long* __restrict__ gstart, int nseg,
-                                                             long n4, int* __restrict__ step) {
-    __shared__ long sstart[ADAM_MAX_SEG];
-    __shared__ const float* sptr[ADAM_MAX_SEG];
-    for (int i = threadIdx.x; i < nseg; i += 256) { sstart[i] = gstart[i]; sptr[i] = gptr[i]; }
-    __syncthreads();
-    unsigned bad = 0;
-    for (long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x; i4 < n4; i4 += (long)gridDim.x * blockDim.x) {
-        const long i = i4 * 4;
-        int lo = 0, hi = nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (sstart[mid] <= i) lo = mid; else hi = mid - 1;
-        }
-        const float* gs = sptr[lo];
-        if (gs) bad |= nonfinite_bits(*(const float4*)(gs + (i - sstart[lo])));
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicMax(step + 2, step[0] + step[3] + 1);
-}
-extern "C" int tri_adam_guard_segments(const void* grad_ptrs, const long* grad_starts, int nseg, long n, int* step, void* stream) {
-    if (nseg < 1 || nseg > ADAM_MAX_SEG || n % 4) { tri_set_error("tri_adam_guard_segments: 1..1024 segments, n % 4 == 0"); return TRI_ERR_ARG; }
-    adam_guard_seg_kernel<<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>((const float* const*)grad_ptrs, grad_starts, nseg, n / 4, step);
-    return tri_check_launch("tri_adam_guard_segments");
-}
-extern "C" int tri_adam_step_segments(float* p, const void* grad_ptrs, const long* grad_starts, int nseg, float* m, float* v, long n,
-                                      const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
-                                      void* stream) {
-    if (nseg < 1 || nseg > ADAM_MAX_SEG || n % 4) { tri_set_error("tri_adam_step_segments: 1..1024 segments, n % 4 == 0"); return TRI_ERR_ARG; }
-    adam_seg_kernel<<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>(p, (const float* const*)grad_ptrs, grad_starts, nseg, m, v, n / 4, step, lr,
-                                                                      lr_dev, b1, b2, eps, wd, gscale);
-    return tri_check_launch("tri_adam_step_segments");
-}
-
-extern "C" int tri_adam_step(float* p, const float* g, float* m, float* v, long n, const int* step, float lr, const float* lr_dev,
-                             float b1, float b2, float eps, float wd, float gscale, void* stream) {
-    adam_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, step, lr, lr_dev, b1, b2, eps, wd, gscale);
-    return tri_check_launch("tri_adam_step");
-}
-
-// ------------------------------------------------------------------------------------------------ gradient clipping
-// Global-norm clipping decided on the device (torch.nn.utils.clip_grad_norm_'s rule), so that it replays inside a captured HIP graph and
-// sees the gradient AFTER the data-parallel all-reduce: (1) every workgroup sums (double)g * (double)g over its grid-stride share of the
-// elements - a function of n and the grid only - and stores ONE double in partial[blockIdx.x]; (2) one workgroup adds the partials in a
-// fixed order and leaves the norm and the coefficient in rec[0..1]; (3) the *_clipped update kernels above read rec[1].  No atomics and
-// no ticket anywhere (a ticket taken by 4,096 workgroups on one address cost 110 us in the guard): two runs give the same bits.
-__device__ __forceinline__ double block_sum_256(double acc) {       // 256 threads, fixed order; the sum is returned in thread 0
-    __shared__ double wsum[4];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return threadIdx.x == 0 ? (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]) : 0.0;
-}
-__device__ __forceinline__ double sumsq4(const float4& v) {
-    return ((double)v.x * (double)v.x + (double)v.y * (double)v.y) + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
-}
-static inline int grad_norm_grid(long n) { return ew_grid(n / 4 + 1); }         // (the guard's grid: the segmented form uses it too, one query)
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ partial) {
-    // scalar head up to the first 16-byte boundary, float4 body, scalar tail (adam_guard_kernel's split)
-    long head = (long)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2, tail0 = head + n4 * 4;
-    const float4* body = (const float4*)(g + head);
-    double acc = 0.0;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) acc += sumsq4(body[i]);
-    if (blockIdx.x == 0) {
-        if ((long)threadIdx.x < head) acc += (double)g[threadIdx.x] * (double)g[threadIdx.x];
-        if ((long)threadIdx.x < n - tail0) acc += (double)g[tail0 + threadIdx.x] * (double)g[tail0 + threadIdx.x];
-    }
-    acc = block_sum_256(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-__global__ __launch_bounds__(256) void grad_sumsq_seg_kernel(const float* const* __restrict__ gptr, const long* __restrict__ gstart, int nseg,
-                                                             long n4, double* __restrict__ partial) {
-    __shared__ long sstart[ADAM_MAX_SEG];
-    __shared__ const float* sptr[ADAM_MAX_SEG];
-    for (int i = threadIdx.x; i < nseg; i += 256) { sstart[i] = gstart[i]; sptr[i] = gptr[i]; }
-    __syncthreads();
-    double acc = 0.0;
-    for (long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x; i4 < n4; i4 += (long)gridDim.x * blockDim.x) {
-        const long i = i4 * 4;
-        int lo = 0, hi = nseg - 1;                                  // last segment whose start is <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (sstart[mid] <= i) lo = mid; else hi = mid - 1;
-        }
-        const float* gs = sptr[lo];
-        if (gs) acc += sumsq4(*(const float4*)(gs + (i - sstart[lo])));       // no gradient: not part of the norm (adam_seg_kernel skips it)
-    }
-    acc = block_sum_256(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __restrict__ partial, int nblk, float gscale, float max_norm,
-                                                             float* __restrict__ rec, int* __restrict__ clipped) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[i];
-    acc = block_sum_256(acc);
-    if (threadIdx.x != 0) return;
-    const double total = fabs((double)gscale) * sqrt(acc);
-    float c = 1.f;                                                  // inf / NaN norm: that step belongs to the guard, rec[0] says why
-    if (__builtin_isfinite(total)) {
-        const double cd = (double)max_norm / (total + 1e-6);
-        if (cd < 1.0) c = (float)cd;
-    }
-    rec[0] = (float)total;
-    rec[1] = c;
-    if (c < 1.f) clipped[0] += 1;
-}
-extern "C" int tri_grad_norm_blocks(long n) {
-    if (n < 0) { tri_set_error("tri_grad_norm_blocks: n < 0"); return TRI_ERR_ARG; }
-    return grad_norm_grid(n);
-}
-extern "C" int tri_grad_sumsq(const float* g, long n, double* partial, void* stream) {
-    if (n < 0 || !partial || (n > 0 && !g) || ((uintptr_t)g & 3)) {
-        tri_set_error("tri_grad_sumsq: n >= 0, a 4-byte aligned gradient and a partial buffer expected");
-        return TRI_ERR_ARG;
-    }
-    grad_sumsq_kernel<<<grad_norm_grid(n), 256, 0, (hipStream_t)stream>>>(g, n, partial);
-    return tri_check_launch("tri_grad_sumsq");
-}
-extern "C" int tri_grad_sumsq_segments(const void* grad_ptrs, const long* grad_starts, int nseg, long n, double* partial, void* stream) {
-    if (nseg < 1 || nseg > ADAM_MAX_SEG || n < 0 || n % 4 || !grad_ptrs || !grad_starts || !partial) {
-        tri_set_error("tri_grad_sumsq_segments: 1..1024 segments, n % 4 == 0, a partial buffer");
-        return TRI_ERR_ARG;
-    }
-    grad_sumsq_seg_kernel<<<grad_norm_grid(n), 256, 0, (hipStream_t)stream>>>((const float* const*)grad_ptrs, grad_starts, nseg, n / 4, partial);
-    return tri_check_launch("tri_grad_sumsq_segments");
-}
-extern "C" int tri_grad_clip_coef(const double* partial, int nblk, float gscale, float max_norm, float* rec, int* clipped, void* stream) {
-    if (nblk < 0 || (nblk > 0 && !partial) || !rec || !clipped || !(max_norm > 0.f)) {
-        tri_set_error("tri_grad_clip_coef: nblk >= 0, max_norm > 0 (inf measures only), rec and clipped expected");
-        return TRI_ERR_ARG;
-    }
-    grad_clip_coef_kernel<<<1, 256, 0, (hipStream_t)stream>>>(partial, nblk, gscale, max_norm, rec, clipped);
-    return tri_check_launch("tri_grad_clip_coef");
-}
-extern "C" int tri_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, const int* step, float lr, const float* lr_dev,
-                                     float b1, float b2, float eps, float wd, float gscale, const float* coef_dev, float clip_value,
-                                     void* stream) {
-    if (!(clip_value > 0.f)) { tri_set_error("tri_adam_step_clipped: clip_value > 0 (inf: no clamp)"); return TRI_ERR_ARG; }
-    if (__builtin_isinf(clip_value))
-        adam_clip_kernel<false><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, step, lr, lr_dev, b1, b2, eps, wd, gscale, coef_dev, clip_value);
-    else
-        adam_clip_kernel<true><<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, step, lr, lr_dev, b1, b2, eps, wd, gscale, coef_dev, clip_value);
-    return tri_check_launch("tri_adam_step_clipped");
-}
-extern "C" int tri_adam_step_segments_clipped(float* p, const void* grad_ptrs, const long* grad_starts, int nseg, float* m, float* v, long n,
-                                              const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd,
-                                              float gscale, const float* coef_dev, float clip_value, void* stream) {
-    if (nseg < 1 || nseg > ADAM_MAX_SEG || n % 4) { tri_set_error("tri_adam_step_segments_clipped: 1..1024 segments, n % 4 == 0"); return TRI_ERR_ARG; }
-    if (!(clip_value > 0.f)) { tri_set_error("tri_adam_step_segments_clipped: clip_value > 0 (inf: no clamp)"); return TRI_ERR_ARG; }
-    const float* const* gp = (const float* const*)grad_ptrs;
-    if (__builtin_isinf(clip_value))
-        adam_seg_clip_kernel<false><<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>(p, gp, grad_starts, nseg, m, v, n / 4, step, lr, lr_dev, b1, b2,
-                                                                                       eps, wd, gscale, coef_dev, clip_value);
-    else
-        adam_seg_clip_kernel<true><<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>(p, gp, grad_starts, nseg, m, v, n / 4, step, lr, lr_dev, b1, b2,
-                                                                                      eps, wd, gscale, coef_dev, clip_value);
-    return tri_check_launch("tri_adam_step_segments_clipped");
 }

@@ -88,7 +88,7 @@ class FusedAdam(torch.optim.Optimizer):
                 raise RuntimeError("FusedAdam: fp32 master parameters expected")
         dev = params[0].device
         self._params = params
-        # [0] applied steps, [1] skipped non-finite elements (fallback), [2] attempt flagged by the guard, [3] steps skipped whole (misc.hip)
+        # [0] applied steps, [1] skipped non-finite elements (fallback), [2] attempt flagged by the guard, [3] steps skipped whole (csrc/adam.hip)
         self._step_dev = torch.zeros((4,), dtype=torch.int32, device=dev)
         ops.one(dev)                                                             # the cached loss-gradient scalar: never first created inside a capture
         self._lr_dev = torch.zeros((1,), dtype=torch.float32, device=dev)
@@ -194,31 +194,35 @@ class FusedAdam(torch.optim.Optimizer):
         """Steps whose gradient norm exceeded max_grad_norm so far ("norm" algorithm; reads a device counter: synchronises)."""
         return 0 if self._clip_cnt is None else int(self._clip_cnt[0].item())
 
-    def _clip_coef(self, sums, grad_scale):
-        """The norm algorithm's two launches after the tick: sums(partial) -> number of partials it filled, then the finalize.
-        Returns the keyword arguments of the *_clipped update (coefficient read on the device / clamp value)."""
-        if self._clip_rec is None:
-            self._alloc_clip()
-        algorithm, value = self._clip
-        if algorithm == "value":
-            return dict(coef_dev=None, clip_value=value)
-        ops.grad_clip_coef(self._clip_partial, sums(self._clip_partial), grad_scale, value, self._clip_rec, self._clip_cnt)
-        return dict(coef_dev=self._clip_rec[1:], clip_value=math.inf)
+    def _launch_step(self, guard, sums, updates, grad_scale):
+        """The launches of one step, in their one order: guard, tick, (sum of squares, finalize,) update.  The three update paths hand in
+        theirs: guard() scans the step's gradient (None: nothing to scan); sums(partial) fills the partial sums of the gradient's squares
+        and returns how many it filled; updates = [(unclipped op, clipped op, arguments, keyword arguments)], one per update launch."""
+        if self._guard and guard is not None:
+            guard()
+        ops.adam_tick(self._step_dev)                                # step += 1 on the device (or skipped += 1), once per optimizer step
+        clip = {}
+        if self._clip is not None:                                   # the keyword arguments of the *_clipped update
+            if self._clip_rec is None:
+                self._alloc_clip()
+            algorithm, value = self._clip
+            if algorithm == "value":
+                clip = dict(coef_dev=None, clip_value=value)
+            else:                                                    # the coefficient is read on the device
+                ops.grad_clip_coef(self._clip_partial, sums(self._clip_partial), grad_scale, value, self._clip_rec, self._clip_cnt)
+                clip = dict(coef_dev=self._clip_rec[1:], clip_value=math.inf)
+        for plain, clipped, args, kw in updates:
+            (plain if self._clip is None else clipped)(*args, **kw, **clip)
 
     def _update_flat(self, g, group, b1, b2, grad_scale):
-        """guard, tick, (sum of squares, finalize,) update over one packed gradient."""
-        if self._guard:
-            ops.adam_guard(g, self._step_dev)                        # (after the all-reduce: every rank takes the same decision)
-        ops.adam_tick(self._step_dev)
+        """One packed gradient (after the all-reduce: every rank takes the same decisions)."""
         args = (self._flat_p, g, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"], group["weight_decay"], grad_scale)
-        if self._clip is None:
-            ops.adam_step(*args, lr_dev=self._lr_dev)
-        else:
-            ops.adam_step_clipped(*args, lr_dev=self._lr_dev, **self._clip_coef(lambda partial: ops.grad_sumsq(g, partial), grad_scale))
+        self._launch_step(lambda: ops.adam_guard(g, self._step_dev), lambda partial: ops.grad_sumsq(g, partial),
+                          [(ops.adam_step, ops.adam_step_clipped, args, dict(lr_dev=self._lr_dev))], grad_scale)
 
     def nonfinite_skipped(self) -> int:
         """Number of gradient elements the kernels refused so far because they were inf / NaN (f16 activation-gradient overflow guard:
-        such an element leaves its parameter and both moments untouched - csrc/misc.hip adam_note_bad).  Reads a device counter
+        such an element leaves its parameter and both moments untouched - csrc/adam.hip adam_note_bad).  Reads a device counter
         (synchronises); 0 in a healthy run.  A training loop should look at it now and then and lower ops.F16_GRAD_SCALE / switch to
         the bf16x3 mode when it grows."""
         return 0 if self._step_dev is None else int(self._step_dev[1].item())
@@ -369,19 +373,17 @@ class FusedAdam(torch.optim.Optimizer):
         if not capturing:
             slot[1] = torch.cuda.Event()
             slot[1].record()
-        if self._guard and gptrs:
-            ops.adam_guard_segments(self._seg_tab[n:n + len(gptrs)], self._seg_tab[2 * n:2 * n + len(gptrs)], gtotal, self._step_dev)
         # (round 6: the tick folded into the guard launch's last workgroup - one node less - was built and measured: 4,096 workgroups taking a
         #  ticket on one address cost 110 us; the kernel-argument form of the pointer table was dropped with it)
-        ops.adam_tick(self._step_dev)                       # step += 1 on the device (or skipped += 1), once per optimizer step
+        def guard():
+            ops.adam_guard_segments(self._seg_tab[n:n + len(gptrs)], self._seg_tab[2 * n:2 * n + len(gptrs)], gtotal, self._step_dev)
+
+        def sums(partial):                                  # the table the update reads: a parameter without a gradient is not in the norm
+            return ops.grad_sumsq_segments(self._seg_ptr, self._seg_start, self._flat_p.numel(), partial)
         args = (self._flat_p, self._seg_ptr, self._seg_start, self._flat_m, self._flat_v, self._step_dev, group["lr"], b1, b2, group["eps"],
                 group["weight_decay"], grad_scale)
-        if self._clip is None:
-            ops.adam_step_segments(*args, lr_dev=self._lr_dev)
-        else:
-            def sums(partial):                              # the table the update reads: a parameter without a gradient is not in the norm
-                return ops.grad_sumsq_segments(self._seg_ptr, self._seg_start, self._flat_p.numel(), partial)
-            ops.adam_step_segments_clipped(*args, lr_dev=self._lr_dev, **self._clip_coef(sums, grad_scale))
+        self._launch_step(guard if gptrs else None, sums,
+                          [(ops.adam_step_segments, ops.adam_step_segments_clipped, args, dict(lr_dev=self._lr_dev))], grad_scale)
         return True
 
     @torch.no_grad()
@@ -422,36 +424,22 @@ class FusedAdam(torch.optim.Optimizer):
             return loss
         if reduce_fn is not None:
             raise RuntimeError("reduce_fn needs flatten=True")
-        if self._guard:                                          # per-parameter path (never graph-captured): guard every gradient first
-            for group in self.param_groups:
-                for p in group["params"]:
-                    if p.grad is not None:
-                        ops.adam_guard(p.grad if p.grad.is_contiguous() else p.grad.contiguous(), self._step_dev)
-        ops.adam_tick(self._step_dev)
-        grads = {id(p): (p.grad if p.grad.is_contiguous() else p.grad.contiguous())
-                 for group in self.param_groups for p in group["params"] if p.grad is not None}
-        clip = None
-        if self._clip is not None:                               # ONE norm over every gradient: a sum-of-squares call each, one finalize
+        # per-parameter path (never graph-captured): ONE guard decision and ONE norm over every gradient - a launch per gradient each -, then
+        # an update launch per parameter (per-group lr by value)
+        grads = [(p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), group)
+                 for group in self.param_groups for p in group["params"] if p.grad is not None]
 
-            def sums(partial):
-                off = 0
-                for p in self._params:
-                    if id(p) in grads:
-                        nb = self._clip_blocks[id(p)]
-                        ops.grad_sumsq(grads[id(p)], partial[off:off + nb])
-                        off += nb
-                return off
-            clip = self._clip_coef(sums, grad_scale)
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                args = (p, grads[id(p)], st["exp_avg"], st["exp_avg_sq"], self._step_dev, group["lr"], b1, b2, group["eps"],
-                        group["weight_decay"], grad_scale)                   # per-group lr by value: this path is never graph-captured
-                if clip is None:
-                    ops.adam_step(*args)
-                else:
-                    ops.adam_step_clipped(*args, **clip)
+        def guard():
+            for _, g, _ in grads:
+                ops.adam_guard(g, self._step_dev)
+
+        def sums(partial):
+            off = 0
+            for p, g, _ in grads:
+                off += ops.grad_sumsq(g, partial[off:off + self._clip_blocks[id(p)]])
+            return off
+        updates = [(ops.adam_step, ops.adam_step_clipped,
+                    (p, g, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"], self._step_dev, group["lr"], *group["betas"], group["eps"],
+                     group["weight_decay"], grad_scale), {}) for p, g, group in grads]
+        self._launch_step(guard, sums, updates, grad_scale)
         return loss
