@@ -729,6 +729,26 @@ int tri_adam_step_segments_clipped(float* p, const void* grad_ptrs, const long* 
                                    const int* step, float lr, const float* lr_dev, float b1, float b2, float eps, float wd, float gscale,
                                    const float* coef_dev, float clip_value, void* stream);
 
+/* ---- Dynamic loss scaling, decided on the device (torch.cuda.amp.GradScaler's back-off and growth; csrc/adam.hip) --------------- */
+/* The step's backward is seeded with the DEVICE scalar state[0] = s instead of 1 (the loss kernels read their upstream gradient from a
+ * device pointer), so every gradient of the step carries s.  Launch order of such a step: tri_adam_guard*, tri_adam_tick,
+ * (tri_grad_sumsq*,) tri_loss_scale_step, tri_adam_step*_clipped with coef_dev = rec + 1.  It takes tri_grad_clip_coef's place: one
+ * workgroup adds partial[0 .. nblk) in that call's order and computes, in double and with s, 1 / s as state[0], state[1] hold them on entry,
+ *     total = |gscale| * (1 / s) * sqrt(sum),  rec[0] = (float)total          (the norm of the TRUE gradient)
+ *     c = max_norm / (total + 1e-6) when that is < 1, else 1; 1 when total is inf / NaN or nblk == 0
+ *     rec[1] = c * (1 / s),  clipped[0] += 1 when c < 1
+ * and then moves the scale the NEXT backward reads.  The step counts as skipped when step[2] == step[0] + step[3] (after the tick):
+ *     skipped:  streak = 0;  if s > min_scale: s = max(s / 2, min_scale), backoffs += 1
+ *     applied:  streak += 1; if streak >= growth_interval: streak = 0, and if s < max_scale: s = min(2 s, max_scale), growths += 1
+ *     state = {s, 1 / s}
+ * state: DEVICE float[2]; cnt: DEVICE int[3] = {streak, backoffs, growths}; step: DEVICE int[4], read only; partial may be NULL with
+ * nblk == 0 (no norm clipping: pass max_norm = +inf); rec: DEVICE float[2]; clipped: DEVICE int[1].  Every scale is a power of two, so
+ * 1 / s, c * (1 / s) and gscale * (1 / s) are exact, and with s = 1 rec holds tri_grad_clip_coef's bits.  No atomics: plain stores by one
+ * thread.  TRI_ERR_ARG: a NULL operand, nblk < 0, max_norm <= 0 or NaN, growth_interval < 1, min_scale or max_scale not a power of two in
+ * [2^-100, 2^100], min_scale > max_scale (state[0] is the caller's to keep inside them: it is not looked at on the host). */
+int tri_loss_scale_step(float* state, int* cnt, const int* step, const double* partial, int nblk, float gscale, float max_norm,
+                        int growth_interval, float min_scale, float max_scale, float* rec, int* clipped, void* stream);
+
 /* ---- Counter-based dropout (the Dropout(0.1) of the reference's clip_text.py / clip_img.py heads; csrc/dropout.hip) ------------ */
 /* used[0] = step[0]; step[0] += 1   (one thread; device int64 [1] each).  Stream-ordered: every later launch on `stream` that reads
  * `used` sees the value of THIS forward, also when the launches are replayed from a HIP graph. */

@@ -186,6 +186,7 @@ SIGNATURES = {
     "tri_grad_clip_coef": (I, [P, I, F, F, P, P, P]),
     "tri_adam_step_clipped": (I, [P, P, P, P, L, P, F, P, F, F, F, F, F, P, F, P]),
     "tri_adam_step_segments_clipped": (I, [P, P, P, I, P, P, L, P, F, P, F, F, F, F, F, P, F, P]),
+    "tri_loss_scale_step": (I, [P, P, P, P, I, F, F, I, F, F, P, P, P]),
     "tri_dropout_tick": (I, [P, P, P]),
     "tri_dropout_apply": (I, [P, P, L, I, C.c_uint, F, C.c_ulonglong, P, C.c_ulonglong, C.c_uint, P]),
 }

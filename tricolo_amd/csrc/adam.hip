@@ -1,4 +1,5 @@
-// The optimizer step of TriCoLo (gfx950): overflow guard, step counter, global-norm gradient clipping and the fused Adam update.
+// The optimizer step of TriCoLo (gfx950): overflow guard, step counter, global-norm gradient clipping, dynamic loss scaling and the fused
+// Adam update.
 // A gradient is read in one of two ways - flat, or through a (pointer, start) segment table - and each reader is written once
 // (FlatReader, SegReader); the guard and the sum of squares are two operations over either reader, the update has one kernel per reader.
 #include "common.h"
@@ -149,6 +150,45 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* __res
     rec[1] = c;
     if (c < 1.f) clipped[0] += 1;
 }
+// Dynamic loss scaling (torch.cuda.amp.GradScaler's back-off and growth), decided on the device.  The backward of the step was seeded with
+// state[0] = s (the loss kernels take their upstream gradient as a device scalar), so every gradient of the step carries s; this launch
+// stands where grad_clip_coef_kernel stands - after the tick, before the update - and does that kernel's work with 1 / s folded in:
+// rec[0] is the norm of the TRUE gradient, rec[1] = c / s the one multiplier the *_clipped update kernels read.  Then it moves the scale for
+// the NEXT backward: halved (down to min_scale) when the guard skipped this step, doubled (up to max_scale) after growth_interval applied
+// steps in a row.  Every scale is a power of two (the entry point checks the bounds), so 1 / s, c / s and gscale / s are exact and s = 1
+// leaves the bits grad_clip_coef_kernel leaves.  One workgroup, the partials added in that kernel's order; thread 0 writes, plain stores.
+__global__ __launch_bounds__(256) void loss_scale_step_kernel(float* __restrict__ state, int* __restrict__ cnt, const int* __restrict__ step,
+                                                              const double* __restrict__ partial, int nblk, float gscale, float max_norm,
+                                                              int growth_interval, float min_scale, float max_scale,
+                                                              float* __restrict__ rec, int* __restrict__ clipped) {
+    __shared__ double sh[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[i];
+    acc = block_sum_d(acc, sh);
+    if (threadIdx.x != 0) return;
+    float s = state[0];
+    const float inv = state[1];                                     // 1 / s of the scale this step's backward used
+    const double total = fabs((double)gscale) * (double)inv * sqrt(acc);
+    float c = 1.f;
+    if (nblk > 0 && __builtin_isfinite(total)) {
+        const double cd = (double)max_norm / (total + 1e-6);
+        if (cd < 1.0) c = (float)cd;
+    }
+    rec[0] = (float)total;
+    rec[1] = c * inv;
+    if (c < 1.f) clipped[0] += 1;
+    int streak = cnt[0];
+    if (adam_step_skipped(step)) {
+        streak = 0;
+        if (s > min_scale) { s = fmaxf(0.5f * s, min_scale); cnt[1] += 1; }
+    } else if (++streak >= growth_interval) {
+        streak = 0;
+        if (s < max_scale) { s = fminf(2.f * s, max_scale); cnt[2] += 1; }
+    }
+    cnt[0] = streak;
+    state[0] = s;
+    state[1] = 1.f / s;
+}
 
 // ------------------------------------------------------------------------------------------------ the update
 // bias corrections as torch computes them (Python doubles): 1 - beta^t in double, then step_size / bias_correction2_sqrt
@@ -290,6 +330,23 @@ extern "C" int tri_grad_clip_coef(const double* partial, int nblk, float gscale,
     }
     grad_clip_coef_kernel<<<1, 256, 0, (hipStream_t)stream>>>(partial, nblk, gscale, max_norm, rec, clipped);
     return tri_check_launch("tri_grad_clip_coef");
+}
+// a loss scale: a power of two whose reciprocal and whose products with a coefficient stay normal numbers
+static bool loss_scale_ok(float s) {
+    int e;
+    return s > 0.f && __builtin_isfinite(s) && frexpf(s, &e) == 0.5f && e >= -99 && e <= 101;
+}
+extern "C" int tri_loss_scale_step(float* state, int* cnt, const int* step, const double* partial, int nblk, float gscale, float max_norm,
+                                   int growth_interval, float min_scale, float max_scale, float* rec, int* clipped, void* stream) {
+    if (!state || !cnt || !step || !rec || !clipped || nblk < 0 || (nblk > 0 && !partial) || !(max_norm > 0.f) || growth_interval < 1 ||
+        !loss_scale_ok(min_scale) || !loss_scale_ok(max_scale) || min_scale > max_scale) {
+        tri_set_error("tri_loss_scale_step: state, cnt, step, rec and clipped, nblk >= 0, max_norm > 0 (inf: no norm clip), growth_interval >= 1 "
+                      "and min_scale <= max_scale, both powers of two in [2^-100, 2^100], expected");
+        return TRI_ERR_ARG;
+    }
+    loss_scale_step_kernel<<<1, 256, 0, (hipStream_t)stream>>>(state, cnt, step, partial, nblk, gscale, max_norm, growth_interval, min_scale,
+                                                               max_scale, rec, clipped);
+    return tri_check_launch("tri_loss_scale_step");
 }
 // An infinite clip_value is "no clamp": the CLAMP = false instantiation, which never looks at it.
 extern "C" int tri_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, const int* step, float lr, const float* lr_dev,

@@ -2135,6 +2135,28 @@ def adam_step_segments_clipped(p, grad_ptrs, grad_starts, m, v, step, lr, b1, b2
           "tri_adam_step_segments_clipped")
 
 
+# ------------------------------------------------------------------------------------------------ dynamic loss scaling (include/tricolo_hip.h)
+def check_loss_scale(value, what) -> float:
+    """A loss scale is a power of two in [2^-100, 2^100] (its reciprocal and its products with a coefficient are exact), as F16_GRAD_SCALE is."""
+    s = float(value)
+    if not (math.isfinite(s) and s > 0.0 and math.frexp(s)[0] == 0.5 and -99 <= math.frexp(s)[1] <= 101):
+        raise ValueError(f"{what}={value!r}: must be a power of two in [2^-100, 2^100] (the kernels divide it out exactly)")
+    return s
+
+
+def loss_scale_step(state, cnt, step, partial, nblk, gscale, max_norm, growth_interval, min_scale, max_scale, rec, clipped):
+    """One launch between adam_tick (and the sum-of-squares launches) and the *_clipped update.  With s = state[0], the scale the step's
+    backward was seeded with: rec[0] = |gscale| / s * sqrt(sum(partial[:nblk])), rec[1] = c / s with grad_clip_coef's c (1 when nblk == 0),
+    clipped[0] += 1 when c < 1; then the scale for the next backward: halved down to min_scale when the guard skipped this step, doubled up to
+    max_scale after growth_interval applied steps in a row.  state: fp32 [2] = {s, 1 / s}, cnt: int32 [3] = {streak, backoffs, growths},
+    step: adam_tick's int32 [4], rec: fp32 [2], clipped: int32 [1], all on the device; partial may be None with nblk == 0."""
+    assert state.dtype == torch.float32 and state.numel() >= 2 and cnt.dtype == torch.int32 and cnt.numel() >= 3
+    assert step.dtype == torch.int32 and step.numel() >= 4
+    assert rec.dtype == torch.float32 and rec.numel() >= 2 and clipped.dtype == torch.int32 and clipped.numel() >= 1
+    check(lib().tri_loss_scale_step(ptr(state), ptr(cnt), ptr(step), ptr(_partial(partial, nblk)) if nblk else None, nblk, gscale, max_norm,
+                                    int(growth_interval), min_scale, max_scale, ptr(rec), ptr(clipped), stream()), "tri_loss_scale_step")
+
+
 # ------------------------------------------------------------------------------------------------ counter-based dropout
 DROPOUT_BITS = 24                                                   # uniform bits compared with p (csrc/dropout.hip)
 _M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF

@@ -16,6 +16,11 @@ change ``param_groups[0]["lr"]`` as usual; eager steps pick it up by themselves,
 Gradient clipping (``max_grad_norm`` / ``clip_grad_value`` / ``set_gradient_clip``, Lightning's ``gradient_clip_val``) is decided on the
 device as the overflow guard is: guard, tick, sum of squares, finalize, update.  The norm is taken AFTER the data-parallel all-reduce and
 the whole step still replays from one HIP graph; with clipping off a step launches exactly what it launched before the option existed.
+
+Dynamic loss scaling (``loss_scale="dynamic"``) is the part of torch.cuda.amp.GradScaler the static f16 scale lacks: the backward is seeded
+with the device scalar ``backward_seed()`` = s, one launch between the tick and the update (tri_loss_scale_step, in the place of the
+clipping finalize) forms the update's multiplier c / s and halves s after a step the guard skipped, doubles it after
+``loss_scale_growth_interval`` applied steps in a row.  All on the device: a captured step backs off and recovers while it replays.
 """
 import math
 import os
@@ -30,13 +35,25 @@ _GUARD_NOTE = os.environ.get("TRICOLO_GUARD_NOTE", "1") != "0"     # A/B switch 
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, flatten=True, guard=True, max_grad_norm=None,
-                 clip_grad_value=None):
+                 clip_grad_value=None, loss_scale=None, loss_scale_init=1.0, loss_scale_growth_interval=2000, loss_scale_min=None,
+                 loss_scale_max=1.0):
         """guard: scan every step's gradient for inf / NaN first (one extra read of the gradients, ~10 us for 18.5 M parameters) and skip
         the WHOLE step when one is found - parameters, both moments and the step counter stay, `skipped_steps()` counts it (what
         torch.cuda.amp.GradScaler does with an overflowed step; the f16 mode's activation gradients can overflow).  guard=False keeps
         only the per-element fallback of the update kernels (a non-finite element leaves its own p, m, v alone).  Either way this
         DIFFERS from torch.optim.Adam, which would write the NaN into the weights (the reference's behaviour: a NaN surfaces as a NaN loss).
-        max_grad_norm / clip_grad_value: set_gradient_clip(value, "norm") / set_gradient_clip(value, "value"); at most one of them."""
+        max_grad_norm / clip_grad_value: set_gradient_clip(value, "norm") / set_gradient_clip(value, "value"); at most one of them.
+        loss_scale: None, or "dynamic" - every backward has to be seeded with backward_seed() then (train.fit and parallel.dp_training_step
+        do); the scale s starts at loss_scale_init, is halved (not below loss_scale_min) after a step the guard skipped and doubled (not
+        above loss_scale_max) after loss_scale_growth_interval applied steps in a row; the update divides s out again, so grad_norm(), both
+        clipping rules and the weights see true gradients.  All three are powers of two.  It multiplies ON TOP of the static f16 scale of
+        the towers (ops.F16_GRAD_SCALE): the defaults - min 1 / F16_GRAD_SCALE, the static scale fully undone, and max 1 - mean "back off
+        below the static scale and recover to it".  Whether a ceiling above 1 helps accuracy or only costs skipped steps has not been
+        measured; no claim is made.  Below 1 the scale eats into the head room of the f16 operands: s = 1 / F16_GRAD_SCALE takes
+        the static scale off the image and voxel towers' activation gradients altogether, and the GRU recurrence's backward, whose f16
+        operands carry a fixed 2^12 of their own, sees gate gradients s times smaller - small ones can then flush to zero in f16.  The
+        heads are not exposed (bf16 pieces, fp32's exponent range).  Read from the code, not measured: profiles/r25/NOTES_loss_scale.md.
+        Needs guard=True: the decision is read from the guard's record."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._guard = bool(guard)
         self._flatten = flatten and len(self.param_groups) == 1
@@ -49,6 +66,22 @@ class FusedAdam(torch.optim.Optimizer):
         self._seg_side = None
         self._clip = None                                                        # None | ("norm", max_norm) | ("value", clip_value)
         self._clip_partial = self._clip_rec = self._clip_cnt = self._clip_blocks = None
+        self._ls = None                                                          # None | dict(init, interval, min, max): dynamic loss scaling
+        self._ls_state = self._ls_cnt = self._ls_seed = None
+        if loss_scale is not None:
+            if loss_scale != "dynamic":
+                raise ValueError(f"FusedAdam: loss_scale={loss_scale!r} is not None or 'dynamic'")
+            if not self._guard:
+                raise ValueError("FusedAdam: loss_scale='dynamic' needs guard=True (the scale backs off on the guard's record of a skipped step)")
+            lo = ops.check_loss_scale(1.0 / ops.F16_GRAD_SCALE if loss_scale_min is None else loss_scale_min, "loss_scale_min")
+            hi = ops.check_loss_scale(loss_scale_max, "loss_scale_max")
+            init = ops.check_loss_scale(loss_scale_init, "loss_scale_init")
+            interval = int(loss_scale_growth_interval)
+            if interval != float(loss_scale_growth_interval) or interval < 1:
+                raise ValueError(f"FusedAdam: loss_scale_growth_interval={loss_scale_growth_interval!r}: a whole number >= 1 expected")
+            if not lo <= init <= hi:
+                raise ValueError(f"FusedAdam: loss_scale_min <= loss_scale_init <= loss_scale_max expected, not {lo} <= {init} <= {hi}")
+            self._ls = dict(init=init, interval=min(interval, 2 ** 31 - 1), min=lo, max=hi)
         if max_grad_norm is not None and clip_grad_value is not None:
             raise ValueError("FusedAdam: max_grad_norm and clip_grad_value exclude each other")
         if max_grad_norm is not None:
@@ -73,8 +106,9 @@ class FusedAdam(torch.optim.Optimizer):
         captures of the step the caller is going to make (each keeps one pinned gradient-pointer table; 32 are provided anyway)."""
         self._captures = max(int(captures), getattr(self, "_captures", 0))
         if self._step_dev is not None:
-            if self._clip is not None:
+            if self._clip is not None or self._ls is not None:
                 self._alloc_clip()
+            self._alloc_scale()
             while hasattr(self, "_seg_capture_pool") and len(self._seg_capture_pool) + len(self._seg_captured) < self._captures:
                 self._seg_capture_pool.append(torch.zeros((3 * len(self._params),), dtype=torch.int64).pin_memory())
             return
@@ -136,10 +170,11 @@ class FusedAdam(torch.optim.Optimizer):
             for p in params:
                 self.state[p]["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 self.state[p]["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        self._alloc_scale()
         if self._pending_state is not None:                          # load_state_dict() came before the first step
             sd, self._pending_state = self._pending_state, None
             self._restore(sd)
-        if self._clip is not None:
+        if self._clip is not None or self._ls is not None:
             self._alloc_clip()
 
     # ------------------------------------------------------------------ gradient clipping
@@ -194,13 +229,89 @@ class FusedAdam(torch.optim.Optimizer):
         """Steps whose gradient norm exceeded max_grad_norm so far ("norm" algorithm; reads a device counter: synchronises)."""
         return 0 if self._clip_cnt is None else int(self._clip_cnt[0].item())
 
+    # ------------------------------------------------------------------ dynamic loss scaling
+    @property
+    def dynamic_loss_scale(self) -> bool:
+        return self._ls is not None
+
+    @property
+    def loss_scale_min(self):
+        """The floor of the dynamic loss scale (None with the option off)."""
+        return None if self._ls is None else self._ls["min"]
+
+    def _alloc_scale(self):
+        """{s, 1 / s} and {streak, backoffs, growths} on the device.  They do not depend on the flat buffers, so backward_seed() may ask for
+        them ahead of prepare(): the first backward of a run comes before its first step."""
+        if self._ls is None or self._ls_state is not None:
+            return
+        first = next((p for g in self.param_groups for p in g["params"] if p.requires_grad), None)
+        if first is None:
+            return
+        if not first.is_cuda:
+            raise RuntimeError("FusedAdam: parameter is not on a GPU (no CPU fallback)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdam: the loss-scale buffers cannot be allocated inside a HIP-graph capture - call prepare() first")
+        s = self._ls["init"]
+        self._ls_state = torch.tensor([s, 1.0 / s], dtype=torch.float32, device=first.device)
+        self._ls_cnt = torch.zeros((3,), dtype=torch.int32, device=first.device)
+        self._ls_seed = self._ls_state[0]
+
+    def backward_seed(self) -> torch.Tensor:
+        """The 0-d device scalar to seed the step's backward with: loss.backward(gradient=opt.backward_seed()).  With loss_scale="dynamic" it
+        is a view of the scale the step kernel keeps on the device - hand over THIS tensor, not a copy: a captured backward then reads the
+        current scale on every replay.  With the option off it is ops.one(device)."""
+        if self._ls is None:
+            if self._params is not None:
+                return ops.one(self._params[0].device)
+            return ops.one(next(p for g in self.param_groups for p in g["params"]).device)
+        if self._ls_seed is None:
+            self._alloc_scale()
+        return self._ls_seed
+
+    def loss_scale(self):
+        """The scale the NEXT backward is seeded with (one device read: synchronises - once per epoch, not per step).  None with the option off."""
+        if self._ls is None:
+            return None
+        return self._ls["init"] if self._ls_state is None else float(self._ls_state[0].item())
+
+    def scale_backoffs(self) -> int:
+        """How often the scale was halved so far (a skipped step at loss_scale_min does not count; one device read)."""
+        return 0 if self._ls_cnt is None else int(self._ls_cnt[1].item())
+
+    def scale_growths(self) -> int:
+        """How often the scale was doubled so far (a full streak at loss_scale_max does not count; one device read)."""
+        return 0 if self._ls_cnt is None else int(self._ls_cnt[2].item())
+
+    def _restore_scale(self, rec):
+        """A checkpointed scale is brought inside THIS optimizer's [loss_scale_min, loss_scale_max] (the run that wrote it may have had a
+        wider range: the step kernel assumes min <= s <= max) and the streak below this optimizer's growth interval."""
+        s = ops.check_loss_scale(rec["scale"], "state_dict()['loss_scale']['scale']")
+        s = min(max(s, self._ls["min"]), self._ls["max"])
+        streak = min(max(int(rec.get("streak", 0)), 0), self._ls["interval"] - 1)
+        with torch.no_grad():
+            self._ls_state.copy_(torch.tensor([s, 1.0 / s], dtype=torch.float32))
+            self._ls_cnt.copy_(torch.tensor([streak, int(rec.get("backoffs", 0)), int(rec.get("growths", 0))], dtype=torch.int32))
+
     def _launch_step(self, guard, sums, updates, grad_scale):
         """The launches of one step, in their one order: guard, tick, (sum of squares, finalize,) update.  The three update paths hand in
         theirs: guard() scans the step's gradient (None: nothing to scan); sums(partial) fills the partial sums of the gradient's squares
-        and returns how many it filled; updates = [(unclipped op, clipped op, arguments, keyword arguments)], one per update launch."""
+        and returns how many it filled; updates = [(unclipped op, clipped op, arguments, keyword arguments)], one per update launch.
+        With loss_scale="dynamic" the finalize is ops.loss_scale_step, launched with either clipping rule and with none."""
+        # (the option is fixed at construction, so prepare() - which every caller has been through - has made its buffers)
+        assert self._ls is None or (self._ls_state is not None and self._clip_rec is not None), "FusedAdam: prepare() did not run"
         if self._guard and guard is not None:
             guard()
         ops.adam_tick(self._step_dev)                                # step += 1 on the device (or skipped += 1), once per optimizer step
+        if self._ls is not None:
+            algorithm, value = self._clip if self._clip is not None else (None, math.inf)
+            nblk = sums(self._clip_partial) if algorithm == "norm" else 0
+            ops.loss_scale_step(self._ls_state, self._ls_cnt, self._step_dev, self._clip_partial, nblk, grad_scale,
+                                value if algorithm == "norm" else math.inf, self._ls["interval"], self._ls["min"], self._ls["max"],
+                                self._clip_rec, self._clip_cnt)
+            clip = dict(coef_dev=self._clip_rec[1:], clip_value=value if algorithm == "value" else math.inf)
+            for _, clipped, args, kw in updates:                     # rec[1] = c / s: the scale is divided out where the coefficient is applied
+                clipped(*args, **kw, **clip)
+            return
         clip = {}
         if self._clip is not None:                                   # the keyword arguments of the *_clipped update
             if self._clip_rec is None:
@@ -258,6 +369,12 @@ class FusedAdam(torch.optim.Optimizer):
             # update: hand out copies (an optimizer that load_state_dict()s this dict in the same process keeps the tensors)
             sd["state"] = {k: {"step": step.clone(), "exp_avg": v["exp_avg"].clone(), "exp_avg_sq": v["exp_avg_sq"].clone()}
                            for k, v in sd["state"].items()}
+        if self._ls is not None:                                     # (a top-level key: torch.optim.Adam.load_state_dict ignores it)
+            if self._ls_state is None:
+                sd["loss_scale"] = {"scale": self._ls["init"], "streak": 0, "backoffs": 0, "growths": 0}
+            else:
+                streak, backoffs, growths = self._ls_cnt.tolist()
+                sd["loss_scale"] = {"scale": float(self._ls_state[0].item()), "streak": streak, "backoffs": backoffs, "growths": growths}
         return sd
 
     def _restore(self, sd):
@@ -282,6 +399,8 @@ class FusedAdam(torch.optim.Optimizer):
             # those steps would fall back to the per-element guard, and the attempt that reaches the old flag would be skipped although
             # its gradient is finite.  A restored optimizer starts a fresh record.
             self._step_dev[1:].zero_()
+        if self._ls is not None and sd.get("loss_scale") is not None:    # absent (a checkpoint of a run without the option): the scale stays
+            self._restore_scale(sd["loss_scale"])
         for g, gs in zip(self.param_groups, sd["param_groups"]):
             for k, v in gs.items():
                 if k != "params":

@@ -238,6 +238,13 @@ def backward_overlapped(total, split: BackwardSplit, order, flat=None):
     return flat
 
 
+def _refuse_dynamic_loss_scale(optimizer, where):
+    """The two-stage backward and GraphedDPStep seed their backward from the embedding gradient, not from the optimizer's scale."""
+    if getattr(optimizer, "dynamic_loss_scale", False):
+        raise RuntimeError(f"{where} does not support FusedAdam(loss_scale='dynamic'): its backward is not seeded with the optimizer's "
+                           "backward_seed() - use the plain dp_training_step, or leave optimizer.loss_scale unset")
+
+
 def dp_training_step(net, batch, optimizer=None, split: BackwardSplit | None = None):
     """One data-parallel training step of TriCoLoNet: local towers -> gathered embeddings -> global losses ->
     backward -> gradient all-reduce (-> optimizer step).  Returns the loss dict (identical on every rank).
@@ -250,11 +257,15 @@ def dp_training_step(net, batch, optimizer=None, split: BackwardSplit | None = N
     if split is not None and optimizer is not None and getattr(optimizer, "_flatten", False):
         # the two-stage backward whenever a split is installed (its gate refuses a plain backward); in a world of one the buckets
         # are simply not reduced
+        _refuse_dynamic_loss_scale(optimizer, "dp_training_step(split=...)")
         optimizer.prepare()
         flat = backward_overlapped(losses["train_loss/total_loss"], split, optimizer._params)
         optimizer.apply_flat(flat)
         return losses
-    losses["train_loss/total_loss"].backward(gradient=ops.one(losses["train_loss/total_loss"].device))
+    # FusedAdam(loss_scale="dynamic") seeds the backward with its device-side scale; the ranks agree on it, because the guard that moves it
+    # sees the all-reduced gradient
+    total = losses["train_loss/total_loss"]
+    total.backward(gradient=optimizer.backward_seed() if hasattr(optimizer, "backward_seed") else ops.one(total.device))
     if hasattr(net, "join_side_streams"):
         net.join_side_streams()                                              # (every tower's gradient kernels are ordered before the optimizer's)
     if optimizer is not None and getattr(optimizer, "_flatten", False):
@@ -290,6 +301,7 @@ class GraphedDPStep:
     def __init__(self, net, optimizer, batch, split: BackwardSplit | None = None):
         if not getattr(optimizer, "_flatten", False):
             raise RuntimeError("GraphedDPStep needs FusedAdam(flatten=True)")
+        _refuse_dynamic_loss_scale(optimizer, "GraphedDPStep")
         self.net, self.opt, self.split = net, optimizer, split
         world, rank = dist.get_world_size(), dist.get_rank()
         pool = torch.cuda.graph_pool_handle()

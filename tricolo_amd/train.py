@@ -81,7 +81,8 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
         for batch in train_batches(epoch):
             opt.zero_grad(set_to_none=True)
             loss = net.training_step(batch, step)
-            loss.backward(gradient=ops.one(loss.device))
+            # FusedAdam(loss_scale="dynamic") seeds the backward with its device-side scale; otherwise the seed is the cached one
+            loss.backward(gradient=opt.backward_seed() if hasattr(opt, "backward_seed") else ops.one(loss.device))
             if torch_clip is not None:
                 total = torch_clip([p for g in opt.param_groups for p in g["params"]], float(clip_val))
                 if clip_alg == "norm":                                # kept on the device: read once per epoch below
@@ -97,19 +98,31 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
             else:
                 rec["grad_norm"] = float(clip_norm.item()) if clip_norm is not None else None
                 rec["clipped_steps"] = int(clip_count.item()) if clip_count is not None else 0
+        # FusedAdam(loss_scale="dynamic"), given as +optimizer.loss_scale=dynamic: the scale the next backward is seeded with, and how often it
+        # was halved / doubled so far (device reads, once per epoch); None and no keys with the option off
+        scale = opt.loss_scale() if hasattr(opt, "loss_scale") else None
+        if scale is not None:
+            rec["loss_scale"], rec["scale_backoffs"], rec["scale_growths"] = scale, opt.scale_backoffs(), opt.scale_growths()
         if hasattr(opt, "skipped_steps"):                             # FusedAdam's overflow guard: one device read per epoch
             rec["skipped_steps"], rec["skipped_elements"] = opt.skipped_steps(), opt.nonfinite_skipped()
             seen = (history[-1].get("skipped_steps", 0) + history[-1].get("skipped_elements", 0)) if history else 0
             if rec["skipped_steps"] + rec["skipped_elements"] > seen:
-                log(f"[tricolo_amd.train] WARNING: {rec['skipped_steps']} optimizer step(s) / {rec['skipped_elements']} gradient element(s) skipped so far "
-                    "because of inf / NaN gradients (f16 activation-gradient overflow?): lower ops.F16_GRAD_SCALE or train in bf16x3")
+                if scale is None:
+                    log(f"[tricolo_amd.train] WARNING: {rec['skipped_steps']} optimizer step(s) / {rec['skipped_elements']} gradient element(s) skipped so far "
+                        "because of inf / NaN gradients (f16 activation-gradient overflow?): lower ops.F16_GRAD_SCALE or train in bf16x3")
+                else:
+                    log(f"[tricolo_amd.train] WARNING: {rec['skipped_steps']} optimizer step(s) / {rec['skipped_elements']} gradient element(s) skipped so far "
+                        f"because of inf / NaN gradients; the dynamic loss scale is now {scale:g} after {rec['scale_backoffs']} back-off(s) "
+                        f"(floor {opt.loss_scale_min:g})")
             # (a resumed run starts with an empty history: its first epoch counts from the checkpoint's global step - FusedAdam.load_state_dict
             #  zeroes the skip record -, and one skipped step of a one-step epoch is a transient, not a frozen run: ADVICE r5)
             prev_sk, prev_step = (history[-1].get("skipped_steps", 0), history[-1]["global_step"]) if history else (0, epoch_start_step)
-            if step - prev_step >= 2 and rec["skipped_steps"] - prev_sk >= step - prev_step:
+            # (with the dynamic loss scale an epoch of skipped steps is the scale on its way down: a frozen run only once it sits at its floor)
+            if step - prev_step >= 2 and rec["skipped_steps"] - prev_sk >= step - prev_step and (scale is None or scale <= opt.loss_scale_min):
                 # the static scale does not back off like GradScaler: a persistent overflow would freeze the weights silently
-                raise RuntimeError(f"every optimizer step of epoch {epoch} was skipped for non-finite gradients: lower TRICOLO_F16_GRAD_SCALE "
-                                   "(a power of two) or train in bf16x3")
+                raise RuntimeError(f"every optimizer step of epoch {epoch} was skipped for non-finite gradients"
+                                   + ("" if scale is None else f" with the dynamic loss scale at its floor {scale:g}")
+                                   + ": lower TRICOLO_F16_GRAD_SCALE (a power of two) or train in bf16x3")
         lr = cosine_lr(cfg, epoch)
         if lr is not None:
             for g in opt.param_groups:
