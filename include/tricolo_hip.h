@@ -468,6 +468,25 @@ int tri_ntxent_multi_fwd(const float* const* z, int M, int B, int D, float tempe
 int tri_ntxent_multi_bwd(const float* const* z, int M, int B, int D, float temperature, float alpha, int norm,
                          const float* const* dpair, const float* dtotal, float* const* dz, const void* workspace,
                          size_t workspace_bytes, void* stream);
+/* The same four calls with a LEARNABLE temperature (CLIP's logit scale): s = clamp(*logit_scale, 0, max_logit_scale), 1 / T = exp(s),
+ * logit_scale a DEVICE scalar that every kernel reads itself - a captured HIP graph follows the parameter from replay to replay.  The
+ * backward forms also WRITE (not accumulate) dlogit_scale (device scalar) = d / d logit_scale with the upstreams folded in: exactly 0
+ * outside [0, max_logit_scale], the boundaries included in the passing range (torch.clamp); row partials + a fixed-order double sum, no
+ * atomics, one launch more than the fixed backward.  Same ranges and dispatch as the fixed twins; workspace
+ * tri_ntxent_ls_workspace(M, B, D) (M = 2 for the single-pair calls), larger than the fixed one by [P][B] floats.  TRI_ERR_ARG for a NULL
+ * logit_scale, a NULL dlogit_scale in a call that forms gradients, a negative or non-finite max_logit_scale, a smaller workspace. */
+size_t tri_ntxent_ls_workspace(int M, int B, int D);
+int tri_ntxent_ls_fwd_bwd(const float* za, const float* zb, int B, int D, const float* logit_scale, float max_logit_scale, float alpha,
+                          int norm, float* loss, float* dza, float* dzb, float* dlogit_scale, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int tri_ntxent_ls_bwd(const float* za, const float* zb, int B, int D, const float* logit_scale, float max_logit_scale, float alpha, int norm,
+                      const float* dloss, float* dza, float* dzb, float* dlogit_scale, const void* workspace, size_t workspace_bytes,
+                      void* stream);
+int tri_ntxent_multi_ls_fwd(const float* const* z, int M, int B, int D, const float* logit_scale, float max_logit_scale, float alpha,
+                            int norm, float* losses, void* workspace, size_t workspace_bytes, void* stream);
+int tri_ntxent_multi_ls_bwd(const float* const* z, int M, int B, int D, const float* logit_scale, float max_logit_scale, float alpha,
+                            int norm, const float* const* dpair, const float* dtotal, float* const* dz, float* dlogit_scale,
+                            const void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Triplet loss, semi-hard with a hard fallback (tricolo/loss/triplet.py) ------------------------------------------------ */
 /* loss = mean over S = {(i, j), j != i : d[i][i] < d[i][j] < d[i][i] + margin} of d[i][i] - d[i][j] + margin, over

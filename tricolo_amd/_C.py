@@ -150,6 +150,12 @@ SIGNATURES = {
     "tri_ntxent_multi_workspace": (Z, [I, I, I]),
     "tri_ntxent_multi_fwd": (I, [P, I, I, I, F, F, I, P, P, Z, P]),
     "tri_ntxent_multi_bwd": (I, [P, I, I, I, F, F, I, P, P, P, P, Z, P]),
+    # learnable temperature: `float temperature` -> (logit_scale device scalar, float max_logit_scale); backward forms + dlogit_scale
+    "tri_ntxent_ls_workspace": (Z, [I, I, I]),
+    "tri_ntxent_ls_fwd_bwd": (I, [P, P, I, I, P, F, F, I, P, P, P, P, P, Z, P]),
+    "tri_ntxent_ls_bwd": (I, [P, P, I, I, P, F, F, I, P, P, P, P, P, Z, P]),
+    "tri_ntxent_multi_ls_fwd": (I, [P, I, I, I, P, F, F, I, P, P, Z, P]),
+    "tri_ntxent_multi_ls_bwd": (I, [P, I, I, I, P, F, F, I, P, P, P, P, P, Z, P]),
     "tri_triplet_workspace": (Z, [I, I]),
     "tri_triplet_fwd": (I, [P, P, I, I, DBL, P, P, P, Z, P]),
     "tri_triplet_bwd": (I, [P, P, I, I, DBL, P, P, P, P, Z, P]),

@@ -1457,10 +1457,30 @@ def gru_bias_grads(dbias):
     return out[0], out[1], out[2], out[3]
 
 
-def ntxent_fwd(za, zb, temperature, alpha, norm=True):
-    """Loss only; returns (loss, workspace) - hand the workspace to ntxent_bwd."""
+MAX_LOGIT_SCALE = math.log(100.0)                 # CLIP's clamp on its learned logit scale
+
+
+def _logit_scale(logit_scale, like):
+    """The learnable temperature of the NT-Xent calls: a 0-d / one-element fp32 tensor on the embeddings' device, read BY THE KERNELS
+    (1 / T = exp(clamp(logit_scale, 0, max_logit_scale))) - never copied, so a captured graph follows in-place updates."""
+    if not (isinstance(logit_scale, torch.Tensor) and logit_scale.numel() == 1 and logit_scale.dtype == torch.float32
+            and logit_scale.device == like.device):
+        raise RuntimeError("ntxent: logit_scale must be a one-element fp32 tensor on the embeddings' device")
+    return logit_scale.detach()
+
+
+def ntxent_fwd(za, zb, temperature, alpha, norm=True, *, logit_scale=None, max_logit_scale=MAX_LOGIT_SCALE):
+    """Loss only; returns (loss, workspace) - hand the workspace to ntxent_bwd.  With `logit_scale` (device scalar) the temperature is
+    learnable: exp(-clamp(logit_scale, 0, max_logit_scale)), read on the device; `temperature` is ignored and may be None."""
     B, D = za.shape
     loss = torch.empty((), dtype=torch.float32, device=za.device)
+    if logit_scale is not None:
+        nbytes = lib().tri_ntxent_ls_workspace(2, B, D)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=za.device)
+        check(lib().tri_ntxent_ls_fwd_bwd(ptr(_f32(za)), ptr(_f32(zb)), B, D, ptr(_logit_scale(logit_scale, za)), float(max_logit_scale),
+                                          float(alpha), 1 if norm else 0, ptr(loss), None, None, None, ptr(ws), nbytes, stream()),
+              "tri_ntxent_ls_fwd_bwd")
+        return loss, ws
     nbytes = lib().tri_ntxent_workspace(B, D)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=za.device)
     check(lib().tri_ntxent_fwd_bwd(ptr(_f32(za)), ptr(_f32(zb)), B, D, float(temperature), float(alpha), 1 if norm else 0, ptr(loss), None,
@@ -1468,10 +1488,15 @@ def ntxent_fwd(za, zb, temperature, alpha, norm=True):
     return loss, ws
 
 
-def ntxent_bwd(za, zb, ws, temperature, alpha, norm=True, dloss=None):
-    """(dza, dzb) times the upstream scalar dloss (device tensor) in one launch."""
+def ntxent_bwd(za, zb, ws, temperature, alpha, norm=True, dloss=None, *, logit_scale=None, max_logit_scale=MAX_LOGIT_SCALE):
+    """(dza, dzb) times the upstream scalar dloss (device tensor) in one launch; with `logit_scale` (dza, dzb, dlogit_scale) in two."""
     B, D = za.shape
     dza, dzb = torch.empty_like(za), torch.empty_like(zb)
+    if logit_scale is not None:
+        dls = torch.empty((), dtype=torch.float32, device=za.device)
+        check(lib().tri_ntxent_ls_bwd(ptr(_f32(za)), ptr(_f32(zb)), B, D, ptr(_logit_scale(logit_scale, za)), float(max_logit_scale), float(alpha),
+                                      1 if norm else 0, ptr(dloss), ptr(dza), ptr(dzb), ptr(dls), ptr(ws), ws.numel(), stream()), "tri_ntxent_ls_bwd")
+        return dza, dzb, dls
     check(lib().tri_ntxent_bwd(ptr(_f32(za)), ptr(_f32(zb)), B, D, float(temperature), float(alpha), 1 if norm else 0, ptr(dloss), ptr(dza),
                                ptr(dzb), ptr(ws), ws.numel(), stream()), "tri_ntxent_bwd")
     return dza, dzb
@@ -1531,29 +1556,47 @@ def _multi_args(zs, workspace=None, dpairs=None):
     return head, arr(dpairs) if dpairs is not None else None, dzs, arr(dzs)
 
 
-def ntxent_multi_fwd(zs, temperature, alpha, norm=True):
+def ntxent_multi_fwd(zs, temperature, alpha, norm=True, *, logit_scale=None, max_logit_scale=MAX_LOGIT_SCALE):
     """Every pair of the M = 2 / 3 embeddings `zs` at once: (losses [P + 1] = pair losses in combination order, then their
-    sum; workspace for ntxent_multi_bwd)."""
+    sum; workspace for ntxent_multi_bwd).  `logit_scale`: the learnable temperature, as in ntxent_fwd."""
+    if logit_scale is not None:
+        head, _, losses, ws = _multi_args(zs, lib().tri_ntxent_ls_workspace)
+        check(lib().tri_ntxent_multi_ls_fwd(*head, ptr(_logit_scale(logit_scale, zs[0])), float(max_logit_scale), float(alpha), 1 if norm else 0,
+                                            ptr(losses), ptr(ws), ws.numel(), stream()), "tri_ntxent_multi_ls_fwd")
+        return losses, ws
     head, _, losses, ws = _multi_args(zs, lib().tri_ntxent_multi_workspace)
     check(lib().tri_ntxent_multi_fwd(*head, float(temperature), float(alpha), 1 if norm else 0, ptr(losses), ptr(ws), ws.numel(),
                                      stream()), "tri_ntxent_multi_fwd")
     return losses, ws
 
 
-def ntxent_multi_bwd(zs, ws, temperature, alpha, norm=True, dpairs=None, dtotal=None):
+def ntxent_multi_bwd(zs, ws, temperature, alpha, norm=True, dpairs=None, dtotal=None, *, logit_scale=None, max_logit_scale=MAX_LOGIT_SCALE):
     """Gradients of all M embeddings in one launch; dpairs (list of 0-d device tensors or None) / dtotal are the upstream
-    gradients of the pair losses / of their sum."""
+    gradients of the pair losses / of their sum.  With `logit_scale` the list ends with dlogit_scale (0-d; one launch more)."""
     head, dp, dzs, dzp = _multi_args(zs, dpairs=dpairs)
+    if logit_scale is not None:
+        dls = torch.empty((), dtype=torch.float32, device=zs[0].device)
+        check(lib().tri_ntxent_multi_ls_bwd(*head, ptr(_logit_scale(logit_scale, zs[0])), float(max_logit_scale), float(alpha), 1 if norm else 0,
+                                            dp, ptr(dtotal), dzp, ptr(dls), ptr(ws), ws.numel(), stream()), "tri_ntxent_multi_ls_bwd")
+        return dzs + [dls]
     check(lib().tri_ntxent_multi_bwd(*head, float(temperature), float(alpha), 1 if norm else 0, dp, ptr(dtotal), dzp, ptr(ws),
                                      ws.numel(), stream()), "tri_ntxent_multi_bwd")
     return dzs
 
 
-def ntxent_fwd_bwd(za, zb, temperature, alpha, norm=True, want_grad=True):
+def ntxent_fwd_bwd(za, zb, temperature, alpha, norm=True, want_grad=True, *, logit_scale=None, max_logit_scale=MAX_LOGIT_SCALE):
     B, D = za.shape
     loss = torch.empty((), dtype=torch.float32, device=za.device)
     dza = torch.empty_like(za) if want_grad else None
     dzb = torch.empty_like(zb) if want_grad else None
+    if logit_scale is not None:                    # (loss, dza, dzb, dlogit_scale)
+        dls = torch.empty((), dtype=torch.float32, device=za.device) if want_grad else None
+        nbytes = lib().tri_ntxent_ls_workspace(2, B, D)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=za.device)
+        check(lib().tri_ntxent_ls_fwd_bwd(ptr(_f32(za.contiguous())), ptr(_f32(zb.contiguous())), B, D, ptr(_logit_scale(logit_scale, za)),
+                                          float(max_logit_scale), float(alpha), 1 if norm else 0, ptr(loss), ptr(dza), ptr(dzb), ptr(dls), ptr(ws),
+                                          nbytes, stream()), "tri_ntxent_ls_fwd_bwd")
+        return loss, dza, dzb, dls
     nbytes = lib().tri_ntxent_workspace(B, D)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=za.device)
     check(lib().tri_ntxent_fwd_bwd(ptr(_f32(za.contiguous())), ptr(_f32(zb.contiguous())), B, D, float(temperature), float(alpha),

@@ -77,6 +77,28 @@ class _AllGatherRows(torch.autograd.Function):
         return dout[r * ctx.rows:(r + 1) * ctx.rows].contiguous()
 
 
+class _ReplicatedGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, world):
+        ctx.inv = 1.0 / world
+        return p.view_as(p)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.inv, None
+
+
+def replicated(p: torch.Tensor) -> torch.Tensor:
+    """A parameter of the LOSS (NT-Xent's learnable logit scale), as the loss should read it: every rank evaluates the identical global
+    loss over the gathered embeddings, so every rank holds the parameter's FULL gradient - unlike a tower parameter, whose rank-local
+    gradients add up to it.  Its gradient is therefore divided by the world size on the way out, and the SUM all-reduce that follows
+    restores it (the ranks' values are bit-identical, so they stay replicated).  The same storage is returned (a view): the kernels
+    read the parameter itself.  Outside a data-parallel run, and in a world of one, `p` comes back as it is."""
+    if not is_dist() or dist.get_world_size() == 1:
+        return p
+    return _ReplicatedGrad.apply(p, dist.get_world_size())
+
+
 def gather_embeddings(output_dict: dict) -> dict:
     """{name: [B_local, D]} -> {name: [B_global, D]} with one fused all-gather (rank-major row order)."""
     if not is_dist():
@@ -333,7 +355,11 @@ class GraphedDPStep:
                 off += d
             losses = net._calculate_losses(glob, "train_loss")
             total = losses["train_loss/total_loss"]
-            (dfull,) = torch.autograd.grad(total, leaf)                 # identical on every rank: no reduce-scatter needed
+            # the loss's own parameters (NT-Xent's learnable logit scale) get their gradient here, the towers' from packed.backward below
+            lp = [p for p in net.loss_fn.parameters() if p.requires_grad] if isinstance(net.loss_fn, torch.nn.Module) else []
+            dfull, *dlp = torch.autograd.grad(total, [leaf] + lp)       # identical on every rank: no reduce-scatter needed
+            for p, g in zip(lp, dlp):
+                p.grad = g
             dlocal = dfull[rank * rows:(rank + 1) * rows].contiguous()
             if split is None:
                 packed.backward(dlocal)

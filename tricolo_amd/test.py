@@ -33,12 +33,16 @@ def select_checkpoint_keys(state_dict, cfg) -> dict:
     config has no such tower (test.py:21-27), and without the frozen CLIP weights a CLIP-text checkpoint carries (`.clip_model.`,
     checkpoint.py)."""
     out = {}
+    loss_cfg = cfg.loss.get(cfg.loss.name) if cfg.get("loss") is not None else None
+    learnable = bool(loss_cfg.get("learnable_temperature", False)) if loss_cfg is not None else False
     for key, value in state_dict.items():
         if cfg.model.image_encoder is None and "image_encoder" in key:
             continue
         if cfg.model.voxel_encoder is None and "voxel_encoder" in key:
             continue
         if ".clip_model." in key:
+            continue
+        if key == "loss_fn.logit_scale" and not learnable:            # a learned temperature plays no part in retrieval
             continue
         out[key] = value
     return out

@@ -49,12 +49,21 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
     net = net.to(device)
     opt = net.configure_optimizers()
     start_epoch, step = 0, 0
+    learnable = getattr(getattr(net, "loss_fn", None), "learnable_temperature", False)     # NTXentLoss(learnable_temperature=True)
     if ckpt_path is not None:                                         # train.py:41-45 -> trainer.fit(ckpt_path=...)
         assert os.path.exists(ckpt_path), "Error: Checkpoint path does not exists."
         doc = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        net.load_state_dict({k: v for k, v in extract_state_dict(doc).items() if ".clip_model." not in k}, strict=True)
+        sd = {k: v for k, v in extract_state_dict(doc).items() if ".clip_model." not in k}
+        net.load_state_dict(sd, strict=True)           # (a fixed-temperature checkpoint into a learnable run: NTXentLoss says so and starts from ln(1 / T))
         if doc.get("optimizer_states"):
-            opt.load_state_dict(doc["optimizer_states"][0])
+            osd = doc["optimizer_states"][0]
+            if learnable and "loss_fn.logit_scale" not in sd:
+                # the new parameter is the LAST one (loss_fn is registered behind the towers): every other index keeps its state, its own
+                # moments start from zero
+                groups = [dict(g) for g in osd["param_groups"]]
+                groups[-1]["params"] = list(groups[-1]["params"]) + [max(i for g in groups for i in g["params"]) + 1]
+                osd = dict(osd, param_groups=groups)
+            opt.load_state_dict(osd)
         start_epoch, step = int(doc.get("epoch", -1)) + 1, int(doc.get("global_step", 0))
     # Lightning's Trainer(gradient_clip_val=..., gradient_clip_algorithm="norm" | "value"), given as +trainer.gradient_clip_val=...:
     # FusedAdam clips inside its step (on the device, after the data-parallel all-reduce, graph-capturable); any other optimizer
@@ -92,6 +101,8 @@ def fit(net, cfg, train_batches, val_batches=None, device="cuda", ckpt_path: str
             last, step = loss, step + 1
         rec = {"epoch": epoch, "global_step": step, "train_loss": float(last.item()) if last is not None else None,
                "lr": float(opt.param_groups[0]["lr"])}
+        if learnable:                                                 # the trained temperature: one device read per epoch
+            rec["train_loss/temperature"] = net.loss_fn.current_temperature()
         if clip_val is not None and clip_alg == "norm":               # norm of the epoch's last step before clipping; steps clipped so far
             if torch_clip is None:
                 rec["grad_norm"], rec["clipped_steps"] = opt.grad_norm(), opt.clipped_steps()
